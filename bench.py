@@ -13,10 +13,16 @@ gradient materialised (N > 1: including the RCCL gradient all-reduce), on the ai
 workload of BASELINE.json (5233-node Delaunay mesh, 5 bi-stride levels, D=128, batch 8 PER GPU, fp32),
 inputs resident in HBM.  `value` = batch-8 steps per second summed over all ranks (weak scaling).
 
-Extra objects on the JSON line (rank 0, N = 1 only):
+A plain run sets up, warms up, times the steps and prints the JSON line.  `--full` adds the secondary figures, each measured
+after the timed region (rank 0, N = 1 only, unless noted):
   roofline      the L0 edge-aggregation kernel (HBM bound), timed with HIP events on its stream
   roofline_mfma the edge-MLP chain kernels (MFMA bound), same method
-  cpu_baseline  the CPU oracle (op-for-op restatement of the reference's PyTorch path) on the host cores
+  rollout       forward-only batch-1 rollout rate, eager and graph replay
+  optimizer_step, host_enqueue_ms_per_step (N > 1 too), distributed.gradient_allreduce_us (N > 1)
+  other_lines   the other BASELINE configurations (airfoil fp32 B=8 runs only)
+  cpu_baseline  the CPU oracle (op-for-op restatement of the reference's PyTorch path) on the host cores; the run asserts that
+                its loss equals the GPU loss
+`--dump-outputs DIR` writes what the last timed step computed (loss, prediction, parameter gradients) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -392,6 +398,32 @@ def timed_steps(step, warmup, steps):
     return steps / dt, dt / steps * 1e3, float(loss.detach())
 
 
+DUMP_MAX_BYTES = 60 << 20   # array data; the .npy headers stay well inside the 64 MB allowance
+
+
+def dump_outputs(out_dir, dp, loss):
+    """--dump-outputs: what the timed step hands its caller after the LAST timed step -- the loss, the prediction [B,N,C]
+    (fused step only) and every parameter gradient (`p.grad`) -- as out_dir/<name>.npy in float32.  Above DUMP_MAX_BYTES
+    every array is cut to the same fraction of its elements, a fixed seeded sample (flat indices in increasing order)."""
+    arrays = {"loss": loss.detach()}
+    if dp.fused is not None:
+        arrays["prediction"] = dp.fused.prediction()
+    for name, p in dp.model.named_parameters():
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        rng = np.random.default_rng(0)
+        for k, a in arrays.items():
+            keep = max(1, a.size * DUMP_MAX_BYTES // total)
+            if keep < a.size:
+                arrays[k] = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def other_lines(sim_airfoil, data_airfoil, loss_f32, warmup=10, steps=30):
     """The other BASELINE configurations on the driver's line (N = 1, default run only): each its own short timed region
     (10 warm-up + 30 steps, wall clock between two synchronisations), same step definition as `value`.
@@ -547,6 +579,12 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--roofline-only", action="store_true", help="only the kernel micro-loops (for rocprofv3 --pmc passes)")
     ap.add_argument("--no-other-lines", action="store_true", help="skip the short timed regions of the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the secondary figures: rooflines, rollout, optimizer step, host "
+                         "enqueue time, the other BASELINE configurations, the CPU baseline and its loss check (N > 1: the "
+                         "gradient all-reduce alone).  The --no-* options above drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the loss, prediction and parameter gradients of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -602,10 +640,12 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    h0 = time.perf_counter()                 # host cost of a step: enqueue 3 steps into an EMPTY queue, no synchronisation
-    for _ in range(3):
-        step()
-    host_ms = (time.perf_counter() - h0) / 3 * 1e3
+    host_ms = None
+    if args.full:
+        h0 = time.perf_counter()             # host cost of a step: enqueue 3 steps into an EMPTY queue, no synchronisation
+        for _ in range(3):
+            step()
+        host_ms = (time.perf_counter() - h0) / 3 * 1e3
     # ---- the timed region (contract): barrier + synchronize, EXACTLY `steps` steps, synchronize + barrier; max over ranks.
     # Inside it every step is also bracketed by HIP events on the launching stream (no synchronisation, a few hundred ns of
     # host time each): their MEDIAN is the per-step figure SURVEY.md section 8(d) asks for, reported next to the wall clock.
@@ -625,10 +665,16 @@ def main():
     elapsed = time.perf_counter() - t0
     per_step = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]) if args.steps else np.zeros(1)
     allreduce_us = None
+    if args.dump_outputs and rank == 0:      # before anything below runs more steps or reduces the gradient buffer again
+        dump_outputs(args.dump_outputs, dp, loss)
+    med_ms = float(np.median(per_step))
     if world > 1:
-        t = torch.tensor([elapsed, float(np.median(per_step)), host_ms], device="cuda", dtype=torch.float64)
+        t = torch.tensor([elapsed, med_ms, host_ms or 0.0], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, med_ms, host_ms = float(t[0]), float(t[1]), float(t[2])   # host enqueue: the slowest rank's
+        elapsed, med_ms = float(t[0]), float(t[1])
+        if args.full:
+            host_ms = float(t[2])            # host enqueue: the slowest rank's
+    if world > 1 and args.full:
         # the gradient message on its own: 20 back-to-back all-reduces of the flat gradient buffer inside one HIP event pair
         for _ in range(3):
             dist.all_reduce(dp.grads.flat)
@@ -642,8 +688,6 @@ def main():
         t = torch.tensor([ea.elapsed_time(eb) / 20 * 1e3], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         allreduce_us = float(t[0])
-    else:
-        med_ms = float(np.median(per_step))
 
     if rank == 0:
         n_params = sum(p.numel() for p in sim.parameters() if p.requires_grad)
@@ -670,8 +714,9 @@ def main():
                                    + ("consistent mesh" if consistent else "block-diagonal batch of different meshes"),
                        "levels_N_E": wl["levels"], "global_batch": args.batch * world, "parallelism": f"dp{world}",
                        "trainable_params": n_params, "loss": float(loss.detach())},
-            "host_enqueue_ms_per_step": host_ms,
         }
+        if args.full:
+            line["host_enqueue_ms_per_step"] = host_ms
         if world > 1:
             probe = getattr(dp.fused, "_ov_probe", None) if dp.fused is not None else None
             line["distributed"] = {"backend": backend, "rccl_ranks": world if backend == "nccl" else 0,
@@ -683,14 +728,15 @@ def main():
                                    "devices": torch.cuda.device_count(),
                                    "note": None if backend == "nccl" else
                                    "ranks share devices over gloo: a functional run of the N > 1 path, not a scaling measurement"}
-        if world == 1 and not args.no_roofline and consistent:
+        if args.full and world == 1 and not args.no_roofline and consistent:
             line["roofline"], line["roofline_mfma"] = roofline_objects(wl, args.batch, args.dtype)
             line["rollout"] = rollout_rate(sim, wl)
-        if world == 1:
+        if args.full and world == 1:
             line["optimizer_step"] = optimizer_step_time(dp)
-        if world == 1 and consistent and args.workload == "airfoil" and args.dtype == "f32" and args.batch == 8 and not args.no_other_lines:
+        if (args.full and world == 1 and consistent and args.workload == "airfoil" and args.dtype == "f32" and args.batch == 8
+                and not args.no_other_lines):
             line["other_lines"] = other_lines(sim, data, line["config"]["loss"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cb = cpu_baseline(args.workload, args.batch, steps=args.cpu_baseline_steps)
             if consistent:   # same seed, same workload: the oracle's loss IS the expected GPU loss (parity at bench size)
                 rel = abs(cb["loss"] - line["config"]["loss"]) / abs(cb["loss"])

@@ -84,7 +84,7 @@ def test_bench_n2_path_with_gloo_on_one_gpu(tmp_path):
     port = 29700 + os.getpid() % 200
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--workload", "cylinder"]
+           "--workload", "cylinder", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
