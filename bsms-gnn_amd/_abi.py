@@ -49,6 +49,9 @@ SIGNATURES = {
                              c_void_p, c_void_p]),
     "bsms_gmp_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, PP, c_void_p,
                              c_void_p, c_void_p, PP, c_void_p]),
+    "bsms_gmp_pos_work_bytes": (c_size_t, [c_i64, c_i64, c_i64]),
+    "bsms_gmp_bwd_pos": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, PP, c_void_p,
+                                 c_void_p, c_void_p, PP, c_void_p, c_void_p, c_void_p]),
     "bsms_bsgmp_saved_bytes": (c_size_t, [PP, c_int, c_i64, c_i64, c_i64, c_int]),
     "bsms_bsgmp_work_bytes": (c_size_t, [PP, c_int, c_i64, c_i64, c_i64, c_int]),
     "bsms_bsgmp_infer_work_bytes": (c_size_t, [PP, c_int, c_i64, c_i64, c_i64, c_int]),
@@ -67,6 +70,9 @@ SIGNATURES = {
                                   c_void_p, c_void_p, PP, c_int, c_int, c_void_p]),
     "bsms_bsgmp_bwd_ev": (c_int, [PP, PP, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, PP, c_void_p,
                                   c_void_p, c_void_p, PP, c_int, c_int, PP, c_void_p]),
+    "bsms_bsgmp_pos_work_bytes": (c_size_t, [PP, c_int, c_i64, c_i64]),
+    "bsms_bsgmp_bwd_pos": (c_int, [PP, PP, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, PP, c_void_p,
+                                   c_void_p, c_void_p, PP, c_int, c_void_p, c_void_p, c_void_p]),
     "bsms_side_lanes_join": (c_int, [c_void_p]),
     "bsms_streams_overlap": (c_int, [c_void_p, c_void_p]),
     "bsms_sim_work_bytes": (c_size_t, [c_i64]),

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libbsms_hip.so")
-SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip"]
+SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip"]
 # csrc/experiments/*.hip (the fp32 fused edge backward, efuse32.hip) are NOT part of the product library: profiles/build_efv.sh
 # compiles them into the experiment builds (-DBSMS_EXPERIMENTS), where gmp.hip / chain.hip keep their hooks
 HEADERS = ["common.h", "chain.h", "chain_dev.h", os.path.join("..", "..", "include", "bsms_hip.h")]

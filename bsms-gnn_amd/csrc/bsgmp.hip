@@ -286,10 +286,60 @@ extern "C" int bsms_bsgmp_bwd_ex(const bsms_plan_t* const* plans, const float* c
                            precision, flags, nullptr, stream);
 }
 
+namespace {
+// pos_work of bsms_bsgmp_bwd_pos: the edge scratch of the largest level, then the position gradients of levels 1..L
+struct PosWork {
+  float* scratch;
+  float* g[kMaxLevels + 1];
+  size_t bytes;
+};
+PosWork carve_pos_work(void* base, const Shape& s) {
+  Carve c(base);
+  PosWork w{};
+  size_t sc = 0;
+  for (int i = 0; i <= s.L; ++i) sc = std::max(sc, pos_edge_scratch_bytes(s.B, s.E[i], s.p));
+  w.scratch = reinterpret_cast<float*>(c.bytes(std::max<size_t>(sc, 256)));
+  for (int i = 1; i <= s.L; ++i) w.g[i] = c.floats(size_t(s.B) * s.N[i] * s.p);   // B rows: also covers a shared pos (1 row)
+  w.bytes = c.off;
+  return w;
+}
+
+int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
+                   const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
+                   const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
+                   int precision, int flags, void* const* block_done_events, float* grad_pos, void* pos_work, hipStream_t st);
+}  // namespace
+
+extern "C" size_t bsms_bsgmp_pos_work_bytes(const bsms_plan_t* const* plans, int L, int64_t B, int64_t p) {
+  Shape s;
+  if (B < 0 || p < 1 || p > 7 || make_shape(plans, L, B, 128, p, 1, &s, "bsgmp_pos_work_bytes")) return 0;
+  return carve_pos_work(nullptr, s).bytes;
+}
+
+extern "C" int bsms_bsgmp_bwd_pos(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
+                                  const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
+                                  const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
+                                  int precision, float* grad_pos, void* pos_work, bsms_stream_t stream) {
+  BSMS_REQUIRE(p >= 1 && p <= 7, BSMS_E_INVALID_ARG, "bsgmp_bwd_pos: pos_dim=%lld (1..7)", (long long)p);
+  BSMS_REQUIRE(!grad_pos || pos_work, BSMS_E_INVALID_ARG, "bsgmp_bwd_pos: grad_pos needs pos_work (bsms_bsgmp_pos_work_bytes)");
+  return bsgmp_bwd_impl(plans, ew, L, h, pos, grad_out, B, D, p, pos_batch_stride, hidden, params, saved, work, grad_h, grads,
+                        precision, 0, nullptr, grad_pos, pos_work, as_stream(stream));
+}
+
 extern "C" int bsms_bsgmp_bwd_ev(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
                                  const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
                                  const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
                                  int precision, int flags, void* const* block_done_events, bsms_stream_t stream) {
+  return bsgmp_bwd_impl(plans, ew, L, h, pos, grad_out, B, D, p, pos_batch_stride, hidden, params, saved, work, grad_h, grads,
+                        precision, flags, block_done_events, nullptr, nullptr, as_stream(stream));
+}
+
+namespace {
+int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
+                   const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
+                   const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
+                   int precision, int flags, void* const* block_done_events, float* grad_pos, void* pos_work, hipStream_t st) {
+  bsms_stream_t stream = st;
   Shape s;
   int rc = make_shape(plans, L, B, D, p, hidden, &s, "bsgmp_bwd");
   if (rc) return rc;
@@ -297,9 +347,17 @@ extern "C" int bsms_bsgmp_bwd_ev(const bsms_plan_t* const* plans, const float* c
   s.prec = precision;
   BSMS_REQUIRE(h && pos && grad_out && params && saved && work && grad_h && grads && (ew || L == 0), BSMS_E_INVALID_ARG,
                "bsgmp_bwd: null argument");
-  hipStream_t st = as_stream(stream);
   Work w = carve_work(work, s);
   Saved v = carve_saved(const_cast<void*>(saved), s, true);
+  // position gradients (bsms_bsgmp_bwd_pos): gp[l] of level l collects its up block, the adjoint of restrict_l applied to
+  // gp[l + 1] and its down block, in that order -- complete when down block l is done, which is when level l - 1 needs it
+  PosWork pw = carve_pos_work(grad_pos ? pos_work : nullptr, s);
+  float* gp[kMaxLevels + 1] = {};
+  if (grad_pos) {
+    gp[0] = grad_pos;
+    for (int i = 1; i <= L; ++i) gp[i] = pw.g[i];
+  }
+  const int64_t posB = pos_batch_stride ? B : 1;
   const float* pos_l[kMaxLevels + 1];
   int64_t pstride_l[kMaxLevels + 1];
   const float* hin_l[kMaxLevels + 1];
@@ -317,7 +375,7 @@ extern "C" int bsms_bsgmp_bwd_ev(const bsms_plan_t* const* plans, const float* c
   if ((rc = side_lane(&lane0, 0, st)) || (rc = side_lane(&lane1, 1, st))) return rc;
   int nblk = 0;
   bool marked[2] = {false, false};   // slots this call has marked (gmp_bwd_core marks both lanes of its slot)
-  auto run_block = [&](int level, const float* x, const float* g_in, int k, float* gx) -> int {
+  auto run_block = [&](int level, const float* x, const float* g_in, int k, float* gx, bool pos_acc) -> int {
     const int slot = nblk & 1;
     int r;
     void* const own = w.gmp_blk[nblk];   // this block's own scratch set, or null: alternate between the two shared ones
@@ -326,7 +384,8 @@ extern "C" int bsms_bsgmp_bwd_ev(const bsms_plan_t* const* plans, const float* c
     ++nblk;
     marked[slot] = true;
     if ((r = gmp_bwd_core(plans[level], x, pos_l[level], g_in, B, D, p, pstride_l[level], hidden, block(params, k, hidden), v.gmp[k],
-                          own ? own : (slot ? w.gmp_b : w.gmp), gx, block(grads, k, hidden), slot, st, precision))) return r;
+                          own ? own : (slot ? w.gmp_b : w.gmp), gx, block(grads, k, hidden), slot, st, precision, gp[level],
+                          pw.scratch, pos_acc))) return r;
     // Gradient-bucket hand-off (bsms_bsgmp_bwd_ev): lane 1's mark of this block covers lane 0's (gmp_marks_chained) and both
     // lanes are in-order streams, so an event recorded on lane 1 HERE completes when every weight gradient of this block,
     // of the blocks before it and of anything queued on the lanes earlier (a deferred bsms_mlp_bwd_ex) has been written.
@@ -344,7 +403,7 @@ extern "C" int bsms_bsgmp_bwd_ev(const bsms_plan_t* const* plans, const float* c
     const int d = L - 1 - i;
     skip_grad[d] = g;      // level 0: the caller's grad_out; deeper: w.skip[d], written by the level above
     float* gu = w.a[0];    // gradient w.r.t. the up block's input u_d
-    if ((rc = run_block(d, v.upin[d], g, L + 1 + i, gu))) return rc;
+    if ((rc = run_block(d, v.upin[d], g, L + 1 + i, gu, false))) return rc;
     // adjoint of prolong_d: a restrict-shaped gather onto level d + 1, kept for that level's skip connection
     float* gnext = (d + 1 < L) ? w.skip[d + 1] : w.a[1];
     if ((rc = bsms_edge_conv(plans[d], gu, B, D, ew[d], 1, 1, gnext, stream))) return rc;
@@ -352,14 +411,16 @@ extern "C" int bsms_bsgmp_bwd_ev(const bsms_plan_t* const* plans, const float* c
   }
   // bottom block
   float* gb = w.a[0];
-  if ((rc = run_block(L, hin_l[L], g, L, (L == 0) ? grad_h : gb))) return rc;
+  if ((rc = run_block(L, hin_l[L], g, L, (L == 0) ? grad_h : gb, false))) return rc;
   const float* gl = gb;
   for (int i = L - 1; i >= 0; --i) {
     // adjoint of restrict_i, plus the gradient that arrived at the skip connection of level i (fused add)
     float* gs = w.a[1];
     if ((rc = edge_conv_add(plans[i], gl, B, D, ew[i], 0, 1, gs, skip_grad[i], st))) return rc;
+    // adjoint of the position restriction pos_{i+1} = restrict_i(pos_i), added to what the up block left in gp[i]
+    if (grad_pos && (rc = edge_conv_add(plans[i], gp[i + 1], posB, p, ew[i], 0, 1, gp[i], gp[i], st))) return rc;
     float* gx = (i == 0) ? grad_h : w.a[0];
-    if ((rc = run_block(i, hin_l[i], gs, i, gx))) return rc;
+    if ((rc = run_block(i, hin_l[i], gs, i, gx, true))) return rc;
     gl = gx;
   }
   // every weight gradient has to be complete when the call returns -- unless the caller has more work for this stream
@@ -369,3 +430,4 @@ extern "C" int bsms_bsgmp_bwd_ev(const bsms_plan_t* const* plans, const float* c
     if (marked[slot] && ((!gmp_marks_chained() && (rc = side_wait_mark(lane0, slot, st))) || (rc = side_wait_mark(lane1, slot, st)))) return rc;
   return BSMS_OK;
 }
+}  // namespace

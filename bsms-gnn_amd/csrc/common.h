@@ -108,7 +108,16 @@ int gmp_fwd_core(const bsms_plan* plan, const float* x, const float* pos, int64_
 bool gmp_marks_chained();   // gmp.hip: waiting for lane 1's mark of a slot is enough
 int gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, const float* grad_out, int64_t B, int64_t D,
                  int64_t p, int64_t pos_bstride, int hidden, const float* const* params, const void* saved, void* work,
-                 float* grad_x, float* const* grads, int defer_slot, hipStream_t stream, int precision = BSMS_F32);
+                 float* grad_x, float* const* grads, int defer_slot, hipStream_t stream, int precision = BSMS_F32,
+                 float* grad_pos = nullptr, void* pos_work = nullptr, bool pos_accumulate = false);
+// posgrad.hip: the position gradient of one GMP block from its first edge gradient gE[0] (plan order; bf16 rows when
+// `g_bf16`) and the saved fiber rows; `scratch` holds pos_edge_scratch_bytes(B, E, p).  grad_pos [B,N,p] (pos_bstride != 0)
+// or [N,p] (0, summed over the batch) is overwritten, or added to when `accumulate`.
+size_t pos_edge_scratch_bytes(int64_t B, int64_t E, int64_t p);
+int gmp_pos_grad(const bsms_plan* plan, const void* gE0, bool g_bf16, const float* fiber, const float* W0_edge, int64_t B,
+                 int64_t D, int64_t p, int64_t pos_bstride, float* grad_pos, bool accumulate, float* scratch, hipStream_t s);
+// out [R,K] = G [R,D] . W[:, 0:K] (W [D,K] row-major): the input gradient of an MLP whose first Linear is narrow (K <= 8)
+int narrow_input_grad(const float* G, int64_t R, int64_t D, const float* W, int K, float* out, hipStream_t s);
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 // bsms_plan_concat (plan.hip: host side; rowsum.hip: the kernel -- plan.hip is also compiled as plain C++ for the sanitizer build):

@@ -386,6 +386,21 @@ extern "C" int bsms_gmp_bwd(const bsms_plan_t* plan, const float* x, const float
                             as_stream(stream), BSMS_F32);
 }
 
+extern "C" size_t bsms_gmp_pos_work_bytes(int64_t B, int64_t E, int64_t p) {
+  if (B < 0 || E < 0 || p < 1 || p > 7) return 0;
+  return std::max<size_t>(pos_edge_scratch_bytes(B, E, p), 256);
+}
+
+extern "C" int bsms_gmp_bwd_pos(const bsms_plan_t* plan, const float* x, const float* pos, const float* grad_out, int64_t B,
+                                int64_t D, int64_t p, int64_t pos_bstride, int H, const float* const* params,
+                                const void* saved, void* work, float* grad_x, float* const* grads, float* grad_pos, void* pos_work,
+                                bsms_stream_t stream) {
+  BSMS_REQUIRE(p >= 1 && p <= 7, BSMS_E_INVALID_ARG, "gmp_bwd_pos: pos_dim=%lld (1..7)", (long long)p);
+  BSMS_REQUIRE(!grad_pos || pos_work, BSMS_E_INVALID_ARG, "gmp_bwd_pos: grad_pos needs pos_work (bsms_gmp_pos_work_bytes)");
+  return bsms::gmp_bwd_core(plan, x, pos, grad_out, B, D, p, pos_bstride, H, params, saved, work, grad_x, grads, -1,
+                            as_stream(stream), BSMS_F32, grad_pos, pos_work, false);
+}
+
 namespace {
 // joins (or marks) the side lanes on EVERY exit path of gmp_bwd_core: an error return between fork and join would
 // otherwise leave the lane dangling, which also breaks an in-progress HIP-graph capture
@@ -409,7 +424,8 @@ bool bsms::gmp_marks_chained() { return !(g_debug_flags & 8) && !(g_debug_flags 
 
 int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, const float* grad_out, int64_t B, int64_t D,
                        int64_t p, int64_t pos_bstride, int H, const float* const* params, const void* saved, void* work,
-                       float* grad_x, float* const* grads, int defer_slot, hipStream_t s, int precision) {
+                       float* grad_x, float* const* grads, int defer_slot, hipStream_t s, int precision, float* grad_pos,
+                       void* pos_work, bool pos_accumulate) {
   int rc = check_gmp(plan, B, D, p, H, "gmp_bwd");
   if (rc) return rc;
   const bool bf = precision != BSMS_F32, bfn = precision == BSMS_BF16_NODES;
@@ -606,6 +622,9 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
     a.y = grad_x; a.accumulate = 1;
     if ((rc = launch_chain_fwd((int)D, IN_ROWS2, OUT_PLAIN, a, s))) return rc;
   }
+  // position gradient (posgrad.hip): on the caller's stream, so gE[0] is read before a later block reuses this scratch set
+  if (grad_pos && (rc = gmp_pos_grad(plan, wk.gE[0], bf, sv.e_fiber, params[2 * nl], B, D, p, pos_bstride, grad_pos, pos_accumulate,
+                                     reinterpret_cast<float*>(pos_work), s))) return rc;
   if (defer_slot >= 0 && scope1.lane && scope2.lane) {   // deferred join: one event covers both lanes (lane 2's mark waits for lane 1's)
     SideLane *a = scope1.lane, *b = scope2.lane;
     scope1.lane = scope2.lane = nullptr;
@@ -748,8 +767,6 @@ extern "C" int bsms_mlp_bwd_ex(const float* x, const float* grad_y, int64_t R, i
   BSMS_REQUIRE((x && grad_y) || R == 0, BSMS_E_INVALID_ARG, "mlp_bwd: null tensor");
   hipStream_t s = as_stream(stream);
   const MlpKind kind = mlp_kind(in_dim, D, out_dim, layer_norm);
-  BSMS_REQUIRE(!(kind == MLP_SMALL_LN && grad_x), BSMS_E_UNSUPPORTED,
-               "mlp_bwd: input gradient of a narrow-input MLP is not implemented (pass grad_x = NULL)");
   BSMS_REQUIRE(kind == MLP_SMALL_LN || grad_x, BSMS_E_INVALID_ARG, "mlp_bwd: grad_x is null");
   MlpSaved sv = carve_mlp_saved(const_cast<void*>(saved), R, D, H);
   MlpWork wk = carve_mlp_work(work, R, D, H);
@@ -777,6 +794,8 @@ extern "C" int bsms_mlp_bwd_ex(const float* x, const float* grad_y, int64_t R, i
   if (!g_node_bf3) for (int q = 0; q <= k; ++q) a.gmax[q] = sv.bound + size_t(16 + q) * kBoundWidth;
   if (kind == MLP_SMALL_LN) {
     rc = launch_chain_bwd((int)D, G_ROWS_LN, F_NONE, a, s);
+    // optional input gradient (a caller differentiating w.r.t. the encoder's input): g0 . W0, narrow (posgrad.hip)
+    if (!rc && grad_x) rc = narrow_input_grad(wk.g[0], R, D, params[0], (int)in_dim, grad_x, s);
   } else {
     a.wh0 = reinterpret_cast<const float4*>(sv.wt[0]);
     a.dx = grad_x;

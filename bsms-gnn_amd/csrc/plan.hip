@@ -165,7 +165,7 @@ extern "C" int bsms_streams_overlap(bsms_stream_t a, bsms_stream_t b) {
   return can_overtake(sa, sb) ? 1 : 0;
 }
 
-extern "C" int bsms_abi_version(void) { return 3; }  // 2: saved == NULL selects inference in *_fwd; 3: bsms_mlp_fwd_ex, larger saved buffers (bound slots)
+extern "C" int bsms_abi_version(void) { return 4; }  // 2: saved == NULL selects inference in *_fwd; 3: bsms_mlp_fwd_ex, larger saved buffers (bound slots); 4: position gradients (bsms_gmp_bwd_pos, bsms_bsgmp_bwd_pos)
 extern "C" const char* bsms_last_error(void) { return bsms::g_err; }
 
 namespace {

@@ -324,10 +324,18 @@ class _GMPFunction(torch.autograd.Function):
         work = _workspace(x.device, L.bsms_gmp_work_bytes(B, N, plan.E, D, hidden))
         pp, keep = _param_ptrs(params)
         gp, keep2 = _param_ptrs(grads)
-        _abi.check(L.bsms_gmp_bwd(plan.handle, x.data_ptr(), pos.data_ptr(), gout.data_ptr(), B, D, p, pos_bstride,
-                                  hidden, pp, saved.data_ptr(), work.data_ptr(), gx.data_ptr(), gp, _stream()),
-                   "bsms_gmp_bwd")
-        return (gx, None, None, None, *grads)
+        gpos = None
+        if ctx.needs_input_grad[1]:   # positions as an autograd input (shape sensitivity): bsms_gmp_bwd + grad_pos
+            gpos = torch.empty_like(pos)
+            pwork = torch.empty(L.bsms_gmp_pos_work_bytes(B, plan.E, p), dtype=torch.uint8, device=x.device)
+            _abi.check(L.bsms_gmp_bwd_pos(plan.handle, x.data_ptr(), pos.data_ptr(), gout.data_ptr(), B, D, p, pos_bstride,
+                                          hidden, pp, saved.data_ptr(), work.data_ptr(), gx.data_ptr(), gp, gpos.data_ptr(),
+                                          pwork.data_ptr(), _stream()), "bsms_gmp_bwd_pos")
+        else:
+            _abi.check(L.bsms_gmp_bwd(plan.handle, x.data_ptr(), pos.data_ptr(), gout.data_ptr(), B, D, p, pos_bstride,
+                                      hidden, pp, saved.data_ptr(), work.data_ptr(), gx.data_ptr(), gp, _stream()),
+                       "bsms_gmp_bwd")
+        return (gx, gpos, None, None, *grads)
 
 
 class GMP(nn.Module):
@@ -353,7 +361,7 @@ class GMP(nn.Module):
             plan = plan_for(g, x.shape[-2])
         _check_gmp_shapes("GMP", x, pos, plan, self.latent_dim, self.pos_dim)
         params = [*self.mlp_node.flat_params(), *self.mlp_edge.flat_params()]
-        if _needs_grad(x, *params):
+        if _needs_grad(x, pos, *params):
             y = _GMPFunction.apply(x, pos, plan, self.hidden_layer, *params)
         else:
             y = _gmp_infer(x, pos, plan, self.hidden_layer, params)
@@ -525,9 +533,18 @@ class _BSGMPFunction(torch.autograd.Function):
         work = _workspace(h.device, L.bsms_bsgmp_work_bytes(pl, depth, B, D, p, hidden))
         pp, keep = _param_ptrs(params)
         gp, keep2 = _param_ptrs(grads)
-        _abi.check(L.bsms_bsgmp_bwd_p(pl, ewp, depth, h.data_ptr(), pos.data_ptr(), gout.data_ptr(), B, D, p, pos_bstride, hidden,
-                                      pp, saved.data_ptr(), work.data_ptr(), gh.data_ptr(), gp, ctx.prec, _stream()), "bsms_bsgmp_bwd")
-        return (gh, None, None, None, None, None, *grads)
+        gpos = None
+        if ctx.needs_input_grad[1]:   # positions as an autograd input: through every block and the pooling of the positions
+            gpos = torch.empty_like(pos)
+            pwork = torch.empty(L.bsms_bsgmp_pos_work_bytes(pl, depth, B, p), dtype=torch.uint8, device=h.device)
+            _abi.check(L.bsms_bsgmp_bwd_pos(pl, ewp, depth, h.data_ptr(), pos.data_ptr(), gout.data_ptr(), B, D, p, pos_bstride,
+                                            hidden, pp, saved.data_ptr(), work.data_ptr(), gh.data_ptr(), gp, ctx.prec,
+                                            gpos.data_ptr(), pwork.data_ptr(), _stream()), "bsms_bsgmp_bwd_pos")
+        else:
+            _abi.check(L.bsms_bsgmp_bwd_p(pl, ewp, depth, h.data_ptr(), pos.data_ptr(), gout.data_ptr(), B, D, p, pos_bstride,
+                                          hidden, pp, saved.data_ptr(), work.data_ptr(), gh.data_ptr(), gp, ctx.prec, _stream()),
+                       "bsms_bsgmp_bwd")
+        return (gh, gpos, None, None, None, None, *grads)
 
 
 _PARAM_EPOCH = [0]
@@ -700,7 +717,7 @@ class BSGMP(nn.Module):
             params = self.block_params()
             hidden = self.bottom_gmp.hidden_layer
             prec = PRECISIONS[self.precision]
-            if _needs_grad(h, *params):
+            if _needs_grad(h, pos, *params):
                 y = _BSGMPFunction.apply(h, pos, all_plans, ews, hidden, prec, *params)
             else:
                 y = _bsgmp_infer(h, pos, all_plans, ews, hidden, params, session, prec)
@@ -713,8 +730,8 @@ class BSGMP(nn.Module):
             skips.append(h)
             skip_pos.append(pos)
             h = _edge_conv(h, ews[i], plan, True, True)          # conv + pool  (BSMS.py:74,79-83)
-            with torch.no_grad():
-                pos = _edge_conv(pos, ews[i], plan, True, True)  # BSMS.py:75,85-88 ; pos carries no gradient
+            with torch.set_grad_enabled(torch.is_grad_enabled() and pos.requires_grad):
+                pos = _edge_conv(pos, ews[i], plan, True, True)  # BSMS.py:75,85-88 ; differentiable when pos requires grad
         h = self.bottom_gmp(h, m_gs[L], pos, plan=plan_for(m_gs[L], h.shape[-2]))
         for i in range(L):
             d = L - 1 - i

@@ -188,7 +188,8 @@ int bsms_gather_rows(const float* x, int64_t B, int64_t N, int64_t D, const int6
  * models/model.py:20-22.  `saved` = NULL selects INFERENCE (nothing is kept for a backward; `work`
  * must then be non-NULL).  Supported shapes: (in_dim <= 8 or in_dim == D) and
  * (out_dim == D with layer_norm, or out_dim <= 8 without).  `saved` keeps the activations the backward
- * needs.  need_dx=0 skips the input gradient (encoder input is data). */
+ * needs.  bsms_mlp_bwd: grad_x = NULL skips the input gradient (the encoder's input is data); a non-null grad_x gets it for
+ * every supported shape, the narrow first Linear (in_dim <= 8) included -- a caller differentiating w.r.t. node_in. */
 size_t bsms_mlp_saved_bytes(int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int hidden);
 size_t bsms_mlp_work_bytes(int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int hidden);
 int bsms_mlp_fwd(const float* x, int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int hidden,
@@ -212,9 +213,10 @@ int bsms_mlp_fwd_ex(const float* x, int64_t R, int64_t in_dim, int64_t D, int64_
  * and the aggregation: out = mlp_node([x, scatter_sum(mlp_edge([fiber, x_i, x_j]), j)]) + x.
  * x,out [B,N,D]; pos [B,N,p] (pos_batch_stride = N*p) or [N,p] (pos_batch_stride = 0, the
  * `repeat` branch ops/basic.py:87-88); 1 <= p <= 7.  `params`: 2*(hidden+1) pointers of mlp_node
- * followed by 2*(hidden+1) of mlp_edge (state_dict order of a GMP module).  pos gets no gradient
- * (SURVEY.md quirk 5).  `saved` = NULL in bsms_gmp_fwd selects INFERENCE (rollout, utils/rollout_utils.py:14-64):
- * no activation is written for a backward, the messages live in `work`. */
+ * followed by 2*(hidden+1) of mlp_edge (state_dict order of a GMP module).  bsms_gmp_bwd gives no gradient w.r.t. pos (the
+ * reference's training loop never asks for one); bsms_gmp_bwd_pos below does.  `saved` = NULL in
+ * bsms_gmp_fwd selects INFERENCE (rollout, utils/rollout_utils.py:14-64): no activation is written for a backward, the
+ * messages live in `work`. */
 size_t bsms_gmp_saved_bytes(int64_t B, int64_t N, int64_t E, int64_t D, int hidden);
 size_t bsms_gmp_work_bytes(int64_t B, int64_t N, int64_t E, int64_t D, int hidden);
 int bsms_gmp_fwd(const bsms_plan_t* plan, const float* x, const float* pos, int64_t B, int64_t D,
@@ -224,6 +226,18 @@ int bsms_gmp_bwd(const bsms_plan_t* plan, const float* x, const float* pos, cons
                  int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
                  const float* const* params, const void* saved, void* work, float* grad_x,
                  float* const* grads, bsms_stream_t stream);
+/* bsms_gmp_bwd + the gradient w.r.t. the node positions (pos is an ordinary autograd input of the reference's GMP.forward,
+ * ops/basic.py:77-85: shape sensitivity, mesh adaptation).  `grad_pos` has the layout of `pos` -- [B,N,p], or [N,p] summed over
+ * the batch when pos_batch_stride = 0 -- and is OVERWRITTEN; `pos_work` is scratch of bsms_gmp_pos_work_bytes(B, E, p) bytes.
+ * grad_pos = NULL: exactly bsms_gmp_bwd (same launches).  Returns BSMS_E_INVALID_ARG for p outside 1..7 and for a non-null
+ * grad_pos with a null pos_work (checked before anything else, no GPU needed).  Cost: one more read of the first edge
+ * gradient [B,E,D] + 2 x 16 or 32 bytes per edge; deterministic.
+ * bsms_gmp_pos_work_bytes returns 0 for B < 0, E < 0 or p outside 1..7. */
+size_t bsms_gmp_pos_work_bytes(int64_t B, int64_t E, int64_t p);
+int bsms_gmp_bwd_pos(const bsms_plan_t* plan, const float* x, const float* pos, const float* grad_out,
+                     int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
+                     const float* const* params, const void* saved, void* work, float* grad_x,
+                     float* const* grads, float* grad_pos, void* pos_work, bsms_stream_t stream);
 
 /* ---------------------------------------------------------------- A9: BSGMP (whole U-Net) ---
  * BSGMP.forward (ops/BSMS.py:39-104) in one call: down blocks + restrict, bottom block, prolong + up blocks + skip
@@ -282,6 +296,18 @@ int bsms_bsgmp_bwd_ev(const bsms_plan_t* const* plans, const float* const* ew, i
                       const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
                       const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
                       int precision, int flags, void* const* block_done_events, bsms_stream_t stream);
+/* bsms_bsgmp_bwd_p + the gradient w.r.t. the level-0 positions `pos`, through every block and through the pooling of the
+ * positions (pos_{l+1} = restrict_l(pos_l), BSMS.py:75,85-88; its adjoint is bsms_edge_conv with aggregating = 0):
+ *   gpos_l = gpos(up block on l) + restrict_l^T(gpos_{l+1}) + gpos(down block l),  accumulated as the backward passes level l.
+ * `grad_pos` has the layout of `pos` ([B,N_0,p], or [N_0,p] when pos_batch_stride = 0) and is OVERWRITTEN; `pos_work` is
+ * scratch of bsms_bsgmp_pos_work_bytes(plans, L, B, p) bytes (edge scratch + the coarse levels' accumulators).  Any precision;
+ * with the bf16 ones the block gradients are read from the bf16 edge gradients.  grad_pos = NULL: exactly bsms_bsgmp_bwd_p.
+ * Same argument checks as bsms_gmp_bwd_pos; the size query returns 0 for null plans, B < 0 or p outside 1..7. */
+size_t bsms_bsgmp_pos_work_bytes(const bsms_plan_t* const* plans, int L, int64_t B, int64_t p);
+int bsms_bsgmp_bwd_pos(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
+                       const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
+                       const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
+                       int precision, float* grad_pos, void* pos_work, bsms_stream_t stream);
 int bsms_side_lanes_join(bsms_stream_t stream);
 /* Do two streams overlap?  HIP places its streams on a few hardware queues (four by default, by reference counts at creation time) and
  * two streams on one queue run in order, whatever their flags.  Returns 1 if work queued on `b` can overtake work queued on `a`, 0 if not

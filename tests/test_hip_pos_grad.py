@@ -1,0 +1,371 @@
+"""GPU: gradients w.r.t. the node positions (bsms_gmp_bwd_pos, bsms_bsgmp_bwd_pos; posgrad.hip) and w.r.t. the input of a
+narrow-input MLP (the encoder), through the drop-in modules, against the CPU oracle with `pos.requires_grad_()`.
+
+In the reference `pos` is an ordinary autograd input of GMP.forward (ops/basic.py:77-85), of the position pooling of
+BSGMP.forward (ops/BSMS.py:75,85-88) and of BSMS_Simulator (models/model.py:147-149): node_in.requires_grad_() +
+loss.backward() gives the gradient w.r.t. the mesh coordinates.  Tolerances as in test_hip_parity.py (1e-5 of the tensor
+scale, data kept away from ReLU kinks); the bf16 precisions and the full-size steps against bounds derived from the measured
+noise of this gradient (see those tests)."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import pick_seed, rel_err
+from oracle import bsms_oracle as ro
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-5
+
+
+@pytest.fixture(scope="module")
+def eng():
+    import bsms_gnn_amd as eng
+    return eng
+
+
+def dev(t):
+    return t.cuda()
+
+
+def load_sd(module, sd):
+    module.load_state_dict(dict(sd), strict=True)
+    return module.cuda()
+
+
+def multigraph(n, e, seed, loops=8):
+    """Directed multigraph with explicit self-loops, repeated edges and targets that receive nothing (degree-0 rows)."""
+    rng = np.random.default_rng(seed)
+    src = rng.integers(0, n, e)
+    dst = rng.integers(0, max(1, n - n // 8), e)
+    dst[:loops] = src[:loops]                          # zero-length edges: the norm term of the fiber is 0 there
+    src[loops:2 * loops] = src[2 * loops:3 * loops]    # repeated (i, j) pairs
+    dst[loops:2 * loops] = dst[2 * loops:3 * loops]
+    return torch.tensor(np.stack([src, dst]), dtype=torch.int64)
+
+
+def gmp_case(D, p, H, B, shared, n=180, e=1400, seed_graph=1):
+    g = multigraph(n, e, seed_graph)
+
+    def build(seed):
+        torch.manual_seed(seed)
+        ref = ro.GMP(D, H, p)
+        x = torch.randn(B, n, D, requires_grad=True)
+        pos = (torch.rand(n, p) if shared else torch.rand(B, n, p)).requires_grad_(True)
+        cot = torch.randn(B, n, D)
+        return ref, (lambda: ref(x, g, pos)), x, pos, cot
+
+    seed = pick_seed(lambda s: build(s)[:2], first=D + p + H)
+    return g, build(seed)
+
+
+def run_mine(mine, x, g, pos, cot, x_grad=True, pos_grad=True):
+    xd = dev(x.detach()).requires_grad_(x_grad)
+    pd = dev(pos.detach()).requires_grad_(pos_grad)
+    y = mine(xd, dev(g), pd)
+    (y * dev(cot)).sum().backward()
+    torch.cuda.synchronize()
+    return y.detach(), xd.grad, pd.grad
+
+
+# ------------------------------------------------------------------------------------------------------------ GMP
+@pytest.mark.parametrize("shared", [False, True], ids=["pos3d", "pos2d_shared"])
+@pytest.mark.parametrize("D,p,H", [(128, 2, 3), (64, 3, 3), (256, 3, 2), (64, 7, 2), (32, 1, 2)])
+def test_gmp_pos_grad_matches_oracle(eng, D, p, H, shared):
+    B = 3
+    g, (ref, _, x, pos, cot) = gmp_case(D, p, H, B, shared)
+    y = ref(x, g, pos)
+    (y * cot).sum().backward()
+    mine = load_sd(eng.GMP(D, H, p), ref.state_dict())
+    yd, gx, gpos = run_mine(mine, x, g, pos, cot)
+    assert gpos is not None and gpos.shape == pos.shape
+    assert rel_err(yd.cpu(), y) < TOL
+    assert rel_err(gpos.cpu(), pos.grad) < TOL, rel_err(gpos.cpu(), pos.grad)
+    assert rel_err(gx.cpu(), x.grad) < TOL
+    for (k, pr), (_, pm) in zip(ref.named_parameters(), mine.named_parameters()):
+        assert rel_err(pm.grad.cpu(), pr.grad) < TOL, k
+
+
+def test_gmp_pos_grad_2d_input(eng):
+    """2-D x with 2-D pos (the reference's unbatched layout)."""
+    D, p, H = 64, 2, 2
+    g, (ref, _, x, pos, cot) = gmp_case(D, p, H, 1, True)
+    x2, c2 = x.detach()[0].clone().requires_grad_(True), cot[0]
+    y = ref(x2, g, pos)
+    (y * c2).sum().backward()
+    mine = load_sd(eng.GMP(D, H, p), ref.state_dict())
+    yd, gx, gpos = run_mine(mine, x2, g, pos, c2)
+    assert yd.dim() == 2 and rel_err(gpos.cpu(), pos.grad) < TOL and rel_err(gx.cpu(), x2.grad) < TOL
+
+
+def test_gmp_zero_length_edges(eng):
+    """Coincident nodes and explicit self-loops: |pos_i - pos_j| = 0.  torch's norm backward contributes 0 there; the
+    gradient is finite and equal to the oracle's."""
+    D, p, H, n, B = 64, 2, 2, 40, 2
+    rng = np.random.default_rng(5)
+    src = rng.integers(0, n, 300)
+    dst = rng.integers(0, n, 300)
+    src[:20] = dst[:20] = np.arange(20)                        # self-loops
+    src[20:30], dst[20:30] = 30, 31                            # 30 and 31 coincide below
+    src[30:40], dst[30:40] = 31, 30
+    g = torch.tensor(np.stack([src, dst]), dtype=torch.int64)
+
+    def build(seed):
+        torch.manual_seed(seed)
+        ref = ro.GMP(D, H, p)
+        x = torch.randn(B, n, D, requires_grad=True)
+        base = torch.rand(B, n, p)
+        base[:, 31] = base[:, 30]
+        pos = base.requires_grad_(True)
+        return ref, (lambda: ref(x, g, pos)), x, pos
+
+    seed = pick_seed(lambda s: build(s)[:2], first=11)
+    ref, _, x, pos = build(seed)
+    cot = torch.randn(B, n, D)
+    y = ref(x, g, pos)
+    (y * cot).sum().backward()
+    mine = load_sd(eng.GMP(D, H, p), ref.state_dict())
+    _, gx, gpos = run_mine(mine, x, g, pos, cot)
+    assert bool(torch.isfinite(gpos).all())
+    assert rel_err(gpos.cpu(), pos.grad) < TOL and rel_err(gx.cpu(), x.grad) < TOL
+
+
+def test_gmp_nothing_else_moves_and_deterministic(eng):
+    """pos.requires_grad changes nothing but pos.grad: output, x.grad and every parameter gradient bit-identical; two runs
+    give bit-identical pos.grad (fixed summation order, no atomics)."""
+    D, p, H, B = 128, 2, 3, 2
+    g, (ref, _, x, pos, cot) = gmp_case(D, p, H, B, False)
+    mine = load_sd(eng.GMP(D, H, p), ref.state_dict())
+    res = []
+    for pg in (False, True, True):
+        mine.zero_grad(set_to_none=True)
+        y, gx, gpos = run_mine(mine, x, g, pos, cot, pos_grad=pg)
+        res.append((y, gx, gpos, [q.grad.clone() for q in mine.parameters()]))
+    (a, b, c) = res
+    assert a[2] is None and b[2] is not None
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and all(torch.equal(u, v) for u, v in zip(a[3], b[3]))
+    assert torch.equal(b[2], c[2])
+
+
+def test_gmp_frozen_parameters(eng):
+    """Shape sensitivity with a trained model: only pos requires grad.  pos.grad equals the trainable run bit for bit and
+    the parameters get no .grad."""
+    D, p, H, B = 64, 3, 3, 2
+    g, (ref, _, x, pos, cot) = gmp_case(D, p, H, B, False)
+    mine = load_sd(eng.GMP(D, H, p), ref.state_dict())
+    _, _, want = run_mine(mine, x, g, pos, cot)
+    for q in mine.parameters():
+        q.requires_grad_(False)
+        q.grad = None
+    _, gx, got = run_mine(mine, x, g, pos, cot, x_grad=False)
+    assert gx is None and torch.equal(got, want)
+    assert all(q.grad is None for q in mine.parameters())
+
+
+# ------------------------------------------------------------------------------------------- encoder input gradient
+@pytest.mark.parametrize("in_dim,D", [(1, 32), (3, 128), (4, 256), (8, 64)])
+def test_narrow_mlp_input_gradient(eng, in_dim, D):
+    """The encoder's input gradient (bsms_mlp_bwd with grad_x on a narrow first Linear): what node_in.grad's state and
+    type columns go through."""
+    R = 1000
+
+    def build(seed):
+        torch.manual_seed(seed)
+        ref = ro.MLP(in_dim, D, D, 3, True)
+        x = torch.randn(R, in_dim, requires_grad=True)
+        return ref, (lambda: ref(x)), x
+
+    seed = pick_seed(lambda s: build(s)[:2], first=in_dim)
+    ref, _, x = build(seed)
+    cot = torch.randn(R, D)
+    (ref(x) * cot).sum().backward()
+    mine = load_sd(eng.MLP(in_dim, D, D, 3, True), ref.state_dict())
+    xd = dev(x.detach()).requires_grad_(True)
+    (mine(xd) * dev(cot)).sum().backward()
+    assert rel_err(xd.grad.cpu(), x.grad) < TOL
+    for (k, pr), (_, pm) in zip(ref.named_parameters(), mine.named_parameters()):
+        assert rel_err(pm.grad.cpu(), pr.grad) < TOL, k
+
+
+# ------------------------------------------------------------------------------------------------------------ BSGMP
+def bsgmp_case(graphs, name, D, H, B, shared):
+    es, ids = graphs.levels(name)
+    L = len(es) - 1
+    base = torch.tensor(graphs.np(f"{name}/pos"), dtype=torch.float32)
+    n, p = base.shape
+
+    def build(seed):
+        torch.manual_seed(seed)
+        ref = ro.BSGMP(L, D, H, p)
+        h = torch.randn(B, n, D, requires_grad=True)
+        pos = (base.clone() if shared else base + 0.05 * torch.randn(B, n, p)).requires_grad_(True)
+        return ref, (lambda: ref(h, ids[:L], es, pos)), h, pos
+
+    seed = pick_seed(lambda s: build(s)[:2], first=3)
+    ref, _, h, pos = build(seed)
+    cot = torch.randn(B, n, D)
+    return es, ids, L, p, ref, h, pos, cot
+
+
+def run_bsgmp(net, h, ids, es, pos, cot, per_block=False, pos_grad=True, h_grad=True):
+    L = net.unet_depth
+    net.per_block = per_block
+    try:
+        hd = dev(h.detach()).requires_grad_(h_grad)
+        pd = dev(pos.detach()).requires_grad_(pos_grad)
+        y = net(hd, [dev(i) for i in ids[:L]], [dev(e) for e in es[:L + 1]], pd)
+        (y * dev(cot)).sum().backward()
+        torch.cuda.synchronize()
+    finally:
+        net.per_block = False
+    return y.detach(), hd.grad, pd.grad
+
+
+@pytest.mark.parametrize("name,shared", [("del64", False), ("del300", False), ("del300", True), ("surf200", False)])
+def test_bsgmp_pos_grad_golden_hierarchies(eng, graphs, name, shared):
+    D, H, B = 32, 3, 2
+    es, ids, L, p, ref, h, pos, cot = bsgmp_case(graphs, name, D, H, B, shared)
+    assert L >= 3
+    y = ref(h, ids[:L], es, pos)
+    (y * cot).sum().backward()
+    net = load_sd(eng.BSGMP(L, D, H, p), ref.state_dict())
+    got = {}
+    for per_block in (False, True):
+        net.zero_grad(set_to_none=True)
+        yd, gh, gpos = run_bsgmp(net, h, ids, es, pos, cot, per_block)
+        assert rel_err(yd.cpu(), y) < TOL and rel_err(gh.cpu(), h.grad) < TOL
+        assert rel_err(gpos.cpu(), pos.grad) < TOL, (per_block, rel_err(gpos.cpu(), pos.grad))
+        for (k, pr), (_, pm) in zip(ref.named_parameters(), net.named_parameters()):
+            assert rel_err(pm.grad.cpu(), pr.grad) < TOL, (per_block, k)
+        got[per_block] = gpos
+    assert rel_err(got[False].cpu(), got[True].cpu()) < TOL
+
+
+@pytest.mark.parametrize("prec", ["f32", "bf16"])
+def test_bsgmp_nothing_else_moves_and_frozen(eng, graphs, prec):
+    """One-call U-Net: pos.requires_grad on / off gives bit-identical outputs, h.grad and parameter gradients; pos.grad is
+    reproducible bit for bit, and with frozen parameters (only pos requires grad) it is the same bits again."""
+    D, H, B = 128, 3, 2
+    es, ids, L, p, ref, h, pos, cot = bsgmp_case(graphs, "del300", D, H, B, False)
+    net = load_sd(eng.BSGMP(L, D, H, p), ref.state_dict())
+    net.precision = prec
+    res = []
+    for pg in (False, True, True):
+        net.zero_grad(set_to_none=True)
+        y, gh, gpos = run_bsgmp(net, h, ids, es, pos, cot, pos_grad=pg)
+        res.append((y, gh, gpos, [q.grad.clone() for q in net.parameters()]))
+    a, b, c = res
+    assert a[2] is None and b[2] is not None and bool(torch.isfinite(b[2]).all())
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and all(torch.equal(u, v) for u, v in zip(a[3], b[3]))
+    assert torch.equal(b[2], c[2])
+    for q in net.parameters():
+        q.requires_grad_(False)
+        q.grad = None
+    _, gh, frozen = run_bsgmp(net, h, ids, es, pos, cot, h_grad=False)
+    assert gh is None and torch.equal(frozen, b[2])
+    assert all(q.grad is None for q in net.parameters())
+
+
+def _close_l2_cos(got, want):
+    a, b = got.double().flatten().cpu(), want.double().flatten().cpu()
+    l2 = float((a - b).norm() / b.norm().clamp_min(1e-300))
+    cos = float(torch.dot(a, b) / (a.norm() * b.norm()).clamp_min(1e-300))
+    return l2, cos
+
+
+@pytest.mark.parametrize("prec", ["bf16", "bf16_nodes"])
+def test_bsgmp_pos_grad_bf16_vs_fp32(eng, prec):
+    """The bf16 precisions read the bf16 edge gradients: the mesh-position gradient of the airfoil step (BSMS_Simulator, masked
+    RMSE, B = 2, 5 levels, D = 128) against the engine's fp32 one.  A node's position gradient is a difference of sums over its
+    outgoing and incoming edges and cancels heavily (even the fp32 oracle is ~2e-3 of its scale away from fp64 here, against
+    <= 1e-4 for the parameter gradients), so it carries ~4x the bf16 noise of the parameter gradients: measured relative L2
+    0.100 / 0.124 and cosine 0.9951 / 0.9923 (bf16 / bf16_nodes) where the worst parameter gradient of the same step is at
+    0.024 / 0.033 (test_hip_bf16.py holds those to 5e-2 / 0.998).  Bound: relative L2 <= 0.2, cosine >= 0.98 -- a wrong row or
+    column read of the bf16 gradient would give a cosine near 0."""
+    from bench import build_workload, data_tuple, make_cfg
+    wl = build_workload("airfoil", 2, "cuda")
+    data = data_tuple(wl)
+    cfg = make_cfg(wl["cfg"])
+    torch.manual_seed(0)
+    sim = eng.BSMS_Simulator(cfg).cuda()
+    sim(data, True, True)                                   # one normaliser accumulation
+    C, p = cfg.out_dim, cfg.pos_dim
+    got, par = {}, {}
+    for pr in ("f32", prec):
+        sim.process.precision = pr
+        sim.zero_grad(set_to_none=True)
+        ni = data[0].clone().requires_grad_(True)
+        eng.masked_rmse(sim((ni, *data[1:]), True, False), data[1], data[2]).backward()
+        got[pr] = ni.grad.detach()
+        par[pr] = {k: q.grad.detach().clone() for k, q in sim.named_parameters() if q.grad is not None}
+    l2, cos = _close_l2_cos(got[prec][..., C:C + p], got["f32"][..., C:C + p])
+    l2s, coss = _close_l2_cos(got[prec][..., :C], got["f32"][..., :C])
+    pw = max((_close_l2_cos(par[prec][k], par["f32"][k]) for k in par["f32"]), key=lambda t: t[0])
+    print(f"\n[{prec}] vs fp32: node_in.grad positions relative L2 {l2:.3e} cosine {cos:.6f} | state columns {l2s:.3e} / {coss:.6f} | "
+          f"worst parameter gradient {pw[0]:.3e} / {pw[1]:.6f}")
+    assert l2 <= 0.2 and cos >= 0.98, (l2, cos)
+
+
+# --------------------------------------------------------------------------------------------------------- full size
+def _three_way(kind, batch):
+    """node_in.grad per column group against an fp64 run of the oracle, next to the fp32 oracle's own distance (all threads and one
+    thread).  Unlike test_hip_fullsize.py, which takes statistics over ~200 parameter tensors, each group here is ONE tensor, and
+    the position group is a difference of sums over a node's outgoing and incoming edges: it amplifies the relative error of the
+    first edge gradient (both fp32 paths are ~1e-4 (L2) / ~2e-3 (max) from fp64 at airfoil B=2, against ~5e-6 for the state
+    columns).  Measured engine / yardstick ratios: airfoil B=2 positions 2.2 (max-norm) and 2.3 (L2) -- the two oracle runs
+    agree with each other to 3 digits, so they span no spread of fp32 orders -- surface B=1 0.36 / 0.73; the other groups
+    <= 1.5 or under the 1e-5 floor.  Limit: 3x the larger oracle distance, both metrics (test_hip_fullsize.py: 1.5x on
+    statistics over many tensors)."""
+    from bench import build_workload, data_tuple, make_cfg, usable_cpus
+    import bsms_gnn_amd as eng
+    torch.set_num_threads(max(1, min(32, usable_cpus())))
+    wl = build_workload(kind, batch, "cpu")
+    data = data_tuple(wl)
+    cfg = make_cfg(wl["cfg"])
+    torch.manual_seed(0)
+    ref32 = ro.BSMS_Simulator(cfg)
+    ref32(data, True, True)                                 # one normaliser accumulation
+    ref64 = ro.BSMS_Simulator(cfg, dtype=torch.float64)
+    ref64.load_state_dict(ref32.state_dict())
+    ref64.double()
+    mine = eng.BSMS_Simulator(cfg)
+    mine.load_state_dict(ref32.state_dict())
+    mine = mine.cuda()
+
+    def step(sim, d, to=lambda t: t):
+        ni = to(d[0]).clone().requires_grad_(True)
+        dd = (ni, to(d[1]), to(d[2]), [to(g) for g in d[3]], [to(i) for i in d[4]])
+        loss = (eng.masked_rmse if sim is mine else ro.masked_rmse)(sim(dd, True, False), dd[1], dd[2])
+        loss.backward()
+        return ni.grad.detach().cpu()
+
+    g32 = step(ref32, data)
+    g64 = step(ref64, data, lambda t: t.double() if t.is_floating_point() else t)
+    nthreads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        g32_one = step(ref32, data)
+    finally:
+        torch.set_num_threads(nthreads)
+    gg = step(mine, data, lambda t: t.cuda())
+    C, p = cfg.out_dim, cfg.pos_dim
+    groups = {"state": slice(0, C), "position": slice(C, C + p), "type": slice(C + p, C + p + 1)}
+    rel = lambda a, b: float((a.double() - b).abs().max() / b.abs().max().clamp_min(1e-300))
+    rel2 = lambda a, b: float((a.double() - b).norm() / b.norm().clamp_min(1e-300))
+    for tag, sl in groups.items():
+        e_gpu, e_n, e_1 = rel(gg[..., sl], g64[..., sl]), rel(g32[..., sl], g64[..., sl]), rel(g32_one[..., sl], g64[..., sl])
+        l_gpu, l_n, l_1 = rel2(gg[..., sl], g64[..., sl]), rel2(g32[..., sl], g64[..., sl]), rel2(g32_one[..., sl], g64[..., sl])
+        limit, limit2 = max(1e-5, 3.0 * max(e_n, e_1)), max(1e-5, 3.0 * max(l_n, l_1))
+        print(f"\n[{kind} B={batch}] node_in.grad {tag}: max-norm gpu {e_gpu:.2e} | cpu32 all threads {e_n:.2e} one thread {e_1:.2e} "
+              f"(limit {limit:.2e}); relative L2 gpu {l_gpu:.2e} | cpu32 {l_n:.2e} / {l_1:.2e} (limit {limit2:.2e})")
+        assert float(g64[..., sl].abs().max()) > 0, tag      # the column group really receives a gradient
+        assert e_gpu <= limit and l_gpu <= limit2, (kind, tag, e_gpu, e_n, e_1, l_gpu, l_n, l_1)
+
+
+def test_fullsize_airfoil_node_in_grad(eng):
+    """airfoil B=2 (5233 nodes, 5 levels, D = 128): BSMS_Simulator + masked RMSE + backward with node_in.requires_grad."""
+    _three_way("airfoil", 2)
+
+
+def test_fullsize_surface_node_in_grad(eng):
+    """surface B=1 (16384 nodes, 6 levels, D = 256, pos_dim = 3)."""
+    _three_way("surface", 1)
