@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libbsms_hip.so")
-SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip"]
+SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "chain_d96.hip", "chain_d160.hip", "chain_d192.hip", "chain_d224.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip"]
 # csrc/experiments/*.hip (the fp32 fused edge backward, efuse32.hip) are NOT part of the product library: profiles/build_efv.sh
 # compiles them into the experiment builds (-DBSMS_EXPERIMENTS), where gmp.hip / chain.hip keep their hooks
 HEADERS = ["common.h", "chain.h", "chain_dev.h", os.path.join("..", "..", "include", "bsms_hip.h")]
@@ -47,7 +47,7 @@ def build(force=False, verbose=True):
         obj = os.path.join(OBJ, os.path.basename(src).replace(".hip", ".o"))
         # no contraction: rowsum.hip rounds x*ew before the add like the reference; sim.hip keeps the fp64 normaliser roundings
         extra = ["-ffp-contract=off"] if src in ("rowsum.hip", "sim.hip") else []
-        if src == "chain.hip" and os.environ.get("BSMS_CHAIN_FLAGS"):   # A/B builds
+        if src.startswith("chain") and os.environ.get("BSMS_CHAIN_FLAGS"):   # A/B builds (chain.hip and the chain_d*.hip widths)
             extra += os.environ["BSMS_CHAIN_FLAGS"].split()
         cmd = [hipcc, *FLAGS, *extra, "-c", os.path.join(CSRC, src), "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)

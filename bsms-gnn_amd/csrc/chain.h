@@ -47,8 +47,9 @@ constexpr int kChunkHdrFloats = 256;                     // 1 KB chunk header (b
 // activations, the messages y and the edge layer gradients are stored as bf16 and the edge MLP's products take bf16
 // operands (weights rounded once per call) with fp32 accumulation; everything at node level stays fp32.
 // A saved activation [rows, D] is followed by its ReLU sign bits, one bit per element packed per (row, lane group):
-// the backward chain masks gradients from 16 bytes per row instead of re-reading 4 D bytes.
-constexpr size_t mask_words_per_row(int64_t D) { return size_t(4) * (D <= 128 ? 1 : D / 128); }
+// the backward chain masks gradients from 16 bytes per row instead of re-reading 4 D bytes.  Each of the 4 lane groups
+// of a row holds D / 4 elements, i.e. ceil(D / 128) words of bits (chain_dev.h: mask_words).
+constexpr size_t mask_words_per_row(int64_t D) { return size_t(4) * size_t((D + 127) / 128); }
 // Tensors the chain kernels write with their paired streaming stores are allocated for whole tiles (the largest tile:
 // kPadRows rows, the edge kernels with two row blocks per wave): the stores then need no per-lane bounds test (rows
 // past R hold garbage nobody reads; the sign bits start after the padding and are padded the same way).
@@ -182,6 +183,11 @@ int launch_prepack(const PackTable& t, hipStream_t s);
 
 int launch_chain_fwd(int D, int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s);
 int launch_chain_bwd(int D, int gin_mode, int first_mode, const ChainBwdArgs& a, hipStream_t s);
+// the generic chain kernels at NB = 6 / 10 / 12 / 14 (D = 96 / 160 / 192 / 224), one translation unit each (chain_d*.hip)
+template <int NB>
+int launch_chain_fwd_nb(int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s);
+template <int NB>
+int launch_chain_bwd_nb(int gin_mode, int first_mode, const ChainBwdArgs& a, hipStream_t s);
 
 // weight gradients ------------------------------------------------------------------------------
 struct WgradJob {

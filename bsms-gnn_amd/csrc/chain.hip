@@ -1,4 +1,7 @@
 // Chain kernels (see chain.h for the register-layout idea) + weight prepack.
+// The generic kernels at D = 96 / 160 / 192 / 224 are compiled in translation units of their own (chain_d*.hip include
+// this file with BSMS_CHAIN_NB set: only the kernel and launcher templates, and the two launchers of that width), so that
+// the build compiles them in parallel with this file.
 #include "chain.h"
 
 // No implicit contraction in this file: hipcc defaults to -ffp-contract=fast and decides PER INSTANTIATION whether a
@@ -15,6 +18,7 @@ using namespace bsms;
 
 namespace {
 
+#ifndef BSMS_CHAIN_NB
 // pass 1 (one 1024-thread block per pack): 2^-k_w from the largest |M| of the matrix and of its mate -> header float
 // kScaleSlot of chunk 0, where pass 2 and the chain kernels read it
 __global__ __launch_bounds__(1024) void k_pack_scale(PackTable tab) {
@@ -187,12 +191,20 @@ __global__ __launch_bounds__(1024) void k_prepack_fused(PackTable tab) {
     }
   }
 }
+#endif  // !BSMS_CHAIN_NB
 
 // -------------------------------------------------------------------------------- forward chain
+// Register budget of the generic chain kernels (waves per EU the compiler allocates for).  D = 32 / 64 / 128, multi-round
+// launches: BSMS_CHAIN_WPE (chain_dev.h).  Single-round variants and D = 256: 2 (256 VGPRs).  D = 96 / 160 / 192 / 224
+// take 2 as well: at 4 the D = 96 forward kernels spill (20-72 bytes of scratch per lane), and the wider ones need 140-230
+// VGPRs (profiles/width_rates.txt) -- one workgroup per CU either way (resident_per_cu).
+template <int NB, bool LONE>
+constexpr int chain_wpe() { return (NB == 2 || NB == 4 || NB == 8) && !LONE ? BSMS_CHAIN_WPE : 2; }
+
 // TIMING (experiments, profiles/tile_timeline.py): phase stamps of wave 0; a separate instantiation so that the
 // production kernel carries none of it.
 template <int NB, int IN, int OUT, bool TIMING = false, bool BF = false, bool LONE = false>
-__global__ __launch_bounds__(kChainMaxThreads) __attribute__((amdgpu_waves_per_eu(NB <= 8 ? (LONE ? 2 : BSMS_CHAIN_WPE) : 2))) void k_chain_fwd(ChainFwdArgs a) {
+__global__ __launch_bounds__(kChainMaxThreads) __attribute__((amdgpu_waves_per_eu(chain_wpe<NB, LONE>()))) void k_chain_fwd(ChainFwdArgs a) {
   constexpr int D = NB * 16;
   extern __shared__ __attribute__((aligned(16))) float4 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lg = lane >> 4;
@@ -778,7 +790,7 @@ __device__ __forceinline__ void mask_by(f32x4 (&gr)[NB], const float* act_row, i
 }
 
 template <int NB, int GIN, int FIRST, bool BF = false, bool LONE = false>
-__global__ __launch_bounds__(kChainMaxThreads) __attribute__((amdgpu_waves_per_eu(NB <= 8 ? (LONE ? 2 : BSMS_CHAIN_WPE) : 2))) void k_chain_bwd(ChainBwdArgs a) {
+__global__ __launch_bounds__(kChainMaxThreads) __attribute__((amdgpu_waves_per_eu(chain_wpe<NB, LONE>()))) void k_chain_bwd(ChainBwdArgs a) {
   constexpr int D = NB * 16;
   extern __shared__ __attribute__((aligned(16))) float4 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lg = lane >> 4;
@@ -1566,6 +1578,10 @@ void k_edge_bwd(ChainBwdArgs a) {
 // Workgroups of 5 waves the chip keeps resident per CU at each width.  NOT the occupancy API's answer: the SPI
 // accounts a 5-wave workgroup like an 8-wave one (census: 320 threads x 120 VGPRs -> 2 per CU where the API says 3;
 // profiles/census).  A grid larger than the residency would only queue, a smaller one idles slots.
+// D = 96 / 160 / 192 / 224 (NB = 6 / 10 / 12 / 14) keep ONE: their kernels are built for 256 VGPRs (chain_wpe) and the
+// largest instantiations use more than 128 (D = 96: up to 137, the wider ones 140-230; two waves per SIMD and workgroup
+// leave room for one), and from NB = 12 on the 3-slot ring alone (82 / 95 KB of LDS) would not fit twice into 160 KB
+// (profiles/width_rates.txt: resource table).
 template <int NB>
 constexpr int resident_per_cu() { return NB <= 4 ? 4 : NB == 8 ? 2 : 1; }
 
@@ -1578,7 +1594,7 @@ template <int NB>
 int chain_compute_waves(int64_t R) {
   const int cus = device_cu_count();
   const int64_t slots = int64_t(cus) * resident_per_cu<NB>();
-  if (NB < 8 || ceil_div(R, kTileRows) <= slots) return kComputeWaves;
+  if (resident_per_cu<NB>() >= 4 || ceil_div(R, kTileRows) <= slots) return kComputeWaves;   // D = 32 / 64: always 4
   const int64_t need = ceil_div(R, slots * 16);   // waves per workgroup for one round
   return need <= 7 ? (int)need : kComputeWaves;
 }
@@ -1858,6 +1874,7 @@ int launch_fwd_t(const ChainFwdArgs& a0, hipStream_t s) {
     }
   }
   BSMS_REQUIRE(launched || !a.bf16, BSMS_E_UNSUPPORTED, "chain_fwd: bf16 precision is built for the edge and node MLPs at D = 128 / 256 only");
+  // (D = 96 has no single-round build: its single-round launches stay on the ring kernel, which saves a set of instantiations)
   if constexpr (NB >= 8) {   // one round of workgroups = a single wave per SIMD: the variant that prefetches its fragments (mfma_stage)
     if (!launched && (a.ntiles <= device_cus() || rows2_lone)) {
       static DynLdsAttr lattr_dev;
@@ -1967,6 +1984,16 @@ int launch_bwd_n(int gin, int first, const ChainBwdArgs& a, hipStream_t s) {
 
 }  // namespace
 
+#ifdef BSMS_CHAIN_NB
+namespace bsms {
+template <int NB>
+int launch_chain_fwd_nb(int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s) { return launch_fwd_n<NB>(in_mode, out_mode, a, s); }
+template <int NB>
+int launch_chain_bwd_nb(int gin, int first, const ChainBwdArgs& a, hipStream_t s) { return launch_bwd_n<NB>(gin, first, a, s); }
+template int launch_chain_fwd_nb<BSMS_CHAIN_NB>(int, int, const ChainFwdArgs&, hipStream_t);
+template int launch_chain_bwd_nb<BSMS_CHAIN_NB>(int, int, const ChainBwdArgs&, hipStream_t);
+}  // namespace bsms
+#else
 // experiments only (not in bsms_hip.h): what residency does the runtime compute for the D = 128 edge chains?
 #ifdef BSMS_EXPERIMENTS
 extern "C" int bsms_debug_occupancy(int* fwd_blocks_per_cu, int* bwd_blocks_per_cu) {
@@ -2005,8 +2032,12 @@ int launch_chain_fwd(int D, int in_mode, int out_mode, const ChainFwdArgs& a, hi
     case 64: return launch_fwd_n<4>(in_mode, out_mode, a, s);
     case 128: return launch_fwd_n<8>(in_mode, out_mode, a, s);
     case 256: return launch_fwd_n<16>(in_mode, out_mode, a, s);
+    case 96: return launch_chain_fwd_nb<6>(in_mode, out_mode, a, s);   // chain_d96.hip, ...
+    case 160: return launch_chain_fwd_nb<10>(in_mode, out_mode, a, s);
+    case 192: return launch_chain_fwd_nb<12>(in_mode, out_mode, a, s);
+    case 224: return launch_chain_fwd_nb<14>(in_mode, out_mode, a, s);
   }
-  BSMS_FAIL(BSMS_E_UNSUPPORTED, "latent width D=%d not supported (32, 64, 128, 256)", D);
+  BSMS_FAIL(BSMS_E_UNSUPPORTED, "latent width D=%d not supported (a multiple of 32, 32..256)", D);
 }
 
 int launch_chain_bwd(int D, int gin, int first, const ChainBwdArgs& a, hipStream_t s) {
@@ -2016,8 +2047,13 @@ int launch_chain_bwd(int D, int gin, int first, const ChainBwdArgs& a, hipStream
     case 64: return launch_bwd_n<4>(gin, first, a, s);
     case 128: return launch_bwd_n<8>(gin, first, a, s);
     case 256: return launch_bwd_n<16>(gin, first, a, s);
+    case 96: return launch_chain_bwd_nb<6>(gin, first, a, s);
+    case 160: return launch_chain_bwd_nb<10>(gin, first, a, s);
+    case 192: return launch_chain_bwd_nb<12>(gin, first, a, s);
+    case 224: return launch_chain_bwd_nb<14>(gin, first, a, s);
   }
-  BSMS_FAIL(BSMS_E_UNSUPPORTED, "latent width D=%d not supported (32, 64, 128, 256)", D);
+  BSMS_FAIL(BSMS_E_UNSUPPORTED, "latent width D=%d not supported (a multiple of 32, 32..256)", D);
 }
 
 }  // namespace bsms
+#endif  // BSMS_CHAIN_NB

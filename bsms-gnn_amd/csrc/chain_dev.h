@@ -172,9 +172,10 @@ __device__ __forceinline__ void store_pair_stream(const f32x4 (&v)[NB], float* b
   }
 }
 
-// ReLU sign bits of this lane's 4 NB values: bit (4 t + r) of word (4 t + r) / 32
+// ReLU sign bits of this lane's 4 NB values: bit (4 t + r) of word (4 t + r) / 32; the last word of NB = 10 / 12 / 14
+// is partly filled
 template <int NB>
-constexpr int mask_words() { return NB <= 8 ? 1 : NB / 8; }
+constexpr int mask_words() { return (NB + 7) / 8; }
 
 // `BF`: the activation block in front of the bits is bf16 (R * D * 2 bytes) instead of fp32
 template <int NB, bool BF = false>
@@ -185,7 +186,7 @@ __device__ __forceinline__ void store_mask_bits(const f32x4 (&v)[NB], float* act
 #pragma unroll
   for (int w = 0; w < W; ++w) {
     unsigned m = 0;
-    constexpr int N = (4 * NB < 32) ? 4 * NB : 32;
+    const int N = (4 * NB - 32 * w < 32) ? 4 * NB - 32 * w : 32;   // elements in word w (w is unrolled: a constant)
 #pragma unroll
     for (int k = N - 1; k >= 0; --k) {   // highest element first: every step shifts the word left by one and appends a bit
       const int e = 32 * w + k;

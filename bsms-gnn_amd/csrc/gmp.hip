@@ -35,7 +35,9 @@ struct Carver {  // identical walk for size queries (base == nullptr) and real b
   }
 };
 
-bool supported_D(int64_t D) { return D == 32 || D == 64 || D == 128 || D == 256; }
+// fp32: every multiple of 32 (the K block of a weight chunk: an even number of 16-feature MFMA blocks) up to 256; wider
+// rows do not fit the chain kernels' LDS ring (chain.hip: max_ring).  The bf16 precisions: 128 / 256 (checked per call).
+bool supported_D(int64_t D) { return D % 32 == 0 && D >= 32 && D <= 256; }
 
 // Experiment switches exist only in a library built with -DBSMS_EXPERIMENTS (BSMS_EXPERIMENTS=1 python
 // bsms-gnn_amd/build.py; used by profiles/experiments.py, tile_timeline.py, ab.sh): the production build has no
@@ -188,7 +190,7 @@ bool edge_fused_possible(int64_t D, int H) { return use_edge_fused(D, H, BSMS_F3
 
 int check_gmp(const bsms_plan_t* plan, int64_t B, int64_t D, int64_t p, int H, const char* who) {
   BSMS_REQUIRE(plan != nullptr, BSMS_E_INVALID_ARG, "%s: plan is null", who);
-  BSMS_REQUIRE(supported_D(D), BSMS_E_UNSUPPORTED, "%s: latent width D=%lld not supported (32, 64, 128, 256)", who, (long long)D);
+  BSMS_REQUIRE(supported_D(D), BSMS_E_UNSUPPORTED, "%s: latent width D=%lld not supported (a multiple of 32, 32..256)", who, (long long)D);
   BSMS_REQUIRE(p >= 1 && p <= 7, BSMS_E_UNSUPPORTED, "%s: pos_dim=%lld (1..7)", who, (long long)p);
   BSMS_REQUIRE(H >= 1 && H < kMaxStages, BSMS_E_UNSUPPORTED, "%s: hidden=%d (1..%d)", who, H, kMaxStages - 1);
   BSMS_REQUIRE(B >= 0, BSMS_E_SHAPE, "%s: B=%lld", who, (long long)B);
@@ -681,7 +683,7 @@ MlpWork carve_mlp_work(void* base, int64_t R, int64_t D, int H) {
 }
 
 int check_mlp(int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int H, int layer_norm, const char* who) {
-  BSMS_REQUIRE(supported_D(D), BSMS_E_UNSUPPORTED, "%s: latent width D=%lld not supported (32, 64, 128, 256)", who, (long long)D);
+  BSMS_REQUIRE(supported_D(D), BSMS_E_UNSUPPORTED, "%s: latent width D=%lld not supported (a multiple of 32, 32..256)", who, (long long)D);
   BSMS_REQUIRE(H >= 1 && H < kMaxStages, BSMS_E_UNSUPPORTED, "%s: hidden=%d (1..%d)", who, H, kMaxStages - 1);
   BSMS_REQUIRE(R >= 0, BSMS_E_SHAPE, "%s: R=%lld", who, (long long)R);
   BSMS_REQUIRE(mlp_kind(in_dim, D, out_dim, layer_norm) != MLP_BAD, BSMS_E_UNSUPPORTED,

@@ -149,7 +149,14 @@ int launch_narrow_k(const NarrowArgs& a, int64_t D, hipStream_t s) {
     case 64: hipLaunchKernelGGL((k_narrow_t<16, 1, K, XBF, POS>), dim3(narrow_grid(a.R, 16)), dim3(256), 0, s, a); break;
     case 128: hipLaunchKernelGGL((k_narrow_t<16, 2, K, XBF, POS>), dim3(narrow_grid(a.R, 16)), dim3(256), 0, s, a); break;
     case 256: hipLaunchKernelGGL((k_narrow_t<16, 4, K, XBF, POS>), dim3(narrow_grid(a.R, 16)), dim3(256), 0, s, a); break;
-    default: BSMS_FAIL(BSMS_E_UNSUPPORTED, "narrow input gradient: D=%lld (32, 64, 128, 256)", (long long)D);
+    default:
+      if constexpr (!XBF) {   // fp32 rows at the other multiples of 32: 8 lanes x 4 x NF4 features (16 x 4 x 3 at 192)
+        if (D == 96) { hipLaunchKernelGGL((k_narrow_t<8, 3, K, XBF, POS>), dim3(narrow_grid(a.R, 32)), dim3(256), 0, s, a); break; }
+        if (D == 160) { hipLaunchKernelGGL((k_narrow_t<8, 5, K, XBF, POS>), dim3(narrow_grid(a.R, 32)), dim3(256), 0, s, a); break; }
+        if (D == 192) { hipLaunchKernelGGL((k_narrow_t<16, 3, K, XBF, POS>), dim3(narrow_grid(a.R, 16)), dim3(256), 0, s, a); break; }
+        if (D == 224) { hipLaunchKernelGGL((k_narrow_t<8, 7, K, XBF, POS>), dim3(narrow_grid(a.R, 32)), dim3(256), 0, s, a); break; }
+      }
+      BSMS_FAIL(BSMS_E_UNSUPPORTED, "narrow input gradient: D=%lld (fp32 rows: multiples of 32 up to 256; bf16 rows: 32, 64, 128, 256)", (long long)D);
   }
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;

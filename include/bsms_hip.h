@@ -42,7 +42,8 @@
  *     test_edge_weight_gradient_envelope pins that envelope.
  *   - Edge lists follow the reference: g = int64 [2,E], g[0] = source i, g[1] = target j
  *     (ops/basic.py:66); aggregation target is j.  "Edge order" below = the caller's order of g.
- *   - `D` (latent width) must be a multiple of 32 for the MLP/GMP entries (MFMA tile width).
+ *   - `D` (latent width) of the MLP/GMP entries: a multiple of 32 (MFMA tile width), 32 <= D <= 256; the bf16
+ *     precisions only at D = 128 / 256 (other widths: BSMS_E_UNSUPPORTED).
  *   - An MLP is `hidden` x (Linear,ReLU) + Linear (+LayerNorm, no affine, eps 1e-5)
  *     (ops/basic.py:6-23).  `params` is a HOST array of 2*(hidden+1) device pointers in state_dict
  *     order: seq.0.weight, seq.0.bias, seq.2.weight, seq.2.bias, ...  Weights are [out,in] row-major
