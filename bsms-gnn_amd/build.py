@@ -10,14 +10,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libbsms_hip.so")
-SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "chain_d96.hip", "chain_d160.hip", "chain_d192.hip", "chain_d224.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip"]
-# csrc/experiments/*.hip (the fp32 fused edge backward, efuse32.hip) are NOT part of the product library: profiles/build_efv.sh
-# compiles them into the experiment builds (-DBSMS_EXPERIMENTS), where gmp.hip / chain.hip keep their hooks
-HEADERS = ["common.h", "chain.h", "chain_dev.h", os.path.join("..", "..", "include", "bsms_hip.h")]
+SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "chain_d32.hip", "chain_d64.hip", "chain_d96.hip", "chain_d128.hip", "chain_d160.hip", "chain_d192.hip", "chain_d224.hip",
+           "chain_d256.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip"]
+# chain.hip: prepack + dispatch on the latent width; chain_d<D>.hip: the chain kernels of one width (templates in chain_kernels.h /
+# chain_edge.h, launchers in chain_launch.h), one translation unit each so that they compile in parallel
+HEADERS = ["common.h", "chain.h", "chain_dev.h", "chain_kernels.h", "chain_edge.h", "chain_launch.h", os.path.join("..", "..", "include", "bsms_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 if os.environ.get("BSMS_EXPERIMENTS") == "1":   # profiling / A-B builds only: BSMS_DEBUG_FLAGS, in-kernel time stamps, launch-shape knobs
     FLAGS.append("-DBSMS_EXPERIMENTS")
-    SOURCES = SOURCES + [os.path.join("experiments", "efuse32.hip")]   # the hooks gmp.hip keeps under BSMS_EXPERIMENTS need it to link
 
 
 def _hipcc():

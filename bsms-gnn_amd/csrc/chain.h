@@ -90,10 +90,6 @@ struct ChainFwdArgs {
   const float4* wp[kMaxStages];  // packs (the Linear's bias travels in the pack header, see PackDesc)
   const float4* wp0b;  // IN_ROWS2: pack for x2 in stage 0 (same scale as wp[0]: PackDesc::mate; the stage's bias rides in THIS pack)
   float* store[kMaxStages];  // post-ReLU activation of stage l, act_floats(R, D) floats: values + sign bits (nullable)
-  int pieces;                // IN_EDGE, D = 128 (round 6): store_in / store[] receive the fp16 x 2 PIECES of the rows instead of fp32 values
-                             // (row r: K block c at byte 512 r + 128 c = 64 bytes of h pieces, 64 of l pieces, in the lane order of the B
-                             // operand; same size, sign bits in the same place) and store_exp[] the rows' scale exponents (RowScale::E)
-  int* store_exp[kMaxStages];  // pieces: [0] for store_in, [l + 1] for store[l]; pad_rows(R) ints each
   // ---- output
   float* y;           // OUT_LN / OUT_PLAIN: [R,D]; OUT_SMALL: [R,C]
   float* y2;          // OUT_PLAIN2: second head [R,D]
@@ -183,7 +179,7 @@ int launch_prepack(const PackTable& t, hipStream_t s);
 
 int launch_chain_fwd(int D, int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s);
 int launch_chain_bwd(int D, int gin_mode, int first_mode, const ChainBwdArgs& a, hipStream_t s);
-// the generic chain kernels at NB = 6 / 10 / 12 / 14 (D = 96 / 160 / 192 / 224), one translation unit each (chain_d*.hip)
+// the chain kernels of one width, NB = D / 16 = 2, 4, ... 16: defined in chain_launch.h, instantiated by one translation unit each (chain_d*.hip)
 template <int NB>
 int launch_chain_fwd_nb(int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s);
 template <int NB>
@@ -253,26 +249,6 @@ struct EdgeFusedBwdArgs {
   int ntiles;                 // filled by the launcher
   unsigned long long* timing; // experiments only: phase stamps (null in production)
 };
-// csrc/experiments/efuse32.hip (EXPERIMENT builds only): fp32 (BSMS_F32), round 6: LayerNorm backward + dgrad chain + dW / db of Linears 1..3 on chip WITHOUT forward recompute --
-// the forward saved a_0..a_2 as fp16 x 2 pieces (ChainFwdArgs::pieces), the backward brings their tiles HBM -> LDS by LDS-DMA; the
-// transposed packs stream through the LDS ring; partials in the layout of efuse.hip (launch_edge_fused_reduce sums them)
-struct EdgeFused32Args {
-  int64_t R;                  // B * E edge rows (plan order)
-  int32_t E, N;
-  const int32_t* dst;         // plan-order targets
-  const float* act[3];        // a_2, a_1, a_0 (execution order) as saved by k_edge_fwd SAVE == 2: pieces + sign bits (act_floats layout)
-  const int* aexp[3];         // their rows' scale exponents
-  const float4* wseq[3];      // FRAG_T packs of Linears 3, 2, 1
-  const float* dy;            // [B*N, D] gradient of the aggregate (gathered by target)
-  const float* y;             // [R, D] messages
-  const float* rstd;          // [R]
-  float* g0;                  // [pad_rows(R), D]: gradient w.r.t. the first edge Linear's output
-  float* part;                // per-workgroup partials, edge_fused_part_floats() floats
-  int ntiles;                 // filled by the launcher
-  unsigned long long* timing; // experiments only: phase stamps (null in production)
-};
-bool edge_fused32_supported(int64_t D, int H, int64_t p, int precision);
-int launch_edge_fused32_bwd(EdgeFused32Args a, int* nwg_out, hipStream_t s);
 constexpr int kEdgeFusedMaxWg = 256;
 bool edge_fused_supported(int64_t D, int H, int64_t p, int precision);
 size_t edge_fused_part_floats(int64_t rows);   // for a launch over `rows` edge rows: one partial per workgroup, at most kEdgeFusedMaxWg

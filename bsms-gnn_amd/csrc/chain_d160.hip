@@ -1,3 +1,8 @@
-// The generic chain kernels at D = 160 (NB = 10) in a translation unit of their own: see chain.hip.
-#define BSMS_CHAIN_NB 10
-#include "chain.hip"
+// The chain kernels and their launchers at D = 160 (NB = 10): a translation unit of its own, compiled in parallel with the other widths.
+#pragma clang fp contract(off)   // before the kernel headers: chain_dev.h says why
+#include "chain_launch.h"
+
+namespace bsms {
+template int launch_chain_fwd_nb<10>(int, int, const ChainFwdArgs&, hipStream_t);
+template int launch_chain_bwd_nb<10>(int, int, const ChainBwdArgs&, hipStream_t);
+}  // namespace bsms

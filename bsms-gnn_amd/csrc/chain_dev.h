@@ -1,6 +1,14 @@
 // Device-side building blocks of the chain kernels (register-tile helpers, the fp16 x 2 split, the LDS weight ring and its
-// loader, the MFMA stage of one Linear): shared by chain.hip and efuse32.hip.  Everything here has internal linkage (anonymous
-// namespace); the including file sets `#pragma clang fp contract(off)` BEFORE the include (see chain.hip for why).
+// loader, the MFMA stage of one Linear): shared by the kernel headers (chain_kernels.h, chain_edge.h) and the prepack (chain.hip).
+// Everything here has internal linkage (anonymous namespace).
+//
+// The including translation unit sets `#pragma clang fp contract(off)` BEFORE its first include.  hipcc defaults to
+// -ffp-contract=fast and decides PER INSTANTIATION whether a multiply feeding an add becomes one fma -- the LayerNorm
+// backward `g - m1 - y * m2` came out fused in some kernel variants and not in others, so the input gradient of a row
+// depended (in the last bit) on the launch shape that happened to process it (found by
+// tests/test_hip_parity.py::test_feature_split_kernels_equal_the_ring_kernels).  Every fused multiply-add of the arithmetic
+// is written as fmaf() explicitly; with the pragma nothing else is fused and all variants of a kernel (ring / single-round /
+// pipelined edge / feature-split) agree bit for bit.
 #pragma once
 #include "chain.h"
 

@@ -224,8 +224,6 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
   }
 }
 
-int device_cus() { return device_cu_count(); }   // common.h: cached per device
-
 }  // namespace
 
 namespace bsms {
@@ -240,7 +238,7 @@ int launch_edge_fwd_res(EdgeFwdResArgs a, hipStream_t s) {
   const hipError_t attr = attr_dev.ensure(reinterpret_cast<const void*>(&k_edge_fwd_res), LDS_BYTES);
   BSMS_REQUIRE(attr == hipSuccess, BSMS_E_HIP, "edge_fwd_res: cannot reserve %d bytes of LDS", LDS_BYTES);
   a.ntiles = int(ceil_div(a.R, 16));
-  const int nwg = int(std::min<int64_t>(ceil_div(a.ntiles, WAVES), device_cus()));
+  const int nwg = int(std::min<int64_t>(ceil_div(a.ntiles, WAVES), device_cu_count()));
   if (nwg > 0) {
     hipLaunchKernelGGL(k_edge_fwd_res, dim3(nwg), dim3(WAVES * 64), LDS_BYTES, s, a);
     BSMS_LAUNCH_CHECK();

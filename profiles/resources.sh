@@ -1,5 +1,5 @@
 #!/bin/bash
-# VGPR / scratch / occupancy of every kernel of a source file:  bash profiles/resources.sh chain.hip
+# VGPR / scratch / occupancy of every kernel of a source file:  bash profiles/resources.sh chain_d128.hip
 cd "$(dirname "$0")/../bsms-gnn_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC ${EXTRA} -c $1 -o /tmp/res_$$.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
 import sys,re
