@@ -1,0 +1,245 @@
+"""Device-resident trajectory bank: trajectories live in HBM, and a training batch is picked, noised, packed and masked
+there by one kernel (csrc/batch.hip: bsms_batch_assemble).  The host contributes a handful of integers per step: which
+(trajectory, frame) pairs make the batch, and the (seed, draw) pair of the noise.
+
+What is replaced: the reference's loader loop -- `proc_data` per sample on the host (datasets/base.py:238-289), the
+collate, and the upload of node_in / node_tar / node_mask per step (datapipe.TrajectoryDataset -> make_loader ->
+trainer.move_to_device here).  Without noise the batches are bit-equal to that route; with noise they follow the same
+arithmetic (`state + noise`, `target + (1 - gamma) * noise`, noise zero on masked nodes) with the generator documented
+in include/bsms_hip.h instead of torch's CPU generator.
+
+Meshes: with `cfg.consist_mesh` all trajectories share ONE interned hierarchy and `batch` returns the consistent-mesh
+tuple with stride-0 [B,...] index views, so the plan cache hits on every step.  Otherwise every trajectory keeps its
+graph.MeshBank entry (plans and edge weights resident) and `batch` returns the per-level LevelData list of
+`MeshBank.collate`."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _abi
+from .datapipe import SingleTrajReader, load_fields, pack_levels
+from .graph import MeshBank, _upload
+
+VALID_TYPES = {"airfoil": (0.0,), "cylinder_flow": (0.0, 5.0)}     # the codes datapipe.MASKS accepts (airfoil.py:23, cylinder_flow.py:24)
+_MASK64 = (1 << 64) - 1
+
+
+class _Sample(C.Structure):      # bsms_batch_sample (include/bsms_hip.h)
+    _fields_ = [("state_in", C.c_void_p), ("state_tar", C.c_void_p), ("pos", C.c_void_p), ("type", C.c_void_p), ("n", C.c_int64)]
+
+
+def epoch_picks(rng, lengths, order="trajectory"):
+    """One epoch of (trajectory, frame) picks.  "trajectory" replays datapipe.TrajectoryDataset.__iter__ draw for draw on the
+    same `numpy.random.Generator`: the trajectories are shuffled, then the frames within each as it comes up.  "global"
+    shuffles all pairs."""
+    if order == "trajectory":
+        trajs = list(range(len(lengths)))
+        rng.shuffle(trajs)
+        out = []
+        for si in trajs:
+            t_ids = np.arange(lengths[si])
+            rng.shuffle(t_ids)
+            out.extend((si, int(ti)) for ti in t_ids)
+        return out
+    if order != "global":
+        raise ValueError(f"order must be 'trajectory' or 'global', got {order!r}")
+    pairs = [(si, ti) for si, n in enumerate(lengths) for ti in range(n)]
+    return [pairs[k] for k in rng.permutation(len(pairs))]
+
+
+class _Traj:
+    __slots__ = ("state", "pos", "type", "pos_static", "type_static", "T", "N", "entry")
+
+
+class TrajectoryBank:
+    """`cfg`: what datapipe.TrajectoryDataset takes (field_names, output_field_names, consist_mesh, unet_depth, mesh_type,
+    noise_level, noise_gamma).  `process`: the model's BSGMP, needed for variable meshes only (it builds the per-mesh plans)."""
+
+    def __init__(self, cfg, dataset="airfoil", device=None, seed=0, process=None, max_bytes=None, order="trajectory", cache_dir=None):
+        if dataset not in VALID_TYPES:
+            raise ValueError(f"dataset must be one of {sorted(VALID_TYPES)}, got {dataset!r}")
+        if order not in ("trajectory", "global"):
+            raise ValueError(f"order must be 'trajectory' or 'global', got {order!r}")
+        self.cfg, self.dataset, self.order, self.cache_dir = cfg, dataset, order, cache_dir
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise _abi.BsmsError("TrajectoryBank needs a GPU device: trajectories are resident in HBM")
+        self.max_bytes, self.bytes_resident = max_bytes, 0
+        self._valid = (C.c_float * len(VALID_TYPES[dataset]))(*VALID_TYPES[dataset])
+        self._std = (C.c_float * len(cfg.noise_level))(*[float(v) for v in cfg.noise_level])
+        self._trajs = []
+        self._hier = None            # consistent mesh: (m_gs, m_ids) device tensors, shared by every trajectory
+        self._views = {}             # ... and their stride-0 [B,...] views per batch size
+        self._meshes = None if cfg.consist_mesh else MeshBank(process, self.device)
+        if self._meshes is not None and process is None:
+            raise ValueError("TrajectoryBank: variable meshes (cfg.consist_mesh = False) need process=model.process")
+        self._reseed(seed)
+
+    def _reseed(self, seed):
+        self.seed = int(seed) & _MASK64
+        self._rng = np.random.default_rng(self.seed)
+        self._epoch, self._cursor, self._draw = [], 0, 0
+
+    def __len__(self):
+        return len(self._trajs)
+
+    @property
+    def lengths(self):
+        """Frames with a target per trajectory (T - 1)."""
+        return [tr.T - 1 for tr in self._trajs]
+
+    # ------------------------------------------------------------------------------------------------ filling
+    def _claim(self, nbytes):
+        if self.max_bytes is not None and self.bytes_resident + nbytes > self.max_bytes:
+            raise _abi.BsmsError(f"TrajectoryBank: {self.bytes_resident + nbytes} bytes would be resident, max_bytes is {self.max_bytes}")
+        self.bytes_resident += nbytes
+
+    def _put(self, t):
+        t = t.contiguous()
+        self._claim(t.numel() * t.element_size())
+        return _upload(t, self.device)
+
+    def add(self, source):
+        """Upload ONE trajectory (a path or a dict, read through datapipe.load_fields).  Returns its index."""
+        cfg = self.cfg
+        reader = None
+        if self._hier is None:       # variable meshes, or the first trajectory of a consistent mesh: build / load the hierarchy
+            reader = SingleTrajReader(cfg, source, "train", self.cache_dir)
+            fields = reader.fields
+        else:
+            fields = load_fields(source, cfg.field_names)
+        state = torch.cat([fields[k] for k in cfg.output_field_names], dim=-1)
+        pos, typ = fields["mesh_pos"], fields["node_type"]
+        tr = _Traj()
+        tr.T, tr.N = int(state.shape[0]), int(state.shape[1])
+        if tr.T < 2:
+            raise ValueError("TrajectoryBank.add: a trajectory needs at least two frames")
+        if state.shape[-1] != len(cfg.noise_level):
+            raise ValueError(f"TrajectoryBank.add: {state.shape[-1]} state channels, cfg.noise_level has {len(cfg.noise_level)}")
+        if typ.shape[-1] != 1:
+            raise ValueError(f"TrajectoryBank.add: node_type must be [T,N,1], got {tuple(typ.shape)}")
+        tr.pos_static, tr.type_static = bool((pos == pos[:1]).all()), bool((typ == typ[:1]).all())
+        tr.entry = None
+        if cfg.consist_mesh:
+            if self._hier is None:
+                self._hier = ([self._put(g) for g in reader.m_gs], [self._put(i) for i in reader.m_ids], tr.N)
+            elif tr.N != self._hier[2]:
+                raise ValueError(f"TrajectoryBank.add: consistent mesh of {self._hier[2]} nodes, this trajectory has {tr.N}")
+        else:
+            before = len(self._meshes._by_content)
+            tr.entry = self._meshes.entry(pack_levels(state[0], None, None, reader.m_gs, reader.m_ids))
+            if len(self._meshes._by_content) > before:
+                self._claim(sum(t.numel() * t.element_size() for pair in tr.entry["keep"] for t in pair if t is not None))
+        tr.state = self._put(state)
+        tr.pos = self._put(pos[0] if tr.pos_static else pos)
+        tr.type = self._put(typ[0] if tr.type_static else typ)
+        self._trajs.append(tr)
+        return len(self._trajs) - 1
+
+    def add_sharded(self, sources, group=None):
+        """Data parallelism: rank r uploads its `rollout.rank_slice` of `sources` and mixes its rank into the seed, so the
+        ranks draw different orders and different noise.  Returns the indices added on this rank."""
+        import torch.distributed as dist
+        from .rollout import rank_slice
+        sources = list(sources)
+        lo, hi = rank_slice(len(sources), group)
+        rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
+        if rank:
+            self._reseed((self.seed + 0x9E3779B97F4A7C15 * rank) & _MASK64)
+        return [self.add(s) for s in sources[lo:hi]]
+
+    # ------------------------------------------------------------------------------------------------ batches
+    def _assemble(self, picks, noisy, draw, return_noise):
+        cfg = self.cfg
+        n_c, table = len(self._std), (_Sample * len(picks))()
+        p, rows = None, 0
+        for k, (si, ti) in enumerate(picks):
+            tr = self._trajs[si]
+            if not 0 <= ti < tr.T - 1:
+                raise IndexError(f"frame {ti} of trajectory {si}: it has {tr.T - 1} frames with a target")
+            frame = tr.N * 4
+            s = table[k]
+            s.state_in = tr.state.data_ptr() + ti * frame * n_c
+            s.state_tar = tr.state.data_ptr() + (ti + 1) * frame * n_c
+            s.pos = tr.pos.data_ptr() + (0 if tr.pos_static else ti * frame * tr.pos.shape[-1])
+            s.type = tr.type.data_ptr() + (0 if tr.type_static else ti * frame)
+            s.n = tr.N
+            rows += tr.N
+            if p is None:
+                p = int(tr.pos.shape[-1])
+            elif p != tr.pos.shape[-1]:
+                raise ValueError("TrajectoryBank: trajectories with different position widths in one batch")
+        new = lambda w: torch.empty(rows, w, device=self.device, dtype=torch.float32)
+        node_in, node_tar, node_mask = new(n_c + p + 1), new(n_c), new(1)
+        noise = new(n_c) if return_noise else None
+        with torch.cuda.device(self.device):
+            _abi.check(_abi.lib().bsms_batch_assemble(
+                C.addressof(table), len(picks), n_c, p, C.addressof(self._std) if noisy else None, float(cfg.noise_gamma),
+                C.addressof(self._valid), len(self._valid), self.seed, int(draw) & _MASK64, node_in.data_ptr(), node_tar.data_ptr(),
+                node_mask.data_ptr(), None if noise is None else noise.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
+                "bsms_batch_assemble")
+        return node_in, node_tar, node_mask, noise
+
+    def _hier_views(self, B):
+        v = self._views.get(B)
+        if v is None:
+            m_gs, m_ids, _ = self._hier
+            v = self._views[B] = ([g.unsqueeze(0).expand(B, *g.shape) for g in m_gs], [i.unsqueeze(0).expand(B, *i.shape) for i in m_ids])
+        return v
+
+    def batch(self, picks, train=True, draw=None, return_noise=False):
+        """The device batch of `picks`, a list of (trajectory, frame).  `train`: inject the training noise; `draw` selects the
+        noise of this batch (None: the bank's running batch counter, which then advances).  Consistent mesh:
+        [node_in [B,N,C+p+1], node_tar [B,N,C], node_mask [B,N,1], m_gs, m_ids]; variable meshes: the per-level LevelData list.
+        `return_noise` appends the noise tensor that was added ([B,N,C] / [rows,C]; zeros when `train` is false)."""
+        picks = [(int(si), int(ti)) for si, ti in picks]
+        if not picks:
+            raise ValueError("TrajectoryBank.batch: no picks")
+        if draw is None:
+            draw, self._draw = self._draw, self._draw + 1
+        node_in, node_tar, node_mask, noise = self._assemble(picks, bool(train), draw, return_noise)
+        if self.cfg.consist_mesh:
+            B, N = len(picks), self._hier[2]
+            m_gs, m_ids = self._hier_views(B)
+            out = [node_in.view(B, N, -1), node_tar.view(B, N, -1), node_mask.view(B, N, 1), m_gs, m_ids]
+            noise = None if noise is None else noise.view(B, N, -1)
+        else:
+            out = self._meshes.assemble([self._trajs[si].entry for si, _ in picks], node_in, node_tar, node_mask)
+        return (out, noise) if return_noise else out
+
+    def next_picks(self, B):
+        """The next `B` picks of the epoch order (fewer at the end of an epoch, like a loader without drop_last)."""
+        if self._cursor >= len(self._epoch):
+            if not self._trajs:
+                raise ValueError("TrajectoryBank: no trajectory has been added")
+            self._epoch, self._cursor = epoch_picks(self._rng, self.lengths, self.order), 0
+        picks = self._epoch[self._cursor:self._cursor + int(B)]
+        self._cursor += len(picks)
+        return picks
+
+    def sample(self, B, train=True, return_noise=False):
+        """`batch` of the next `B` picks of the epoch order; the noise draw counts the batches."""
+        return self.batch(self.next_picks(B), train=train, return_noise=return_noise)
+
+    # ------------------------------------------------------------------------------------------------ rollout
+    def hierarchy(self, i):
+        """(m_gs, m_ids) of trajectory `i` as device tensors ([2,E_l] / [N_{l+1}])."""
+        if self.cfg.consist_mesh:
+            return list(self._hier[0]), list(self._hier[1])
+        keep = self._trajs[i].entry["keep"]
+        return [g for g, _ in keep], [f for _, f in keep[:len(keep) - 1]]
+
+    def trajectory(self, i):
+        """What datapipe.TrajectoryDataset(mode="rollout") yields for trajectory `i`, on the device and without noise:
+        (node_in [T-1,N,C+p+1], node_tar [T-1,N,C], node_mask [T-1,N,1], m_gs, m_ids)."""
+        tr = self._trajs[i]
+        node_in, node_tar, node_mask, _ = self._assemble([(i, t) for t in range(tr.T - 1)], False, 0, False)
+        m_gs, m_ids = self.hierarchy(i)
+        return node_in.view(tr.T - 1, tr.N, -1), node_tar.view(tr.T - 1, tr.N, -1), node_mask.view(tr.T - 1, tr.N, 1), m_gs, m_ids
+
+    def rollouts(self, indices=None):
+        """Iterable of rollout batches for rollout.rollout_dataset: `trajectory(i)` with the loader's batch axis of 1."""
+        for i in (range(len(self._trajs)) if indices is None else indices):
+            inp, tar, mask, m_gs, m_ids = self.trajectory(i)
+            yield inp.unsqueeze(0), tar.unsqueeze(0), mask.unsqueeze(0), [g.unsqueeze(0) for g in m_gs], [f.unsqueeze(0) for f in m_ids]

@@ -462,9 +462,14 @@ class MeshBank:
         """`samples`: list of per-sample lists of host LevelData (what `collate_variable_meshes` takes).  Returns the per-level
         device LevelData of the block-diagonal batch."""
         ents = [self.entry(s) for s in samples]
-        depth = len(samples[0]) - 1
         cat0 = lambda get: None if get(samples[0][0]) is None else _upload(torch.cat([get(s[0]) for s in samples], 0), self.device)
-        x, y, mask = cat0(lambda d: d.x), cat0(lambda d: d.y), cat0(lambda d: d.mask)
+        return self.assemble(ents, cat0(lambda d: d.x), cat0(lambda d: d.y), cat0(lambda d: d.mask))
+
+    def assemble(self, ents, x, y, mask):
+        """The per-level device LevelData of the block-diagonal batch of the resident meshes `ents` (one `entry` per sample), given
+        the level-0 node tensors `x` / `y` / `mask` of the batch already on the device (databank.TrajectoryBank writes them there
+        itself; `collate` uploads them)."""
+        depth = len(ents[0]["plans"]) - 1
         out, plans, ews = [], [], []
         for lvl in range(depth + 1):
             parts = [e["plans"][lvl] for e in ents]

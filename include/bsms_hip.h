@@ -349,6 +349,39 @@ int bsms_sim_loss_bwd(const float* pred, const float* target, const float* mask,
                       const double* meansq, const double* std_eps, const float* sums, float* loss_out /* nullable */,
                       float* grad_norm_pred, bsms_stream_t stream);
 
+/* ---------------------------------------------------------------- batch assembly from resident trajectories ---
+ * The level-0 node tensors of a batch (datasets/base.py:238-289, `proc_data`, plus the collate) built by ONE launch from
+ * trajectories that live in HBM.  `samples` is a HOST table; sample s contributes n rows, rows of consecutive samples
+ * are consecutive in the outputs (batch-global row r):
+ *   node_in  [R, C+p+1] = [state_in(C) + noise | pos(p) | type(1)]
+ *   node_tar [R, C]     = state_tar + g * noise,   g = fl32(1 - noise_gamma)   (1 - noise_gamma evaluated in fp64)
+ *   node_mask[R]        = 1 if type equals one of the n_valid codes in `valid_types` (HOST), else 0
+ *   noise_out[R, C]     = the noise that was added (nullable)
+ * `noise_std` (HOST [C]) NULL: no noise, the state columns are copied bit for bit.  The table travels as a kernel argument,
+ * 64 samples per launch (more samples: more launches, the row offset carried across); nothing is uploaded and nothing
+ * synchronises.  Envelope: C in 1..8, p in 1..7, n_valid in 1..4 (BSMS_E_UNSUPPORTED otherwise), R < 2^32; null pointers
+ * give BSMS_E_INVALID_ARG; n_samples == 0 returns BSMS_OK without a launch; all checked before any device call.
+ *
+ * NOISE CONTRACT (independent of launch shape and of the chunking).  For batch-global row r and channel c:
+ *   (x0,x1,x2,x3) = Philox4x32-10( counter = (r, c / 4, draw_lo, draw_hi), key = (seed_lo, seed_hi) )
+ *                   multipliers 0xD2511F53 (on counter word 0), 0xCD9E8D57 (on word 2); key increments 0x9E3779B9, 0xBB67AE85
+ *   u_i = ((x_i >> 8) + 0.5) * 2^-24                                   (a real number in (0,1); see below)
+ *   z0 = sqrt(-2 ln u0) cos(2 pi u1),  z1 = sqrt(-2 ln u0) sin(2 pi u1);  z2, z3 likewise from (u2, u3)
+ *   noise(r,c) = fl32(noise_std[c]) * z[c % 4] in fp32, and exactly 0 where node_mask is 0
+ *   node_in = fl32(state + noise),  node_tar = fl32(tar + fl32(g * noise))     (no fused multiply-add)
+ * u_i has 25 significant bits when x_i >> 8 >= 2^23, so the kernel never rounds it: it forms w = min(u, 1 - u), which fp32
+ * holds exactly, takes ln u as logf(w) or log1pf(-w) and the angle as fl32(fl32(2 pi) * w) with the sign of the sine
+ * flipped in the upper half.  logf / log1pf / sqrtf / sincosf are the accurate library versions: z is within ~2.5e-6 of
+ * the fp64 evaluation of the formulas above (|z| <= 5.9). */
+typedef struct {
+  const float *state_in, *state_tar, *pos, *type; /* DEVICE: [n,C], [n,C], [n,p], [n] */
+  int64_t n;
+} bsms_batch_sample;
+int bsms_batch_assemble(const bsms_batch_sample* samples, int64_t n_samples, int64_t C, int64_t p,
+                        const float* noise_std /* HOST [C], nullable */, double noise_gamma,
+                        const float* valid_types /* HOST */, int64_t n_valid, uint64_t seed, uint64_t draw, float* node_in,
+                        float* node_tar, float* node_mask, float* noise_out /* nullable */, bsms_stream_t stream);
+
 /* ---------------------------------------------------------------- hierarchy builder (host) ---
  * BistrideMultiLayerGraph (graph_wrappers/bsms_graph_wrapper.py:8-154 + graph_wrapper.py:67-134): the
  * bi-stride multi-level hierarchy of a mesh, built natively on the HOST (no GPU needed, no SciPy/MKL).
