@@ -5,11 +5,12 @@ libbsms_hip.so (include/bsms_hip.h).  Import name: `bsms_gnn_amd` (directory: `b
 from . import _abi  # noqa: F401
 from .graph import LevelData, LevelPlan, MeshBank, clear_plan_cache, collate_variable_meshes, concat_plans, plan_for  # noqa: F401
 from .model import BSMS_Simulator, Normalizer, masked_rmse  # noqa: F401
-from .ops import BSGMP, GMP, MLP, InferenceSession, Unpool, WeightedEdgeConv, degree, scatter_sum  # noqa: F401
+from .ops import BSGMP, GMP, MLP, InferenceSession, Unpool, WeightedEdgeConv, degree, error_sums, scatter_sum  # noqa: F401
+from .eval import error_mean_std  # noqa: F401
 from .databank import TrajectoryBank, epoch_picks  # noqa: F401
 from .dp import DataParallel, GradBuckets, global_masked_rmse  # noqa: F401
 from .hierarchy import BistrideMultiLayerGraph, to_flat_edge  # noqa: F401
-from .rollout import RolloutErrors, rank_slice, rollout_batch, rollout_dataset, rollout_errors, rollout_one_traj, rollout_rmse  # noqa: F401
+from .rollout import RolloutErrors, rank_slice, rollout_bank, rollout_batch, rollout_dataset, rollout_errors, rollout_one_traj, rollout_rmse  # noqa: F401
 from .step import FusedStep  # noqa: F401
 from .trainer import DevicePrefetcher, FusedAdamW, Trainer, WarmupCosineDecay  # noqa: F401
 

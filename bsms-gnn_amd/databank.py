@@ -230,6 +230,12 @@ class TrajectoryBank:
         keep = self._trajs[i].entry["keep"]
         return [g for g, _ in keep], [f for _, f in keep[:len(keep) - 1]]
 
+    def resident(self, i):
+        """The resident tensors of trajectory `i` themselves, not copies: (state [T,N,C], node_type [N,1] if it is static else
+        [T,N,1]).  rollout.rollout_bank reads its targets from `state[1:]` in place."""
+        tr = self._trajs[i]
+        return tr.state, tr.type
+
     def trajectory(self, i):
         """What datapipe.TrajectoryDataset(mode="rollout") yields for trajectory `i`, on the device and without noise:
         (node_in [T-1,N,C+p+1], node_tar [T-1,N,C], node_mask [T-1,N,1], m_gs, m_ids)."""

@@ -76,6 +76,59 @@ def _grad_targets(params):
     return out
 
 
+# --------------------------------------------------------------------------------- evaluation sums
+def _segment_view(t, what, S, seg_rows, width, stride):
+    """(tensor whose data_ptr is row 0 of segment 0, rows between segments) of a float32 device tensor read as S segments of
+    [seg_rows, width]: contiguous, or [S, seg_rows(, width)] with dense segments and any row-aligned step between them (a
+    column block of a wider tensor; a stride-0 expand).  `stride` overrides the step.  The span is checked against the storage."""
+    if not t.is_cuda or t.dtype != torch.float32:
+        raise _abi.BsmsError(f"error_sums: {what} must be a float32 GPU tensor (got {t.dtype} on {t.device}); there is no CPU fallback")
+    if stride is None:
+        if t.numel() == S * seg_rows * width and t.is_contiguous():
+            stride = seg_rows
+        elif t.numel() == seg_rows * width and t.is_contiguous():
+            stride = 0                                   # one segment's worth: shared by all segments
+        else:
+            seg = t[0] if t.dim() >= 2 and t.shape[0] == S else None
+            if seg is None or seg.numel() != seg_rows * width or not seg.is_contiguous() or t.stride(0) % width:
+                raise ValueError(f"error_sums: {what} of shape {tuple(t.shape)} / strides {tuple(t.stride())} is not {S} dense segments of "
+                                 f"[{seg_rows}, {width}] a whole number of rows apart")
+            stride = t.stride(0) // width
+    stride = int(stride)
+    if stride < 0:
+        raise ValueError(f"error_sums: {what}_stride = {stride}")
+    room = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+    if seg_rows and ((S - 1) * stride + seg_rows) * width > room:
+        raise ValueError(f"error_sums: {what}: {S} segments of {seg_rows} rows, {stride} rows apart, reach past the tensor's storage")
+    return t, stride
+
+
+def error_sums(pred, target, mask, seg_rows, *, pred_stride=None, target_stride=None, mask_stride=None):
+    """Masked error sums of S segments of `seg_rows` rows (bsms_error_sums): fp64 [S, 1+3C] = [M | SE | AE | TT] per segment,
+    d = fl32(pred - target).  `pred` is [S, seg_rows, C] (or contiguous [S * seg_rows, C]); `target` and `mask` hold the same
+    segments, or ONE segment shared by all.  Segments may be views any whole number of rows apart -- a column block of a wider
+    tensor, a stride-0 expand -- and the `*_stride` arguments (in rows) override what the views say.  One launch pair on the
+    current stream; nothing is copied and nothing synchronises."""
+    C, seg_rows = int(pred.shape[-1]), int(seg_rows)
+    if seg_rows < 0:
+        raise ValueError(f"error_sums: seg_rows = {seg_rows}")
+    if pred.dim() == 3:
+        S = int(pred.shape[0])
+    elif seg_rows == 0 or pred.numel() % (seg_rows * C):
+        raise ValueError(f"error_sums: pred of shape {tuple(pred.shape)} does not say how many segments of {seg_rows} rows it holds")
+    else:
+        S = pred.numel() // (seg_rows * C)
+    pred, ps = _segment_view(pred, "pred", S, seg_rows, C, pred_stride)
+    target, ts = _segment_view(target, "target", S, seg_rows, C, target_stride)
+    mask, ms = _segment_view(mask, "mask", S, seg_rows, 1, mask_stride)
+    L = _abi.lib()
+    sums = torch.empty(S, 1 + 3 * C, device=pred.device, dtype=torch.float64)
+    work = _workspace(pred.device, L.bsms_error_sums_work_bytes(S, seg_rows))
+    _abi.check(L.bsms_error_sums(pred.data_ptr(), target.data_ptr(), mask.data_ptr(), S, seg_rows, C, ps, ts, ms, sums.data_ptr(),
+                                 work.data_ptr(), _stream()), "bsms_error_sums")
+    return sums
+
+
 # --------------------------------------------------------------------------------- tensor prims
 class _SegmentSum(torch.autograd.Function):
     @staticmethod

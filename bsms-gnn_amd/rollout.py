@@ -169,6 +169,33 @@ class RolloutErrors:
         self.time(rmse_t, accumulate=True)
         return rmse, rmse_c, rmse_t
 
+    def add_sums(self, sums):
+        """`add` from the masked error sums of ONE trajectory (`ops.error_sums` with one segment per time step): sums [T-1, 1+3C]
+        fp64 = [M | SE | AE | TT].  The three figures of `rollout_errors` follow from them,
+          rmse [1,1] = sqrt(sum SE / sum M / C)     rmse_c [T-1,C] = sqrt(SE / M)     rmse_t = rmse_c.T
+        (evaluated in fp64, stored as float32) and are fed to the accumulators exactly as `add` feeds them."""
+        from .model import Normalizer
+        sums = sums.to(torch.float64)
+        if sums.dim() != 2 or sums.shape[1] < 4 or (sums.shape[1] - 1) % 3:
+            raise ValueError(f"RolloutErrors.add_sums: sums [T-1, 1+3C] expected, got {tuple(sums.shape)}")
+        C = (sums.shape[1] - 1) // 3
+        if self.time is not None and (self.time.size != sums.shape[0] or self.channel.size != C):
+            raise ValueError(f"RolloutErrors.add_sums: {sums.shape[0]} time steps of {C} channels, the accumulators were started with "
+                             f"{self.time.size} of {self.channel.size} (trajectories of different lengths need accumulators of their own)")
+        M, SE = sums[:, :1], sums[:, 1:1 + C]
+        rmse = torch.sqrt(SE.sum() / M.sum() / C).float().reshape(1, 1)
+        rmse_c = torch.sqrt(SE / M).float()
+        rmse_t = rmse_c.detach().clone().T
+        if self.all is None:
+            dev = sums.device if self.device is None else self.device
+            self.all = Normalizer(1, device=dev, name="rmse_accumulator")
+            self.channel = Normalizer(C, device=dev, name="rmse_accumulators_of_channel")
+            self.time = Normalizer(sums.shape[0], device=dev, name="rmse_accumulators_of_time")
+        self.all(rmse, accumulate=True)
+        self.channel(rmse_c, accumulate=True)
+        self.time(rmse_t, accumulate=True)
+        return rmse, rmse_c, rmse_t
+
     def _ensure(self, T1, C, device):
         """A rank that got no trajectory still has to take part in the merge (with zero weight)."""
         from .model import Normalizer
@@ -189,6 +216,62 @@ class RolloutErrors:
         """{name: (mean, std)} for name in all / channel / time (rollout.py:118-143); fp64 tensors."""
         return {k: (a.mean().detach().clone(), a.std_with_epsilon().detach().clone())
                 for k, a in (("all", self.all), ("channel", self.channel), ("time", self.time))}
+
+
+@torch.no_grad()
+def rollout_bank(trainer, bank, indices=None, batch=8, use_graph=False, errors=None, keep_results=False):
+    """Rollout evaluation of the trajectories of a `databank.TrajectoryBank`, up to `batch` of them advanced together, with
+    the error statistics taken on the device (`ops.error_sums` -> `RolloutErrors.add_sums`).  Returns the `RolloutErrors`;
+    with `keep_results` also the list of [T-1, N_i, C] device results in `indices` order (views of their group's tensor).
+
+    Trajectories are taken in `indices` order (default: all) in groups of consecutive trajectories of EQUAL length T, a
+    group ending early where T changes.  Consistent mesh: the group's initial conditions and masks are one
+    `bank.batch([(i, 0) ...], train=False)` and one stepper advances [B,N,.] into results [T-1,B,N,C].  Variable meshes: the
+    same call yields the block-diagonal union of the group's meshes (graph.MeshBank, one plan concatenation per level and
+    group) and the stepper runs with a batch axis of 1 over sum N rows into results [T-1, sum N, C].  Per trajectory ONE
+    error_sums launch with a segment per time step then reads strided views only: its column / row block of `results`, the
+    bank's resident state[1:] as the target, and its frame-0 node mask shared by all steps.  The accumulators are fed in
+    `indices` order whatever the grouping.
+
+    Not here: data-parallel sharding (`rollout_dataset` keeps that role), the sums fused into the step's epilogue, and
+    groups of unequal T."""
+    from .ops import error_sums
+    model = trainer.model if hasattr(trainer, "model") else trainer
+    errors = RolloutErrors(bank.device) if errors is None else errors
+    indices = list(range(len(bank))) if indices is None else [int(i) for i in indices]
+    batch = max(int(batch), 1)
+    consistent = bool(bank.cfg.consist_mesh)
+    kept, k = [], 0
+    while k < len(indices):
+        group = [indices[k]]
+        T = bank.resident(group[0])[0].shape[0]
+        while len(group) < batch and k + len(group) < len(indices) and bank.resident(indices[k + len(group)])[0].shape[0] == T:
+            group.append(indices[k + len(group)])
+        k += len(group)
+        data = bank.batch([(i, 0) for i in group], train=False)
+        if consistent:
+            ic, _, mask, m_gs, m_ids = data
+        else:
+            ic, mask = data[0].x.unsqueeze(0), data[0].mask.unsqueeze(0)
+            m_gs, m_ids = [d.edge_index.unsqueeze(0) for d in data], [d.face.unsqueeze(0) for d in data[:-1]]
+        C = bank.resident(group[0])[0].shape[-1]
+        results = ic.new_empty(T - 1, *ic.shape[:-1], C)
+        stepper = _Stepper(model, ic, mask, m_gs, m_ids, C, use_graph and ic.is_cuda)
+        for ti in range(T - 1):
+            results[ti] = stepper.step()
+        row0 = 0
+        for b, i in enumerate(group):
+            state = bank.resident(i)[0]
+            n = state.shape[1]
+            if consistent:
+                mine, node_mask = results[:, b], mask[b, :, 0]
+            else:
+                mine, node_mask = results[:, 0, row0:row0 + n], mask[0, row0:row0 + n, 0]
+                row0 += n
+            errors.add_sums(error_sums(mine, state[1:], node_mask, n, mask_stride=0))
+            if keep_results:
+                kept.append(mine)
+    return (errors, kept) if keep_results else errors
 
 
 @torch.no_grad()

@@ -226,6 +226,26 @@ class Trainer:
         se = (pred - tar) ** 2
         return torch.sqrt((se * mask).sum() / mask.sum() / se.shape[-1])
 
+    def get_error(self, data, relative=True):
+        """trainer/trainer.py:231-271: (error_mean, error_std) per channel as float32 NumPy arrays [C] -- the masked absolute
+        error, divided by each sample's target scale when `relative`.  The reference copies prediction, target and mask to the
+        host and reduces there; here one bsms_error_sums launch reduces over the nodes, eval.error_mean_std finishes on the
+        device, and 2C numbers are copied back.  Consistent mesh: B samples of N rows; variable meshes: the reference sees the
+        block-diagonal batch as [1, sum N, C], i.e. ONE sample of sum N rows (its target and mask stay [sum N, C] / [sum N, 1]
+        there, which NumPy broadcasts for the error but reduces over the CHANNEL axis for the scale; the scale here is the
+        per-channel one over the sum N rows, what the function computes whenever target and prediction have the same rank).
+        During warm-up the prediction is zeros (and the normalisers accumulate), as in the reference."""
+        from .eval import error_mean_std
+        from .ops import error_sums
+        data = self.move_to_device(data)
+        with torch.no_grad():
+            pred = self.get_pred(data)
+            tar, mask = self.get_label_mask(data)
+            rows = pred.shape[-2]
+            mean, std = error_mean_std(error_sums(pred.reshape(-1, rows, pred.shape[-1]), tar, mask, rows), rows, relative)
+            out = torch.stack([mean, std]).float().cpu().numpy()
+        return out[0], out[1]
+
     def iter(self, data):
         """One training iteration (trainer.py:134-156): statistics only during warm-up, otherwise
         fwd + loss + bwd (+ gradient all-reduce) + clip + AdamW + LR schedule."""

@@ -349,6 +349,30 @@ int bsms_sim_loss_bwd(const float* pred, const float* target, const float* mask,
                       const double* meansq, const double* std_eps, const float* sums, float* loss_out /* nullable */,
                       float* grad_norm_pred, bsms_stream_t stream);
 
+/* ---------------------------------------------------------------- evaluation: masked error sums ---
+ * The reductions behind the reference's evaluation figures -- `Trainer.get_error` (trainer/trainer.py:254-269: per-sample
+ * target scale, mean and standard deviation of the masked absolute error) and the rollout driver's RMSEs (rollout.py:99-107)
+ * -- which the reference takes on the host after copying prediction, target and mask there.  One call over S segments
+ * (the samples of a batch, or the time steps of a rolled-out trajectory) of seg_rows rows each:
+ *   sums[s, :] = [ M | SE[0..C) | AE[0..C) | TT[0..C) ]   (DEVICE double, row length 1 + 3C), over the rows r of segment s with
+ *   d = fl32(pred - target) (ONE fp32 rounding, as the reference's subtraction) and m = mask:
+ *     M = sum m    SE[c] = sum m * d_c^2    AE[c] = sum m * |d_c|    TT[c] = sum m * target_c^2    (products and sums in fp64)
+ * Segment s reads pred + s * pred_stride * C, target + s * target_stride * C and mask + s * mask_stride: the strides count ROWS,
+ * so a segment can be a column block of a wider tensor; a mask_stride of 0 shares one mask between all segments.  Rows inside
+ * a segment are contiguous ([seg_rows, C] / [seg_rows]).
+ * Limits: C in 1..8 (BSMS_E_UNSUPPORTED otherwise, checked before any pointer is looked at), seg_rows in 0..2^31-1, S >= 0
+ * (at least 2^20 segments per call).  S == 0 returns BSMS_OK and touches nothing; seg_rows == 0 writes zeros; null pointers
+ * with work to do give BSMS_E_INVALID_ARG.
+ * The call allocates nothing, does not synchronise and reads nothing back: it can be captured into a HIP graph.  `work` holds
+ * bsms_error_sums_work_bytes(S, seg_rows) bytes (non-decreasing in both arguments).
+ * DETERMINISM: no atomics.  The rows of a segment are cut into pieces of 1024 rows counted from the segment's own first row,
+ * each piece is reduced in a fixed tree, and a second kernel adds the pieces of a segment in index order -- a segment's sums
+ * are bit-identical from run to run and do not depend on S, on the strides or on the other segments of the launch. */
+size_t bsms_error_sums_work_bytes(int64_t S, int64_t seg_rows);
+int bsms_error_sums(const float* pred, const float* target, const float* mask, int64_t S, int64_t seg_rows, int64_t C,
+                    int64_t pred_stride, int64_t target_stride, int64_t mask_stride, double* sums, void* work,
+                    bsms_stream_t stream);
+
 /* ---------------------------------------------------------------- batch assembly from resident trajectories ---
  * The level-0 node tensors of a batch (datasets/base.py:238-289, `proc_data`, plus the collate) built by ONE launch from
  * trajectories that live in HBM.  `samples` is a HOST table; sample s contributes n rows, rows of consecutive samples
