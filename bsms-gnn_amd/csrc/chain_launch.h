@@ -129,19 +129,6 @@ void pick_stream(int64_t ntiles, int cw, int nload_default, int& nload, int& nri
   while (nring > 3 && (nring - 2) * mine > 63) --nring;
 }
 
-// One launch of a chain kernel that takes its weight ring as dynamic LDS.  The first launch of a kernel on a device raises
-// its LDS limit to `lds_max` (the deepest ring of the width; DynLdsAttr keeps one answer per kernel and device).  `what`
-// names the launcher and `build` the variant (null: the plain ring kernel) in the error text.
-template <auto Kernel, class Args>
-int launch_ring(const char* what, const char* build, unsigned grid, unsigned threads, size_t lds, size_t lds_max, const Args& a, hipStream_t s) {
-  static DynLdsAttr attr_dev;
-  const hipError_t attr = attr_dev.ensure(reinterpret_cast<const void*>(Kernel), (int)lds_max);
-  if (build) BSMS_REQUIRE(attr == hipSuccess, BSMS_E_HIP, "%s: cannot reserve LDS (%s)", what, build);
-  BSMS_REQUIRE(attr == hipSuccess, BSMS_E_HIP, "%s: cannot reserve %zu bytes of LDS", what, lds_max);
-  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds, s, a);
-  BSMS_LAUNCH_CHECK();
-  return BSMS_OK;
-}
 template <int NB>
 size_t ring_lds_max() { return Ring<NB>::lds_bytes(max_ring<NB>()); }
 
@@ -155,8 +142,8 @@ int launch_edge_fwd_t(ChainFwdArgs& a, hipStream_t s) {
   const size_t lds = Ring<NB>::lds_bytes(a.nring);
   static const int lone = knob("BSMS_EDGE_LONE", 1);
   if (lone && a.ntiles <= device_cu_count() && !a.timing)   // one round of workgroups: the variant that passes the chunk barrier early (stage_rb<LONE>)
-    return launch_ring<k_edge_fwd<NB, RB, SAVE, true>>("edge_fwd", "single-round build", grid, threads, lds, ring_lds_max<NB>(), a, s);
-  return launch_ring<k_edge_fwd<NB, RB, SAVE>>("edge_fwd", nullptr, grid, threads, lds, ring_lds_max<NB>(), a, s);
+    return launch_dyn_lds<k_edge_fwd<NB, RB, SAVE, true>>("edge_fwd", "single-round build", grid, threads, lds, ring_lds_max<NB>(), a, s);
+  return launch_dyn_lds<k_edge_fwd<NB, RB, SAVE>>("edge_fwd", nullptr, grid, threads, lds, ring_lds_max<NB>(), a, s);
 }
 
 // the software-pipelined edge kernels take the production configuration only; anything else stays on k_chain_fwd
@@ -189,8 +176,8 @@ int launch_edge_bwd_t(ChainBwdArgs& a, hipStream_t s) {
   const size_t lds = Ring<NB>::lds_bytes(a.nring);
   static const int lone = knob("BSMS_EDGE_LONE", 1);
   if (lone && a.ntiles <= device_cu_count())   // see launch_edge_fwd_t
-    return launch_ring<k_edge_bwd<NB, RB, true>>("edge_bwd", "single-round build", grid, threads, lds, ring_lds_max<NB>(), a, s);
-  return launch_ring<k_edge_bwd<NB, RB>>("edge_bwd", nullptr, grid, threads, lds, ring_lds_max<NB>(), a, s);
+    return launch_dyn_lds<k_edge_bwd<NB, RB, true>>("edge_bwd", "single-round build", grid, threads, lds, ring_lds_max<NB>(), a, s);
+  return launch_dyn_lds<k_edge_bwd<NB, RB>>("edge_bwd", nullptr, grid, threads, lds, ring_lds_max<NB>(), a, s);
 }
 
 template <int NB>
@@ -268,24 +255,24 @@ int launch_fwd_t(const ChainFwdArgs& a0, hipStream_t s) {
   const size_t lds = a.bf16 ? Ring<NB, 1>::lds_bytes(a.nring) : Ring<NB>::lds_bytes(a.nring), lds_max = ring_lds_max<NB>();
   // ---- the variant
   if constexpr (NB == 8 && IN == IN_EDGE) {   // the only production instantiation with stamps
-    if (a.timing) return launch_ring<k_chain_fwd<NB, IN, OUT, true>>("chain_fwd", "timing build", grid, threads, lds, lds_max, a, s);
+    if (a.timing) return launch_dyn_lds<k_chain_fwd<NB, IN, OUT, true>>("chain_fwd", "timing build", grid, threads, lds, lds_max, a, s);
   }
 #ifdef BSMS_EXPERIMENTS
   if constexpr (NB == 8 && IN == IN_ROWS2 && OUT == OUT_LN) {   // phase stamps of a single-round node chain (profiles/lone_timeline.py)
     if (a.timing && a.ntiles <= device_cu_count())
-      return launch_ring<k_chain_fwd<NB, IN, OUT, true, false, true>>("chain_fwd", "timing build", grid, threads, lds, lds_max, a, s);
+      return launch_dyn_lds<k_chain_fwd<NB, IN, OUT, true, false, true>>("chain_fwd", "timing build", grid, threads, lds, lds_max, a, s);
   }
 #endif
   if constexpr ((NB == 8 || NB == 16) && (IN == IN_EDGE || IN == IN_ROWS2) && OUT == OUT_LN) {   // the bf16 arithmetic: edge MLP (BSMS_BF16), node MLP (BSMS_BF16_NODES)
-    if (a.bf16) return launch_ring<k_chain_fwd<NB, IN, OUT, false, true>>("chain_fwd", "bf16 build", grid, threads, lds, lds_max, a, s);
+    if (a.bf16) return launch_dyn_lds<k_chain_fwd<NB, IN, OUT, false, true>>("chain_fwd", "bf16 build", grid, threads, lds, lds_max, a, s);
   }
   BSMS_REQUIRE(!a.bf16, BSMS_E_UNSUPPORTED, "chain_fwd: bf16 precision is built for the edge and node MLPs at D = 128 / 256 only");
   // (D = 96 has no single-round build: its single-round launches stay on the ring kernel, which saves a set of instantiations)
   if constexpr (NB >= 8) {   // one round of workgroups = a single wave per SIMD: the variant that prefetches its fragments (mfma_stage)
     if (a.ntiles <= device_cu_count() || rows2_lone)
-      return launch_ring<k_chain_fwd<NB, IN, OUT, false, false, true>>("chain_fwd", "single-round build", grid, threads, lds, lds_max, a, s);
+      return launch_dyn_lds<k_chain_fwd<NB, IN, OUT, false, false, true>>("chain_fwd", "single-round build", grid, threads, lds, lds_max, a, s);
   }
-  return launch_ring<k_chain_fwd<NB, IN, OUT>>("chain_fwd", nullptr, grid, threads, lds, lds_max, a, s);
+  return launch_dyn_lds<k_chain_fwd<NB, IN, OUT>>("chain_fwd", nullptr, grid, threads, lds, lds_max, a, s);
 }
 // Only the combinations the path uses are instantiated (each is a large unrolled kernel).
 template <int NB>
@@ -339,14 +326,14 @@ int launch_bwd_t(const ChainBwdArgs& a0, hipStream_t s) {
   // ---- the variant
   constexpr bool kEdgeMlp = GIN == G_EDGE_LN && FIRST == F_NONE, kNodeMlp = GIN == G_ROWS_LN && FIRST == F_HEADS2;
   if constexpr ((NB == 8 || NB == 16) && (kEdgeMlp || kNodeMlp)) {
-    if (a.bf16) return launch_ring<k_chain_bwd<NB, GIN, FIRST, true>>("chain_bwd", kEdgeMlp ? "bf16 build" : "bf16 node build", grid, threads, lds, lds_max, a, s);
+    if (a.bf16) return launch_dyn_lds<k_chain_bwd<NB, GIN, FIRST, true>>("chain_bwd", kEdgeMlp ? "bf16 build" : "bf16 node build", grid, threads, lds, lds_max, a, s);
   }
   BSMS_REQUIRE(!a.bf16, BSMS_E_UNSUPPORTED, "chain_bwd: bf16 precision is built for the edge and node MLPs at D = 128 / 256 only");
   if constexpr (NB >= 8) {   // see launch_fwd_t
     if (a.ntiles <= device_cu_count())
-      return launch_ring<k_chain_bwd<NB, GIN, FIRST, false, true>>("chain_bwd", "single-round build", grid, threads, lds, lds_max, a, s);
+      return launch_dyn_lds<k_chain_bwd<NB, GIN, FIRST, false, true>>("chain_bwd", "single-round build", grid, threads, lds, lds_max, a, s);
   }
-  return launch_ring<k_chain_bwd<NB, GIN, FIRST>>("chain_bwd", nullptr, grid, threads, lds, lds_max, a, s);
+  return launch_dyn_lds<k_chain_bwd<NB, GIN, FIRST>>("chain_bwd", nullptr, grid, threads, lds, lds_max, a, s);
 }
 template <int NB>
 int launch_bwd_n(int gin, int first, const ChainBwdArgs& a, hipStream_t s) {

@@ -78,6 +78,21 @@ struct DynLdsAttr {
     return hipError_t(st - 1);
   }
 };
+#ifdef __HIPCC__
+// One launch of a kernel that takes dynamic LDS beyond the default limit.  The first launch of a kernel on a device raises its
+// LDS limit to `lds_max` (the most any launch of it asks for; DynLdsAttr keeps one answer per kernel and device), so only
+// kernels that run get the attribute.  `what` names the launcher and `build` the variant (null: the plain kernel) in the error text.
+template <auto Kernel, class Args>
+int launch_dyn_lds(const char* what, const char* build, unsigned grid, unsigned threads, size_t lds, size_t lds_max, const Args& a, hipStream_t s) {
+  static DynLdsAttr attr_dev;
+  const hipError_t attr = attr_dev.ensure(reinterpret_cast<const void*>(Kernel), (int)lds_max);
+  if (build) BSMS_REQUIRE(attr == hipSuccess, BSMS_E_HIP, "%s: cannot reserve %zu bytes of LDS (%s)", what, lds_max, build);
+  BSMS_REQUIRE(attr == hipSuccess, BSMS_E_HIP, "%s: cannot reserve %zu bytes of LDS", what, lds_max);
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds, s, a);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}
+#endif
 inline int device_cu_count() {
   static int cus[kMaxDevices] = {};
   const int dev = current_device_index();

@@ -1,28 +1,36 @@
 // Weight-gradient kernels: dW = G^T A with the reduction over (up to millions of) edge / node rows.
 //
-// k_wgrad: split-K GEMM on the 16x16x32 matrix instructions with fp32 operands in HBM, split ONCE per element while they
-// are staged into LDS.  Two arithmetics (WgradJob::g_bound / a_bound, chain.h):
-//   H2   both operands come with a magnitude bound: fp16 x 2 pieces with one power-of-two scale per TENSOR (the
-//        reduction index is the row, so the chain kernels' per-row scales cannot be used) and three partial products
-//        h l + l h + h h per fragment pair -- the arithmetic of the chain kernels (chain.h);
-//   BF3  no bounds: the exact three-way bf16 split of rounds 1-2, six partial products (needs no range information).
-// A workgroup owns one 128x128 block of dW and a contiguous slab of rows, 32 rows per chunk:
-//   stage   1024 threads load the chunk of G and of A row-major (16-byte loads, full 512-byte row bursts, three
-//           chunks ahead in registers), split every value into its 16-bit pieces (H2: h, l; BF3: hi, mid, lo) and store
-//           one row-major plane per piece and matrix (row pitch 288 B so that 8 consecutive rows hit disjoint banks);
+// Split-K GEMMs on the 16x16x32 matrix instructions; the operands are read from HBM once per workgroup and staged into LDS.
+// Three arithmetics, one per kind of job (WgradJob, chain.h; launch_wgrad sorts the jobs of a call by kind):
+//   H2    fp32 operands that come with a magnitude bound (g_bound / a_bound): fp16 x 2 pieces with one power-of-two scale per
+//         TENSOR (the reduction index is the row, so the chain kernels' per-row scales cannot be used) and three partial
+//         products h l + l h + h h per fragment pair -- the arithmetic of the chain kernels (chain.h);
+//   BF3   fp32 operands without bounds: the exact three-way bf16 split, six partial products (needs no range information);
+//   bf16  operands stored as bf16 (bf16 precision of a GMP block): staged as they are, one product.
+// Kernels (a workgroup owns one block of dW and a contiguous slab of rows; 1024 threads):
+//   k_wgrad<TIMING, H2>   BF3 (H2 = false) and H2 on 128 x 128 blocks, 32 rows per chunk, three chunks ahead in registers;
+//                         TIMING (BF3 only) adds time stamps and exists in experiment builds only (profiles/wgrad_timeline.py);
+//   k_wgrad_wide          H2 on 128 x 256 blocks (D = 256), two chunks ahead;
+//   k_wgrad_bf64<WIDE>    bf16 jobs, 64 rows per chunk, on 128 x 128 (three chunks ahead) or 128 x 256 blocks (two).
+// (bf16 jobs on 32-row chunks were a mode of k_wgrad until the 64-row kernels replaced it in round 6; it is retired.)
+// The pieces they share -- slab_of, xcd_grouped, operand_scales, column_fragment and the two column-sum
+// epilogues -- exist once.  Per chunk:
+//   stage   the threads load the chunk of G and of A row-major (16-byte loads, full 512-byte row bursts), split every fp32 value
+//           into its 16-bit pieces (H2: h, l; BF3: hi, mid, lo) and store one row-major plane per piece and matrix (row pitch
+//           288 B, or 544 B for 256 columns, so that 8 consecutive rows hit disjoint banks);
 //   MFMA    the reduction index (rows) is the MFMA's K, i.e. an operand fragment is a COLUMN of 8 rows per lane:
 //           ds_read_b64_tr_b16 delivers exactly that from the row-major planes (a 16-lane group transposes a
 //           4-row x 16-column block), two reads per fragment, no bank conflicts.
-// The planes are double buffered (108 KB, one 16-wave workgroup per CU, one barrier per chunk): a wave stages chunk
-// c+1, then multiplies chunk c, and the four waves of a SIMD overlap each other's phases.  At this rate the kernel is HBM bound
-// (two fp32 streams, each read once).  Partial blocks go to a workspace and are summed in slab order by
+// The planes are double buffered (72-108 KB, one 16-wave workgroup per CU, one barrier per chunk): a wave stages chunk
+// c+1, then multiplies chunk c, and the four waves of a SIMD overlap each other's phases.  At this rate the kernels are HBM bound
+// (two streams, each read once).  Partial blocks go to a workspace and are summed in slab order by
 // k_wgrad_reduce (deterministic; no float atomics).  Several layers' gradients are batched into one launch so the
 // small coarse levels still fill the chip.  The bias gradient (column sums of G) is accumulated in fp32 by the
 // staging threads.
 // D = 256 (round 6): four 128 x 128 blocks per slab would read -- and split -- every row of G and A twice.  Launches of edge-level
-// size take k_wgrad_wide / k_wgrad_bf64_wide (a workgroup owns 128 x 256 of dW: A staged once), and in every tiling the workgroups
-// of one slab are placed on the same XCD (tile_of / wide_tile) so that the remaining duplicate reads are L2 hits: 1.04 x the
-// algorithmic bytes from HBM (profiles/r06_step_pmc_surface.txt).
+// size take the 128 x 256 blocks (A staged once), and in every tiling the workgroups of one slab are placed on the same XCD
+// (xcd_grouped) so that the remaining duplicate reads are L2 hits: 1.04 x the algorithmic bytes from HBM
+// (profiles/r06_step_pmc_surface.txt).
 #include "chain.h"
 #include <cstdlib>
 #include <type_traits>
@@ -33,14 +41,18 @@ namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 using s16x4 = __attribute__((ext_vector_type(4))) short;
 using s16x8 = __attribute__((ext_vector_type(8))) short;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-constexpr int TB = 128;    // dW block edge
-constexpr int RC = 32;     // rows per chunk (= K of one MFMA)
-constexpr int LROW = 144;  // bf16 per LDS row: 128 columns + 16 pad (288 B: 8 banks further per row)
+constexpr int TB = 128;      // dW block edge
+constexpr int RC = 32;       // rows per chunk of the fp32 kernels (= K of one MFMA)
+constexpr int RC2 = 64;      // rows per chunk of the bf16 kernels (two K steps)
+constexpr int LROW = 144;    // 16-bit values per LDS row of a 128-column plane: 128 + 16 pad (288 B: 8 banks further per row)
+constexpr int LROW_W = 272;  // ... of a 256-column plane (544 B = 136 dwords: again 8 banks further per row)
 constexpr int PLANE = RC * LROW;
+constexpr int WG_THREADS = 1024;  // 16 waves = 4 per SIMD, one workgroup per CU
 
 struct WgradTable {
   int njobs, D, nblk;
@@ -51,7 +63,7 @@ struct WgradTable {
   float* partials;   // [tiles][TB*TB]
   float* colsums;    // [tiles][TB]
   unsigned long long* timing;  // experiments only: per-workgroup s_memtime stamps (null in production)
-  int wide;          // k_wgrad_wide launch (D = 256): a tile is 128 rows x ALL 256 columns of dW, tile = split * nblk + bi
+  int wide;          // launch on 128 x 256 blocks (D = 256): a tile is 128 rows x ALL 256 columns of dW, tile = split * nblk + bi
 };
 
 __device__ __forceinline__ void split3(float x, unsigned& hi, unsigned& mid, unsigned& lo) {  // exact: x = hi + mid + lo
@@ -98,16 +110,45 @@ __device__ __forceinline__ int bound_exp(float b) {
   return E < 14 ? 14 : E;
 }
 
-// MFMA operand of one 16-column block from a row-major plane: lane (c = lane & 15, q = lane >> 4) receives column
-// `col0 + c`, rows 4q..4q+3 (slots 0-3) and 16+4q..16+4q+3 (slots 4-7).  ds_read_b64_tr_b16: within a 16-lane group
+// H2: one power-of-two scale per operand tensor from its magnitude bound = the largest entry of the operand's bound slot
+// (chain.h: kBoundWidth entries, two float4 per thread).  The products are un-scaled by 2^(Eg + Ea - 282).
+struct Scales { int Eg, Ea; float sG, sA; };
+__device__ __forceinline__ Scales operand_scales(const WgradJob& job, int tid, int lane, int wave) {
+  static_assert(kBoundWidth == 8 * WG_THREADS, "two float4 of each bound slot per thread");
+  __shared__ unsigned bred[2][WG_THREADS / 64];
+  const u32x4* gs = reinterpret_cast<const u32x4*>(job.g_bound);
+  const u32x4* as = reinterpret_cast<const u32x4*>(job.a_bound);
+  const u32x4 gv = gs[tid], gw = gs[tid + WG_THREADS], av = as[tid], aw = as[tid + WG_THREADS];
+  unsigned gm = max(max(max(gv[0], gv[1]), max(gv[2], gv[3])), max(max(gw[0], gw[1]), max(gw[2], gw[3])));   // non-negative floats order like integers
+  unsigned am = max(max(max(av[0], av[1]), max(av[2], av[3])), max(max(aw[0], aw[1]), max(aw[2], aw[3])));
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    gm = max(gm, (unsigned)__shfl_xor((int)gm, o, 64));
+    am = max(am, (unsigned)__shfl_xor((int)am, o, 64));
+  }
+  if (lane == 0) { bred[0][wave] = gm; bred[1][wave] = am; }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < WG_THREADS / 64; ++w) { gm = max(gm, bred[0][w]); am = max(am, bred[1][w]); }
+  Scales sc;
+  sc.Eg = bound_exp(__uint_as_float(gm) * job.g_mul);
+  sc.Ea = bound_exp(__uint_as_float(am) * job.a_mul);
+  sc.sG = __uint_as_float(unsigned(268 - sc.Eg) << 23);
+  sc.sA = __uint_as_float(unsigned(268 - sc.Ea) << 23);
+  return sc;
+}
+
+// MFMA operand of one 16-column block from a row-major plane of row pitch PITCH: lane (c = lane & 15, q = lane >> 4) receives
+// column `col0 + c`, rows 4q..4q+3 (slots 0-3) and 16+4q..16+4q+3 (slots 4-7).  ds_read_b64_tr_b16: within a 16-lane group
 // lane i' supplies the 8 bytes at its address and lane i receives element (i & 3) of suppliers 4k + (i >> 2), k = 0..3
 // (profiles/census/tr_test.hip), so supplier i' points at row (i' >> 2), columns 4 (i' & 3)...
+template <int PITCH = LROW>
 __device__ __forceinline__ bf16x8 column_fragment(const short* plane, int col0, int lane) {
   const int q = lane >> 4, ip = lane & 15;
-  const short* p = plane + (4 * q + (ip >> 2)) * LROW + col0 + 4 * (ip & 3);
+  const short* p = plane + (4 * q + (ip >> 2)) * PITCH + col0 + 4 * (ip & 3);
   using lds_s16x4 = __attribute__((address_space(3))) s16x4;
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 16 * LROW));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 16 * PITCH));
   const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(bf16x8, v);
 }
@@ -121,85 +162,106 @@ __device__ __forceinline__ f32x4 mma_h(const bf16x8& a, const bf16x8& b, f32x4 c
 
 __device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// Tile of a launch -> (slab, block row, block column).  At D = 256 (nblk = 2) the four workgroups of a slab read the same rows of G
-// and A (two of them each half): they are placed EIGHT workgroup indices apart -- same XCD (workgroups go round-robin over the 8
-// XCDs), same dispatch round -- so that three of the four reads of a chunk are served by that XCD's L2 (round 6; measured on the
-// 128 x 256 tiles of k_wgrad_wide: 1.04 x the algorithmic bytes from HBM instead of 2 x).  nblk = 1: the identity.  `tile` is where
-// k_wgrad_reduce looks for the block's partial sums (slab-major, as before).
-struct TileRef { int split, bi, bj; int64_t tile; };
-__device__ __forceinline__ TileRef tile_of(const WgradTable& tab, int j, int block) {
-  const int local = block - tab.first_tile[j];
-  TileRef t;
-  if (tab.nblk == 2) {
-    const int full = (tab.nsplit[j] >> 3) << 3;
-    int blk;
-    if (local < 4 * full) {
-      const int r = local & 31;
-      blk = r >> 3;
-      t.split = ((local >> 5) << 3) + (r & 7);
-    } else {
-      const int l2 = local - 4 * full;
-      t.split = full + (l2 >> 2);
-      blk = l2 & 3;
-    }
-    t.bi = blk >> 1;
-    t.bj = blk & 1;
+// XCD-grouped tile map: index of a workgroup within its job -> (slab, block of the slab) with PER blocks per slab.  The PER
+// workgroups of a slab read the same rows of G and A: they are placed EIGHT workgroup indices apart -- same XCD (workgroups go
+// round-robin over the 8 XCDs), same dispatch round -- so that all but one read of a chunk are served by that XCD's L2 (round 6;
+// measured on the 128 x 256 tiles: 1.04 x the algorithmic bytes from HBM instead of 2 x).  Whole groups of 8 slabs; the blocks of
+// the last slabs are neighbours.
+template <int PER>
+__device__ __forceinline__ void xcd_grouped(int local, int nsplit, int& split, int& blk) {
+  constexpr int SH = PER == 4 ? 2 : 1;
+  static_assert(PER == 1 << SH, "two or four blocks per slab");
+  const int full = (nsplit >> 3) << 3;
+  if (local < PER * full) {
+    const int r = local & (8 * PER - 1);
+    blk = r >> 3;
+    split = ((local >> (3 + SH)) << 3) + (r & 7);
   } else {
-    t.bj = local % tab.nblk;
-    t.bi = (local / tab.nblk) % tab.nblk;
-    t.split = local / (tab.nblk * tab.nblk);
+    const int l2 = local - PER * full;
+    split = full + (l2 >> SH);
+    blk = l2 & (PER - 1);
   }
-  t.tile = tab.first_tile[j] + (int64_t(t.split) * tab.nblk + t.bi) * tab.nblk + t.bj;
-  return t;
 }
 
-constexpr int WG_THREADS = 1024;  // 16 waves = 4 per SIMD, one workgroup per CU
+// What a workgroup works on: its job j (found from first_tile and copied to `job`), the slab [r0, r1) of the job's rows in
+// `nchunk` chunks of CHUNK rows, and the block (bi, bj) of dW.  WIDE: 128 x 256 blocks, two per slab (bj = 0); otherwise
+// nblk x nblk blocks of 128 x 128, XCD-grouped at nblk = 2 (D = 256: four per slab) and in launch order at nblk = 1.  `tile` is
+// where k_wgrad_reduce looks for the block's partial sums (slab-major).
+struct Slab { int j, split, bi, bj, nchunk; int64_t tile, r0, r1; };
+template <bool WIDE, int CHUNK>
+__device__ __forceinline__ Slab slab_of(const WgradTable& tab, int block, WgradJob& job) {
+  Slab s;
+  int j = 0;
+  while (j + 1 < tab.njobs && block >= tab.first_tile[j + 1]) ++j;
+  s.j = j;
+  job = tab.job[j];
+  const int local = block - tab.first_tile[j];
+  if constexpr (WIDE) {
+    xcd_grouped<2>(local, tab.nsplit[j], s.split, s.bi);
+    s.bj = 0;
+    s.tile = tab.first_tile[j] + s.split * 2 + s.bi;
+  } else {
+    if (tab.nblk == 2) {
+      int blk;
+      xcd_grouped<4>(local, tab.nsplit[j], s.split, blk);
+      s.bi = blk >> 1;
+      s.bj = blk & 1;
+    } else {
+      s.bj = local % tab.nblk;
+      s.bi = (local / tab.nblk) % tab.nblk;
+      s.split = local / (tab.nblk * tab.nblk);
+    }
+    s.tile = tab.first_tile[j] + (int64_t(s.split) * tab.nblk + s.bi) * tab.nblk + s.bj;
+  }
+  s.r0 = int64_t(s.split) * tab.rows_per_wg[j];
+  s.r1 = min(job.R, s.r0 + tab.rows_per_wg[j]);
+  s.nchunk = int((s.r1 - s.r0 + CHUNK - 1) / CHUNK);
+  return s;
+}
+
+// Column sums of G (the bias gradient) of a workgroup, combined in fixed order through LDS once the chunk loop is done.
+// Quads (fp32 kernels): thread tid holds columns 4 (tid % 32) .. of its rows tid / 32 + 32 k.
+__device__ __forceinline__ void colsum_quads(short* planes, const f32x4& csum, const WgradTable& tab, int64_t tile, int tid) {
+  f32x4* red = reinterpret_cast<f32x4*>(planes);
+  red[tid] = csum;
+  __syncthreads();
+  if (tid < 32) {
+    f32x4 v = red[tid];
+    for (int l = 1; l < 32; ++l) v += red[l * 32 + tid];
+    *reinterpret_cast<f32x4*>(tab.colsums + tile * TB + tid * 4) = v;
+  }
+}
+// Octets (bf16 kernels): thread tid holds columns scol = 8 (tid % 16) .. of its rows srow + 64 k, srow = tid / 16.
+__device__ __forceinline__ void colsum_octets(short* planes, const float (&csum)[8], const WgradTable& tab, int64_t tile, int tid, int srow, int scol) {
+  float* red = reinterpret_cast<float*>(planes);   // [64 row lanes][128 columns]
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 8; ++k) red[srow * TB + scol + k] = csum[k];
+  __syncthreads();
+  if (tid < TB) {
+    float v = red[tid];
+    for (int l = 1; l < 64; ++l) v += red[l * TB + tid];
+    tab.colsums[tile * TB + tid] = v;
+  }
+}
+
 constexpr int NPF = 3;            // chunks in flight in registers beyond the one being staged
 static_assert(NPF == 3, "the step schedule in k_wgrad is written out for three register sets");
 
-// TIMING: experiments (profiles/wgrad_timeline.py); the production instantiation carries no stamps
-// JB: every job of the launch is a bf16 job (WgradJob::bf16); H2: every job carries operand bounds (fp16 x 2 pieces);
-// compile-time switches so that every instantiation keeps its branch-free load schedule
-template <bool TIMING, bool JB = false, bool H2 = false>
+// TIMING: experiments (profiles/wgrad_timeline.py; BF3 only); the production instantiations carry no stamps
+// H2: every job carries operand bounds (fp16 x 2 pieces); a compile-time switch so that either instantiation keeps its
+// branch-free load schedule
+template <bool TIMING, bool H2>
 __global__ __launch_bounds__(WG_THREADS) void k_wgrad(WgradTable tab) {
   extern __shared__ __attribute__((aligned(16))) short planes[];  // [2 buffers][G|A][hi|mid|lo][32 rows][LROW]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int j = 0;
-  while (j + 1 < tab.njobs && int(blockIdx.x) >= tab.first_tile[j + 1]) ++j;
-  const WgradJob job = tab.job[j];
-  const TileRef tr = tile_of(tab, j, blockIdx.x);
-  const int bj = tr.bj, bi = tr.bi, split = tr.split;
+  WgradJob job;
+  const Slab sl = slab_of<false, RC>(tab, blockIdx.x, job);
   const int D = tab.D;
-  const int64_t r0 = int64_t(split) * tab.rows_per_wg[j];
-  const int64_t r1 = min(job.R, r0 + tab.rows_per_wg[j]);
-  const int nchunk = int((r1 - r0 + RC - 1) / RC);
-  const int n0 = bi * TB, k0 = bj * TB;
-  // H2: one power-of-two scale per operand tensor from its magnitude bound
-  int Eg = 139, Ea = 139;
-  float sG = 1.f, sA = 1.f;
-  if (H2) {   // bound = largest entry of the operand's bound slot (chain.h: kBoundWidth = 4 entries per thread)
-    static_assert(kBoundWidth == 8 * WG_THREADS, "two float4 of each bound slot per thread");
-    __shared__ unsigned bred[2][WG_THREADS / 64];
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-    const u32x4* gs = reinterpret_cast<const u32x4*>(job.g_bound);
-    const u32x4* as = reinterpret_cast<const u32x4*>(job.a_bound);
-    const u32x4 gv = gs[tid], gw = gs[tid + WG_THREADS], av = as[tid], aw = as[tid + WG_THREADS];
-    unsigned gm = max(max(max(gv[0], gv[1]), max(gv[2], gv[3])), max(max(gw[0], gw[1]), max(gw[2], gw[3])));   // non-negative floats order like integers
-    unsigned am = max(max(max(av[0], av[1]), max(av[2], av[3])), max(max(aw[0], aw[1]), max(aw[2], aw[3])));
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      gm = max(gm, (unsigned)__shfl_xor((int)gm, o, 64));
-      am = max(am, (unsigned)__shfl_xor((int)am, o, 64));
-    }
-    if (lane == 0) { bred[0][wave] = gm; bred[1][wave] = am; }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < WG_THREADS / 64; ++w) { gm = max(gm, bred[0][w]); am = max(am, bred[1][w]); }
-    Eg = bound_exp(__uint_as_float(gm) * job.g_mul);
-    Ea = bound_exp(__uint_as_float(am) * job.a_mul);
-    sG = __uint_as_float(unsigned(268 - Eg) << 23);
-    sA = __uint_as_float(unsigned(268 - Ea) << 23);
-  }
+  const int64_t r0 = sl.r0, r1 = sl.r1;
+  const int n0 = sl.bi * TB, k0 = sl.bj * TB;
+  Scales sc{139, 139, 1.f, 1.f};
+  if constexpr (H2) sc = operand_scales(job, tid, lane, wave);
 
   // staging: 1024 threads move one 32-row chunk of G and of A, one float4 of each per thread (row = tid / 32,
   // columns 4 (tid % 32) ..): full 512-byte row bursts, NPF chunks ahead in registers
@@ -207,13 +269,8 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad(WgradTable tab) {
   const bool vg = n0 + scol < D, va = k0 + scol < D;
   // loads are unconditional (a predicated load costs a branch and a vmcnt(0)): out-of-range rows / columns read a
   // valid address and are zeroed when they are staged
-  // bf16 job (bf16 precision of a GMP block: edge gradients and edge activations are stored as bf16): both matrices are
-  // read as 4 x bf16 = 8 bytes per thread, staged into the `hi` plane as they are and multiplied with ONE product
-  constexpr bool jb = JB;
   const float* gsrc = job.G + (vg ? n0 + scol : 0);
   const float* asrc = job.A + (va ? k0 + scol : 0);
-  const unsigned short* gsrc16 = reinterpret_cast<const unsigned short*>(job.G) + (vg ? n0 + scol : 0);
-  const unsigned short* asrc16 = reinterpret_cast<const unsigned short*>(job.A) + (va ? k0 + scol : 0);
   const int64_t rlast = r1 - 1;
   f32x4 sg[NPF], sa[NPF];
   bool live[NPF];
@@ -221,36 +278,22 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad(WgradTable tab) {
     const int64_t r = r0 + int64_t(chunk) * RC + srow;
     live[set] = r < r1;
     const int64_t rc = r < r1 ? r : rlast;
-    if (jb) {
-      const u32x2 g2 = *reinterpret_cast<const u32x2*>(gsrc16 + rc * job.ldg), a2 = *reinterpret_cast<const u32x2*>(asrc16 + rc * job.lda);
-      sg[set] = f32x4{__uint_as_float(g2[0]), __uint_as_float(g2[1]), 0.f, 0.f};
-      sa[set] = f32x4{__uint_as_float(a2[0]), __uint_as_float(a2[1]), 0.f, 0.f};
-    } else {
-      sg[set] = *reinterpret_cast<const f32x4*>(gsrc + rc * job.ldg);
-      sa[set] = *reinterpret_cast<const f32x4*>(asrc + rc * job.lda);
-    }
+    sg[set] = *reinterpret_cast<const f32x4*>(gsrc + rc * job.ldg);
+    sa[set] = *reinterpret_cast<const f32x4*>(asrc + rc * job.lda);
   };
-  const bool want_db = job.db && bj == 0;
+  const bool want_db = job.db && sl.bj == 0;
   f32x4 csum = {0.f, 0.f, 0.f, 0.f};  // column sums of G over this thread's rows
   auto stash = [&](int set, int buf) {
     short* dst = planes + buf * (6 * PLANE) + srow * LROW + scol;
     u32x2 h, m, l;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const f32x4 gq = (live[set] && vg) ? sg[set] : zero, aq = (live[set] && va) ? sa[set] : zero;
-    if (jb) {   // the raw bf16 quads go to the hi planes; mid / lo are not read for this job
-      const unsigned g0 = __float_as_uint(gq[0]), g1 = __float_as_uint(gq[1]);
-      *reinterpret_cast<u32x2*>(dst + 0 * PLANE) = u32x2{g0, g1};
-      *reinterpret_cast<u32x2*>(dst + 3 * PLANE) = u32x2{__float_as_uint(aq[0]), __float_as_uint(aq[1])};
-      if (want_db)
-        csum += f32x4{__uint_as_float(g0 << 16), __uint_as_float(g0 & 0xffff0000u), __uint_as_float(g1 << 16), __uint_as_float(g1 & 0xffff0000u)};
-      return;
-    }
     if (H2) {   // planes 0 / 1: G pieces h / l; planes 3 / 4: A pieces h / l
-      split_quad_h2(gq, sG, h, l);
+      split_quad_h2(gq, sc.sG, h, l);
       *reinterpret_cast<u32x2*>(dst + 0 * PLANE) = h;
       *reinterpret_cast<u32x2*>(dst + 1 * PLANE) = l;
       if (want_db) csum += gq;
-      split_quad_h2(aq, sA, h, l);
+      split_quad_h2(aq, sc.sA, h, l);
       *reinterpret_cast<u32x2*>(dst + 3 * PLANE) = h;
       *reinterpret_cast<u32x2*>(dst + 4 * PLANE) = l;
       return;
@@ -276,10 +319,10 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad(WgradTable tab) {
 
   // chunk c is staged from register set c % NPF into LDS buffer c & 1 one iteration before its MFMAs; one barrier
   // per chunk orders "buffer written" and "buffer free" at once
-  if (nchunk == 0) {   // cannot happen for a launched slab; keeps the unconditional loads in range
-    float* part0 = tab.partials + tr.tile * (TB * TB);
+  if (sl.nchunk == 0) {   // cannot happen for a launched slab; keeps the unconditional loads in range
+    float* part0 = tab.partials + sl.tile * (TB * TB);
     for (int o = tid; o < TB * TB; o += WG_THREADS) part0[o] = 0.f;
-    if (want_db && tid < TB) tab.colsums[tr.tile * TB + tid] = 0.f;
+    if (want_db && tid < TB) tab.colsums[sl.tile * TB + tid] = 0.f;
     return;
   }
 #pragma unroll
@@ -299,18 +342,6 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad(WgradTable tab) {
   auto multiply = [&](auto buf_tag) {
     constexpr int BUF = decltype(buf_tag)::value;
     const short* buf = planes + BUF * (6 * PLANE);
-    if (jb) {
-      bf16x8 g1[2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a) g1[a] = column_fragment(buf + 0 * PLANE, 32 * wr + 16 * a, lane);
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const bf16x8 a1 = column_fragment(buf + 3 * PLANE, 32 * wc + 16 * b, lane);
-        acc[0][b] = mma(g1[0], a1, acc[0][b]);
-        acc[1][b] = mma(g1[1], a1, acc[1][b]);
-      }
-      return;
-    }
     if (H2) {
       bf16x8 g_h[2], g_l[2];
 #pragma unroll
@@ -374,7 +405,7 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad(WgradTable tab) {
   // 6 = lcm(register sets, buffers): both are compile-time in every step.  The body has no conditional step (a
   // skipped step would make hipcc's vmcnt bookkeeping pessimistic: vmcnt(0) instead of leaving two chunks in
   // flight); chunks past the slab are zeros and add nothing -- the launcher makes slabs multiples of 6 chunks.
-  for (int c = 0; c < nchunk; c += 6) {
+  for (int c = 0; c < sl.nchunk; c += 6) {
     step(c, integral_constant<int, 1>{}, integral_constant<int, 0>{});
     step(c + 1, integral_constant<int, 2>{}, integral_constant<int, 1>{});
     step(c + 2, integral_constant<int, 0>{}, integral_constant<int, 0>{});
@@ -385,24 +416,15 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad(WgradTable tab) {
 
   // D[row = 4 q + r][col = c] of block (a, b) = dW[32 wr + 16 a + 4 q + r][32 wc + 16 b + c]
   const int q = lane >> 4, cc = lane & 15;
-  float* part = tab.partials + tr.tile * (TB * TB);
+  float* part = tab.partials + sl.tile * (TB * TB);
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int b = 0; b < 2; ++b)
 #pragma unroll
       for (int r = 0; r < 4; ++r)   // H2: un-scale by the exact power of two 2^-(k_G + k_A) (ldexp: exact over the whole range)
-        part[(32 * wr + 16 * a + 4 * q + r) * TB + 32 * wc + 16 * b + cc] = H2 ? ldexpf(acc[a][b][r], Eg + Ea - 282) : acc[a][b][r];
-  if (want_db) {  // combine the 32 row-threads of each column quad in fixed order through LDS
-    f32x4* red = reinterpret_cast<f32x4*>(planes);
-    red[tid] = csum;
-    __syncthreads();
-    if (tid < 32) {
-      f32x4 v = red[tid];
-      for (int l = 1; l < 32; ++l) v += red[l * 32 + tid];
-      *reinterpret_cast<f32x4*>(tab.colsums + tr.tile * TB + tid * 4) = v;
-    }
-  }
+        part[(32 * wr + 16 * a + 4 * q + r) * TB + 32 * wc + 16 * b + cc] = H2 ? ldexpf(acc[a][b][r], sc.Eg + sc.Ea - 282) : acc[a][b][r];
+  if (want_db) colsum_quads(planes, csum, tab, sl.tile, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -410,79 +432,21 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad(WgradTable tab) {
 // row of G and of A is read from HBM -- and split into its pieces -- TWICE (profiles/r06_surface_notes.txt: level 0 of the surface
 // step, 1.2 GB algorithmic, 730 us on 128 workgroups).  Here a workgroup owns 128 rows of dW (columns of G) x ALL 256 columns (of
 // A): A is read and split once, G twice; a wave owns 32 x 64 of dW = 2 x 4 MFMA blocks, i.e. 24 products per 12 fragment reads
-// where k_wgrad has 12 per 8.  Same staging, same step schedule, same products in the same order per accumulator (chunk after
-// chunk, rows ascending; h l, l h, h h) -- the results are bit-identical to k_wgrad<., false, true>.  LDS: 2 x [G h | G l | A h | A l]
-// = 2 x (2 x 9 KB + 2 x 17 KB) = 104 KB; the A planes have a 544-byte row pitch (136 dwords: again 8 banks further per row).
-constexpr int LROW_W = 272;
+// where k_wgrad has 12 per 8.  Same staging, same products in the same order per accumulator (chunk after chunk, rows ascending;
+// h l, l h, h h) -- the results are bit-identical to k_wgrad<., true>.  LDS: 2 x [G h | G l | A h | A l]
+// = 2 x (2 x 9 KB + 2 x 17 KB) = 104 KB.
 constexpr int PLANE_W = RC * LROW_W;
 constexpr int BUF_W = 2 * PLANE + 2 * PLANE_W;
-
-__device__ __forceinline__ bf16x8 column_fragment_w(const short* plane, int col0, int lane) {   // column_fragment on a 272-short pitch
-  const int q = lane >> 4, ip = lane & 15;
-  const short* p = plane + (4 * q + (ip >> 2)) * LROW_W + col0 + 4 * (ip & 3);
-  using lds_s16x4 = __attribute__((address_space(3))) s16x4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 16 * LROW_W));
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// Tile of a wide launch -> (slab, block of G columns).  The two workgroups of a slab read the same rows of A: they are placed EIGHT
-// workgroup indices apart, i.e. on the same XCD (workgroups go round-robin over the 8 XCDs) and in the same dispatch round, so that the
-// second read of an A chunk is served by that XCD's L2 instead of HBM.  Whole groups of 8 slabs; the last slabs pair up as neighbours.
-__device__ __forceinline__ void wide_tile(int local, int nsplit, int& split, int& bi) {
-  const int full = (nsplit >> 3) << 3;
-  if (local < 2 * full) {
-    const int r = local & 15;
-    bi = r >> 3;
-    split = ((local >> 4) << 3) + (r & 7);
-  } else {
-    const int l2 = local - 2 * full;
-    split = full + (l2 >> 1);
-    bi = l2 & 1;
-  }
-}
 
 __global__ __launch_bounds__(WG_THREADS) void k_wgrad_wide(WgradTable tab) {
   extern __shared__ __attribute__((aligned(16))) short planes[];  // [2 buffers][G h | G l | A h | A l]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int j = 0;
-  while (j + 1 < tab.njobs && int(blockIdx.x) >= tab.first_tile[j + 1]) ++j;
-  const WgradJob job = tab.job[j];
-  int split, bi;
-  wide_tile(blockIdx.x - tab.first_tile[j], tab.nsplit[j], split, bi);
-  const int64_t tile = tab.first_tile[j] + split * 2 + bi;   // where k_wgrad_reduce looks for this block's partial sums
-  const int64_t r0 = int64_t(split) * tab.rows_per_wg[j];
-  const int64_t r1 = min(job.R, r0 + tab.rows_per_wg[j]);
-  const int nchunk = int((r1 - r0 + RC - 1) / RC);
-  const int n0 = bi * TB;
+  WgradJob job;
+  const Slab sl = slab_of<true, RC>(tab, blockIdx.x, job);
+  const int64_t r0 = sl.r0, r1 = sl.r1;
+  const int n0 = sl.bi * TB;
   constexpr int TILE = TB * 2 * TB;   // floats per partial tile: [128][256]
-  // one power-of-two scale per operand tensor from its magnitude bound (k_wgrad, H2)
-  int Eg, Ea;
-  float sG, sA;
-  {
-    static_assert(kBoundWidth == 8 * WG_THREADS, "two float4 of each bound slot per thread");
-    __shared__ unsigned bred[2][WG_THREADS / 64];
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-    const u32x4* gs = reinterpret_cast<const u32x4*>(job.g_bound);
-    const u32x4* as = reinterpret_cast<const u32x4*>(job.a_bound);
-    const u32x4 gv = gs[tid], gw = gs[tid + WG_THREADS], av = as[tid], aw = as[tid + WG_THREADS];
-    unsigned gm = max(max(max(gv[0], gv[1]), max(gv[2], gv[3])), max(max(gw[0], gw[1]), max(gw[2], gw[3])));
-    unsigned am = max(max(max(av[0], av[1]), max(av[2], av[3])), max(max(aw[0], aw[1]), max(aw[2], aw[3])));
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      gm = max(gm, (unsigned)__shfl_xor((int)gm, o, 64));
-      am = max(am, (unsigned)__shfl_xor((int)am, o, 64));
-    }
-    if (lane == 0) { bred[0][wave] = gm; bred[1][wave] = am; }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < WG_THREADS / 64; ++w) { gm = max(gm, bred[0][w]); am = max(am, bred[1][w]); }
-    Eg = bound_exp(__uint_as_float(gm) * job.g_mul);
-    Ea = bound_exp(__uint_as_float(am) * job.a_mul);
-    sG = __uint_as_float(unsigned(268 - Eg) << 23);
-    sA = __uint_as_float(unsigned(268 - Ea) << 23);
-  }
+  const Scales sc = operand_scales(job, tid, lane, wave);
   // staging: one float4 of G (columns n0 + 4 (tid % 32) ..) and two of A (columns 4 (tid % 32) .. and 128 further) per thread and
   // chunk, row tid / 32: every load instruction covers full 512-byte bursts of 32 rows
   const int srow = tid >> 5, scol = (tid & 31) * 4;
@@ -507,14 +471,14 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad_wide(WgradTable tab) {
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     u32x2 h, l;
     const f32x4 gq = live[set] ? sg[set] : zero;
-    split_quad_h2(gq, sG, h, l);
+    split_quad_h2(gq, sc.sG, h, l);
     *reinterpret_cast<u32x2*>(dst + srow * LROW + scol) = h;
     *reinterpret_cast<u32x2*>(dst + PLANE + srow * LROW + scol) = l;
     if (want_db) csum += gq;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const f32x4 aq = live[set] ? sa[set][u] : zero;
-      split_quad_h2(aq, sA, h, l);
+      split_quad_h2(aq, sc.sA, h, l);
       *reinterpret_cast<u32x2*>(dst + 2 * PLANE + srow * LROW_W + scol + TB * u) = h;
       *reinterpret_cast<u32x2*>(dst + 2 * PLANE + PLANE_W + srow * LROW_W + scol + TB * u) = l;
     }
@@ -526,10 +490,10 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad_wide(WgradTable tab) {
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (nchunk == 0) {   // cannot happen for a launched slab; keeps the unconditional loads in range
-    float* part0 = tab.partials + tile * TILE;
+  if (sl.nchunk == 0) {   // cannot happen for a launched slab; keeps the unconditional loads in range
+    float* part0 = tab.partials + sl.tile * TILE;
     for (int o = tid; o < TILE; o += WG_THREADS) part0[o] = 0.f;
-    if (want_db && tid < TB) tab.colsums[tile * TB + tid] = 0.f;
+    if (want_db && tid < TB) tab.colsums[sl.tile * TB + tid] = 0.f;
     return;
   }
 #pragma unroll
@@ -548,8 +512,8 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad_wide(WgradTable tab) {
     }
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      const bf16x8 a_h = column_fragment_w(buf + 2 * PLANE, 64 * wc + 16 * b, lane);
-      const bf16x8 a_l = column_fragment_w(buf + 2 * PLANE + PLANE_W, 64 * wc + 16 * b, lane);
+      const bf16x8 a_h = column_fragment<LROW_W>(buf + 2 * PLANE, 64 * wc + 16 * b, lane);
+      const bf16x8 a_l = column_fragment<LROW_W>(buf + 2 * PLANE + PLANE_W, 64 * wc + 16 * b, lane);
       acc[0][b] = mma_h(g_h[0], a_l, acc[0][b]);
       acc[1][b] = mma_h(g_h[1], a_l, acc[1][b]);
       acc[0][b] = mma_h(g_l[0], a_h, acc[0][b]);
@@ -566,207 +530,81 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad_wide(WgradTable tab) {
     wg_barrier();
   };
   using std::integral_constant;
-  for (int c = 0; c < nchunk; c += 2) {   // chunk c: register set c % 2, buffer c & 1; no conditional step (slabs are multiples of 6 chunks)
+  for (int c = 0; c < sl.nchunk; c += 2) {   // chunk c: register set c % 2, buffer c & 1; no conditional step (slabs are multiples of 6 chunks)
     step(c, integral_constant<int, 1>{}, integral_constant<int, 0>{});
     step(c + 1, integral_constant<int, 0>{}, integral_constant<int, 1>{});
   }
   // D[row = 4 q + r][col = c] of block (a, b) = dW[n0 + 32 wr + 16 a + 4 q + r][64 wc + 16 b + c]
   const int q = lane >> 4, cc = lane & 15;
-  float* part = tab.partials + tile * TILE;
+  float* part = tab.partials + sl.tile * TILE;
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        part[(32 * wr + 16 * a + 4 * q + r) * (2 * TB) + 64 * wc + 16 * b + cc] = ldexpf(acc[a][b][r], Eg + Ea - 282);
-  if (want_db) {  // combine the 32 row-threads of each column quad in fixed order through LDS
-    f32x4* red = reinterpret_cast<f32x4*>(planes);
-    red[tid] = csum;
-    __syncthreads();
-    if (tid < 32) {
-      f32x4 v = red[tid];
-      for (int l = 1; l < 32; ++l) v += red[l * 32 + tid];
-      *reinterpret_cast<f32x4*>(tab.colsums + tile * TB + tid * 4) = v;
-    }
-  }
+        part[(32 * wr + 16 * a + 4 * q + r) * (2 * TB) + 64 * wc + 16 * b + cc] = ldexpf(acc[a][b][r], sc.Eg + sc.Ea - 282);
+  if (want_db) colsum_quads(planes, csum, tab, sl.tile, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // k_wgrad_bf64: the bf16 jobs (WgradJob::bf16: gradient and activation tensors stored as bf16, ONE product per fragment
-// pair) with 64-row chunks.  In k_wgrad<., true> a chunk is 32 rows = 8 KB per operand and a thread moves 8 bytes of each:
-// half the bytes in flight per CU of the fp32 form at the same step overhead, and the chunk step is paced by HBM latency
-// x bytes in flight -- 2.6-2.9 TB/s on 132 workgroups.  Here a thread moves 16 bytes of each operand per
-// chunk (rows tid / 16, columns 8 (tid % 16) ..), a chunk is two K steps of the MFMA: the same 32 KB per step and 96 KB
-// in flight as the fp32 kernel.  Same products in the same order per accumulator (chunk after chunk, rows ascending).
-constexpr int RC2 = 64;
+// pair) with 64-row chunks.  The chunk step is paced by HBM latency x bytes in flight: a thread moves 16 bytes
+// of G per chunk (rows tid / 16, columns 8 (tid % 16) ..) and a chunk is two K steps of the MFMA, so that a step moves as many
+// bytes as one of the fp32 kernels.  Same products in the same order per accumulator (chunk after chunk, rows ascending) in
+// both forms:
+//   WIDE = false  128 x 128 blocks: 16 bytes of A per thread, three register sets (32 KB per step, 96 KB in flight), a wave
+//                 owns 2 x 2 MFMA blocks; columns past D are masked;
+//   WIDE = true   (round 6) D = 256 on the 128 x 256 blocks of k_wgrad_wide -- A is read once instead of twice: 2 x 16 bytes
+//                 of A per thread on a 544-byte pitch, two register sets (two 48 KB chunks in flight; a third set spills at
+//                 128 VGPRs), a wave owns 2 x 4 MFMA blocks; no column is past D.
 constexpr int PLANE2 = RC2 * LROW;
+constexpr int bf64_buf(bool wide) { return PLANE2 + RC2 * (wide ? LROW_W : LROW); }   // 16-bit values per buffer [G | A]: 36 KB, or 18 KB + 34 KB
 
+template <bool WIDE>
 __global__ __launch_bounds__(WG_THREADS) void k_wgrad_bf64(WgradTable tab) {
-  extern __shared__ __attribute__((aligned(16))) short planes[];  // [2 buffers][G|A][64 rows][LROW]
+  constexpr int NA = WIDE ? 2 : 1;             // 128-column halves of A = 16-byte loads of A per thread and chunk
+  constexpr int AROW = WIDE ? LROW_W : LROW;   // row pitch of the A plane
+  constexpr int NSET = WIDE ? 2 : 3;           // register sets
+  constexpr int NBC = 2 * NA;                  // MFMA block columns of a wave
+  constexpr int BUF = bf64_buf(WIDE);
+  constexpr int TILE = TB * NA * TB;           // floats per partial tile
+  extern __shared__ __attribute__((aligned(16))) short planes[];  // [2 buffers][G 64 x LROW | A 64 x AROW]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int j = 0;
-  while (j + 1 < tab.njobs && int(blockIdx.x) >= tab.first_tile[j + 1]) ++j;
-  const WgradJob job = tab.job[j];
-  const TileRef tr = tile_of(tab, j, blockIdx.x);
-  const int bj = tr.bj, bi = tr.bi, split = tr.split;
-  const int D = tab.D;
-  const int64_t r0 = int64_t(split) * tab.rows_per_wg[j];
-  const int64_t r1 = min(job.R, r0 + tab.rows_per_wg[j]);
-  const int nchunk = int((r1 - r0 + RC2 - 1) / RC2);
-  const int n0 = bi * TB, k0 = bj * TB;
-  float* part = tab.partials + tr.tile * (TB * TB);
-  const bool want_db = job.db && bj == 0;
-  if (nchunk == 0) {   // cannot happen for a launched slab
-    for (int o = tid; o < TB * TB; o += WG_THREADS) part[o] = 0.f;
-    if (want_db && tid < TB) tab.colsums[tr.tile * TB + tid] = 0.f;
+  WgradJob job;
+  const Slab sl = slab_of<WIDE, RC2>(tab, blockIdx.x, job);
+  const int64_t r0 = sl.r0, r1 = sl.r1;
+  const int n0 = sl.bi * TB, k0 = sl.bj * TB;
+  float* part = tab.partials + sl.tile * TILE;
+  const bool want_db = job.db && sl.bj == 0;
+  if (sl.nchunk == 0) {   // cannot happen for a launched slab
+    for (int o = tid; o < TILE; o += WG_THREADS) part[o] = 0.f;
+    if (want_db && tid < TB) tab.colsums[sl.tile * TB + tid] = 0.f;
     return;
   }
-  using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
   const int srow = tid >> 4, scol = (tid & 15) * 8;
-  const bool vg = n0 + scol < D, va = k0 + scol < D;
+  const bool vg = WIDE || n0 + scol < tab.D, va = WIDE || k0 + scol < tab.D;
   const unsigned short* gsrc = reinterpret_cast<const unsigned short*>(job.G) + (vg ? n0 + scol : 0);
   const unsigned short* asrc = reinterpret_cast<const unsigned short*>(job.A) + (va ? k0 + scol : 0);
   const int64_t rlast = r1 - 1;
-  u32x4 sg[NPF], sa[NPF];
-  bool live[NPF];
+  u32x4 sg[NSET], sa[NSET][NA];
+  bool live[NSET];
   auto fetch = [&](int chunk, int set) {   // unconditional loads: chunks past the slab re-read its last row (never staged)
     const int64_t r = r0 + int64_t(chunk) * RC2 + srow;
     live[set] = r < r1;
     const int64_t rc = r < r1 ? r : rlast;
     sg[set] = *reinterpret_cast<const u32x4*>(gsrc + rc * job.ldg);
-    sa[set] = *reinterpret_cast<const u32x4*>(asrc + rc * job.lda);
+#pragma unroll
+    for (int u = 0; u < NA; ++u) sa[set][u] = *reinterpret_cast<const u32x4*>(asrc + rc * job.lda + TB * u);
   };
   float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // column sums of G over this thread's rows
   auto stash = [&](int set, int buf) {
-    short* dst = planes + buf * (2 * PLANE2) + srow * LROW + scol;
+    short* dst = planes + buf * BUF;
     const u32x4 zero = {0u, 0u, 0u, 0u};
-    const u32x4 gq = (live[set] && vg) ? sg[set] : zero, aq = (live[set] && va) ? sa[set] : zero;
-    *reinterpret_cast<u32x4*>(dst) = gq;
-    *reinterpret_cast<u32x4*>(dst + PLANE2) = aq;
-    if (want_db) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        csum[2 * k] += __uint_as_float(gq[k] << 16);
-        csum[2 * k + 1] += __uint_as_float(gq[k] & 0xffff0000u);
-      }
-    }
-  };
-  const int wr = wave >> 2, wc = wave & 3;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto multiply = [&](int buf) {
-    const short* base = planes + buf * (2 * PLANE2);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {   // two K steps of 32 rows
-      const short* pg = base + ks * 32 * LROW;
-      const short* pa = base + PLANE2 + ks * 32 * LROW;
-      bf16x8 g1[2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a) g1[a] = column_fragment(pg, 32 * wr + 16 * a, lane);
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const bf16x8 a1 = column_fragment(pa, 32 * wc + 16 * b, lane);
-        acc[0][b] = mma(g1[0], a1, acc[0][b]);
-        acc[1][b] = mma(g1[1], a1, acc[1][b]);
-      }
-    }
-  };
-#pragma unroll
-  for (int c = 0; c < NPF; ++c) fetch(c, c);
-  stash(0, 0);
-  fetch(NPF, 0);
-  wg_barrier();
-  auto step = [&](int c, auto set1_tag, auto buf_tag) {
-    constexpr int SET1 = decltype(set1_tag)::value, BUF = decltype(buf_tag)::value;
-    stash(SET1, BUF ^ 1);          // chunk c + 1 -> the other buffer (zeros past the slab)
-    fetch(c + 1 + NPF, SET1);
-    multiply(BUF);
-    wg_barrier();
-  };
-  using std::integral_constant;
-  for (int c = 0; c < nchunk; c += 6) {   // the schedule of k_wgrad: register sets and buffers compile-time in every step
-    step(c, integral_constant<int, 1>{}, integral_constant<int, 0>{});
-    step(c + 1, integral_constant<int, 2>{}, integral_constant<int, 1>{});
-    step(c + 2, integral_constant<int, 0>{}, integral_constant<int, 0>{});
-    step(c + 3, integral_constant<int, 1>{}, integral_constant<int, 1>{});
-    step(c + 4, integral_constant<int, 2>{}, integral_constant<int, 0>{});
-    step(c + 5, integral_constant<int, 0>{}, integral_constant<int, 1>{});
-  }
-  const int q = lane >> 4, cc = lane & 15;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) part[(32 * wr + 16 * a + 4 * q + r) * TB + 32 * wc + 16 * b + cc] = acc[a][b][r];
-  if (want_db) {  // the 64 row-threads of each column octet in fixed order through LDS
-    float* red = reinterpret_cast<float*>(planes);   // [64 row lanes][128 columns]
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) red[srow * TB + scol + k] = csum[k];
-    __syncthreads();
-    if (tid < TB) {
-      float v = red[tid];
-      for (int l = 1; l < 64; ++l) v += red[l * TB + tid];
-      tab.colsums[tr.tile * TB + tid] = v;
-    }
-  }
-}
-
-// k_wgrad_bf64_wide (round 6): k_wgrad_bf64 at D = 256 with the 128 x 256 tiles of k_wgrad_wide -- A (bf16 rows) is read once instead
-// of twice.  64-row chunks: a thread moves 16 bytes of G and 2 x 16 bytes of A; same products in the same order per accumulator.
-constexpr int PLANE2_W = RC2 * LROW_W;
-constexpr int BUF2_W = PLANE2 + PLANE2_W;   // [G | A]: 18 KB + 34 KB
-
-__global__ __launch_bounds__(WG_THREADS) void k_wgrad_bf64_wide(WgradTable tab) {
-  extern __shared__ __attribute__((aligned(16))) short planes[];  // [2 buffers][G 64 x LROW | A 64 x LROW_W]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int j = 0;
-  while (j + 1 < tab.njobs && int(blockIdx.x) >= tab.first_tile[j + 1]) ++j;
-  const WgradJob job = tab.job[j];
-  int split, bi;
-  wide_tile(blockIdx.x - tab.first_tile[j], tab.nsplit[j], split, bi);
-  const int64_t tile = tab.first_tile[j] + split * 2 + bi;
-  const int64_t r0 = int64_t(split) * tab.rows_per_wg[j];
-  const int64_t r1 = min(job.R, r0 + tab.rows_per_wg[j]);
-  const int nchunk = int((r1 - r0 + RC2 - 1) / RC2);
-  const int n0 = bi * TB;
-  constexpr int TILE = TB * 2 * TB;
-  float* part = tab.partials + tile * TILE;
-  const bool want_db = job.db != nullptr;
-  if (nchunk == 0) {   // cannot happen for a launched slab
-    for (int o = tid; o < TILE; o += WG_THREADS) part[o] = 0.f;
-    if (want_db && tid < TB) tab.colsums[tile * TB + tid] = 0.f;
-    return;
-  }
-  using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-  const int srow = tid >> 4, scol = (tid & 15) * 8;
-  const unsigned short* gsrc = reinterpret_cast<const unsigned short*>(job.G) + n0 + scol;
-  const unsigned short* asrc = reinterpret_cast<const unsigned short*>(job.A) + scol;
-  const int64_t rlast = r1 - 1;
-  constexpr int NPW = 2;   // register sets: two 48 KB chunks in flight (a third set spills at 128 VGPRs)
-  u32x4 sg[NPW], sa[NPW][2];
-  bool live[NPW];
-  auto fetch = [&](int chunk, int set) {   // unconditional loads: chunks past the slab re-read its last row (never staged)
-    const int64_t r = r0 + int64_t(chunk) * RC2 + srow;
-    live[set] = r < r1;
-    const int64_t rc = r < r1 ? r : rlast;
-    sg[set] = *reinterpret_cast<const u32x4*>(gsrc + rc * job.ldg);
-    sa[set][0] = *reinterpret_cast<const u32x4*>(asrc + rc * job.lda);
-    sa[set][1] = *reinterpret_cast<const u32x4*>(asrc + rc * job.lda + TB);
-  };
-  float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // column sums of G over this thread's rows
-  auto stash = [&](int set, int buf) {
-    short* dst = planes + buf * BUF2_W;
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-    const u32x4 gq = live[set] ? sg[set] : zero;
+    const u32x4 gq = (live[set] && vg) ? sg[set] : zero;
     *reinterpret_cast<u32x4*>(dst + srow * LROW + scol) = gq;
 #pragma unroll
-    for (int u = 0; u < 2; ++u) *reinterpret_cast<u32x4*>(dst + PLANE2 + srow * LROW_W + scol + TB * u) = live[set] ? sa[set][u] : zero;
+    for (int u = 0; u < NA; ++u) *reinterpret_cast<u32x4*>(dst + PLANE2 + srow * AROW + scol + TB * u) = (live[set] && va) ? sa[set][u] : zero;
     if (want_db) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -775,65 +613,68 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad_bf64_wide(WgradTable tab) 
       }
     }
   };
-  const int wr = wave >> 2, wc = wave & 3;   // dW rows [32 wr, +32) x cols [64 wc, +64)
-  f32x4 acc[2][4];
+  // 16 waves: wave owns dW rows [32 wr, +32) x cols [16 NBC wc, +16 NBC) = 2 x NBC MFMA blocks
+  const int wr = wave >> 2, wc = wave & 3;
+  f32x4 acc[2][NBC];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < NBC; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
   auto multiply = [&](int buf) {
-    const short* base = planes + buf * BUF2_W;
+    const short* base = planes + buf * BUF;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {   // two K steps of 32 rows
       const short* pg = base + ks * 32 * LROW;
-      const short* pa = base + PLANE2 + ks * 32 * LROW_W;
+      const short* pa = base + PLANE2 + ks * 32 * AROW;
       bf16x8 g1[2];
 #pragma unroll
       for (int a = 0; a < 2; ++a) g1[a] = column_fragment(pg, 32 * wr + 16 * a, lane);
 #pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const bf16x8 a1 = column_fragment_w(pa, 64 * wc + 16 * b, lane);
+      for (int b = 0; b < NBC; ++b) {
+        const bf16x8 a1 = column_fragment<AROW>(pa, 16 * NBC * wc + 16 * b, lane);
         acc[0][b] = mma(g1[0], a1, acc[0][b]);
         acc[1][b] = mma(g1[1], a1, acc[1][b]);
       }
     }
   };
 #pragma unroll
-  for (int c = 0; c < NPW; ++c) fetch(c, c);
+  for (int c = 0; c < NSET; ++c) fetch(c, c);
   stash(0, 0);
-  fetch(NPW, 0);
+  fetch(NSET, 0);
   wg_barrier();
   auto step = [&](int c, auto set1_tag, auto buf_tag) {
-    constexpr int SET1 = decltype(set1_tag)::value, BUF = decltype(buf_tag)::value;
-    stash(SET1, BUF ^ 1);          // chunk c + 1 -> the other buffer (zeros past the slab)
-    fetch(c + 1 + NPW, SET1);
-    multiply(BUF);
+    constexpr int SET1 = decltype(set1_tag)::value, BUF1 = decltype(buf_tag)::value;
+    stash(SET1, BUF1 ^ 1);          // chunk c + 1 -> the other buffer (zeros past the slab)
+    fetch(c + 1 + NSET, SET1);
+    multiply(BUF1);
     wg_barrier();
   };
   using std::integral_constant;
-  for (int c = 0; c < nchunk; c += 2) {   // chunk c: register set c % 2, buffer c & 1
-    step(c, integral_constant<int, 1>{}, integral_constant<int, 0>{});
-    step(c + 1, integral_constant<int, 0>{}, integral_constant<int, 1>{});
+  // the schedule of k_wgrad: chunk c uses register set c % NSET and buffer c & 1, both compile-time in every step, and no
+  // step is conditional -- lcm(NSET, 2) steps per round
+  if constexpr (NSET == 3) {
+    for (int c = 0; c < sl.nchunk; c += 6) {
+      step(c, integral_constant<int, 1>{}, integral_constant<int, 0>{});
+      step(c + 1, integral_constant<int, 2>{}, integral_constant<int, 1>{});
+      step(c + 2, integral_constant<int, 0>{}, integral_constant<int, 0>{});
+      step(c + 3, integral_constant<int, 1>{}, integral_constant<int, 1>{});
+      step(c + 4, integral_constant<int, 2>{}, integral_constant<int, 0>{});
+      step(c + 5, integral_constant<int, 0>{}, integral_constant<int, 1>{});
+    }
+  } else {
+    for (int c = 0; c < sl.nchunk; c += 2) {
+      step(c, integral_constant<int, 1>{}, integral_constant<int, 0>{});
+      step(c + 1, integral_constant<int, 0>{}, integral_constant<int, 1>{});
+    }
   }
   const int q = lane >> 4, cc = lane & 15;
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int b = 0; b < NBC; ++b)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) part[(32 * wr + 16 * a + 4 * q + r) * (2 * TB) + 64 * wc + 16 * b + cc] = acc[a][b][r];
-  if (want_db) {  // the 64 row-threads of each column octet in fixed order through LDS
-    float* red = reinterpret_cast<float*>(planes);   // [64 row lanes][128 columns]
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) red[srow * TB + scol + k] = csum[k];
-    __syncthreads();
-    if (tid < TB) {
-      float v = red[tid];
-      for (int l = 1; l < 64; ++l) v += red[l * TB + tid];
-      tab.colsums[tile * TB + tid] = v;
-    }
-  }
+      for (int r = 0; r < 4; ++r) part[(32 * wr + 16 * a + 4 * q + r) * (NA * TB) + 16 * NBC * wc + 16 * b + cc] = acc[a][b][r];
+  if (want_db) colsum_octets(planes, csum, tab, sl.tile, tid, srow, scol);
 }
 
 // dW[n][col0+k] = sum over slabs of the partial blocks; db likewise.  A block owns 64 float4 outputs; its 4
@@ -1094,9 +935,8 @@ static int launch_wgrad_same(int D, const WgradJob* jobs, int njobs, void* work,
   constexpr bool wide_on = true;
 #endif
   static const int64_t wide_min_rows = knob_rows("BSMS_WGRAD_WIDE_MIN", 262144);
-  // D = 256: 128 x 256 tiles, A read once (k_wgrad_wide) -- for launches of edge-level size; short launches keep the 128 x 128 blocks
-  const bool bf64 = bf && [] { const char* e = getenv("BSMS_WGRAD_BF64"); return !e || atoi(e) != 0; }();
-  const bool wide = wide_on && (bf ? bf64 : h2) && D == 2 * TB && !g_wgrad_timing && total_rows >= wide_min_rows;
+  // D = 256: 128 x 256 tiles, A read once -- for launches of edge-level size; short launches keep the 128 x 128 blocks
+  const bool wide = wide_on && (bf || h2) && D == 2 * TB && !g_wgrad_timing && total_rows >= wide_min_rows;
   tab.wide = wide ? 1 : 0;
   const int blocks = wide ? tab.nblk : tab.nblk * tab.nblk;
   const int tile_units = wide ? 2 : 1;   // partial tiles of 128 x 128 floats a workgroup writes
@@ -1133,43 +973,24 @@ static int launch_wgrad_same(int D, const WgradJob* jobs, int njobs, void* work,
   tab.partials = reinterpret_cast<float*>(work);
   tab.colsums = tab.partials + size_t(kMaxTiles) * TB * TB;
   tab.timing = g_wgrad_timing;
-  const size_t lds = size_t(2) * 6 * PLANE * sizeof(short);   // 108 KB: 2 x [G|A][3 planes][32 rows][288 B]
-  static DynLdsAttr attr_dev;
-  const hipError_t attr = attr_dev.ensure(reinterpret_cast<const void*>(&k_wgrad<false>), (int)lds);
-  static DynLdsAttr attr_t_dev;
-  const hipError_t attr_t = attr_t_dev.ensure(reinterpret_cast<const void*>(&k_wgrad<true>), (int)lds);
-  BSMS_REQUIRE(attr == hipSuccess && attr_t == hipSuccess, BSMS_E_HIP, "wgrad: cannot reserve %zu bytes of LDS", lds);
-  if (wide && bf) {
-    const size_t lds_bw = size_t(2) * BUF2_W * sizeof(short);   // 104 KB
-    static DynLdsAttr attr_bw_dev;
-    const hipError_t attr_bw = attr_bw_dev.ensure(reinterpret_cast<const void*>(&k_wgrad_bf64_wide), (int)lds_bw);
-    BSMS_REQUIRE(attr_bw == hipSuccess, BSMS_E_HIP, "wgrad: cannot reserve %zu bytes of LDS (bf16 build, 128 x 256 tiles)", lds_bw);
-    hipLaunchKernelGGL(k_wgrad_bf64_wide, dim3(first), dim3(WG_THREADS), lds_bw, s, tab);
-  } else if (wide) {
-    const size_t lds_w = size_t(2) * BUF_W * sizeof(short);   // 104 KB
-    static DynLdsAttr attr_w_dev;
-    const hipError_t attr_w = attr_w_dev.ensure(reinterpret_cast<const void*>(&k_wgrad_wide), (int)lds_w);
-    BSMS_REQUIRE(attr_w == hipSuccess, BSMS_E_HIP, "wgrad: cannot reserve %zu bytes of LDS (128 x 256 tiles)", lds_w);
-    hipLaunchKernelGGL(k_wgrad_wide, dim3(first), dim3(WG_THREADS), lds_w, s, tab);
-  } else if (h2) {
-    static DynLdsAttr attr_h_dev;
-  const hipError_t attr_h = attr_h_dev.ensure(reinterpret_cast<const void*>(&k_wgrad<false, false, true>), (int)lds);
-    BSMS_REQUIRE(attr_h == hipSuccess, BSMS_E_HIP, "wgrad: cannot reserve %zu bytes of LDS (fp16 x 2 build)", lds);
-    hipLaunchKernelGGL((k_wgrad<false, false, true>), dim3(first), dim3(WG_THREADS), lds, s, tab);
-  } else if (bf64) {
-    const size_t lds_b = size_t(2) * 2 * PLANE2 * sizeof(short);   // 72 KB: 2 x [G|A][64 rows][288 B]
-    static DynLdsAttr attr_b64_dev;
-  const hipError_t attr_b64 = attr_b64_dev.ensure(reinterpret_cast<const void*>(&k_wgrad_bf64), (int)lds_b);
-    BSMS_REQUIRE(attr_b64 == hipSuccess, BSMS_E_HIP, "wgrad: cannot reserve %zu bytes of LDS (bf16 build, 64-row chunks)", lds_b);
-    hipLaunchKernelGGL(k_wgrad_bf64, dim3(first), dim3(WG_THREADS), lds_b, s, tab);
-  } else if (bf) {
-    static DynLdsAttr attr_b_dev;
-  const hipError_t attr_b = attr_b_dev.ensure(reinterpret_cast<const void*>(&k_wgrad<false, true>), (int)lds);
-    BSMS_REQUIRE(attr_b == hipSuccess, BSMS_E_HIP, "wgrad: cannot reserve %zu bytes of LDS (bf16 build)", lds);
-    hipLaunchKernelGGL((k_wgrad<false, true>), dim3(first), dim3(WG_THREADS), lds, s, tab);
-  } else if (tab.timing) hipLaunchKernelGGL(k_wgrad<true>, dim3(first), dim3(WG_THREADS), lds, s, tab);
-  else hipLaunchKernelGGL(k_wgrad<false>, dim3(first), dim3(WG_THREADS), lds, s, tab);
-  BSMS_LAUNCH_CHECK();
+  // Which kernel, first match: bf16 jobs on 128 x 256 tiles; fp16 x 2 jobs on 128 x 256 tiles; fp16 x 2 jobs; bf16 jobs;
+  // (experiment builds) range-free jobs with time stamps; range-free jobs.  `build` names the variant in the error text.
+  struct Variant {
+    int (*launch)(const char*, const char*, unsigned, unsigned, size_t, size_t, const WgradTable&, hipStream_t);
+    size_t lds;
+    const char* build;
+  };
+  constexpr size_t lds = size_t(2) * 6 * PLANE * sizeof(short);   // 108 KB: 2 x [G|A][3 planes][32 rows][288 B]
+  Variant v{&launch_dyn_lds<k_wgrad<false, false>, WgradTable>, lds, nullptr};
+  if (wide && bf) v = {&launch_dyn_lds<k_wgrad_bf64<true>, WgradTable>, size_t(2) * bf64_buf(true) * sizeof(short), "bf16 build, 128 x 256 tiles"};   // 104 KB
+  else if (wide) v = {&launch_dyn_lds<k_wgrad_wide, WgradTable>, size_t(2) * BUF_W * sizeof(short), "128 x 256 tiles"};   // 104 KB
+  else if (h2) v = {&launch_dyn_lds<k_wgrad<false, true>, WgradTable>, lds, "fp16 x 2 build"};
+  else if (bf) v = {&launch_dyn_lds<k_wgrad_bf64<false>, WgradTable>, size_t(2) * bf64_buf(false) * sizeof(short), "bf16 build, 64-row chunks"};   // 72 KB: 2 x [G|A][64 rows][288 B]
+#ifdef BSMS_EXPERIMENTS
+  else if (tab.timing) v.launch = &launch_dyn_lds<k_wgrad<true, false>, WgradTable>;
+#endif
+  const int rc = v.launch("wgrad", v.build, (unsigned)first, WG_THREADS, v.lds, v.lds, tab, s);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)ceil_div((D * D + D) / 4, 64), njobs), dim3(256), 0, s, tab);
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
@@ -1222,6 +1043,7 @@ int launch_small_wgrad(const SmallWgradArgs& a, void* work, hipStream_t s) {
                SW_MAXS);
   BSMS_REQUIRE(a.D >= 32 && a.D <= 256 && a.D % 4 == 0, BSMS_E_UNSUPPORTED, "small_wgrad: D=%d", a.D);
   BSMS_REQUIRE(a.S != nullptr || a.p + 1 == a.S_cols, BSMS_E_INVALID_ARG, "small_wgrad: fiber mode needs S_cols = p+1");
+  BSMS_REQUIRE(!a.colsum_S || a.S, BSMS_E_INVALID_ARG, "small_wgrad: colsum_S needs an explicit narrow matrix");
   float* part = reinterpret_cast<float*>(work);
   const int nrl = 256 / (a.D / 4);
   int64_t rows_per = std::max<int64_t>(4 * nrl, ceil_div(a.R, SW_WGS));
@@ -1236,10 +1058,7 @@ int launch_small_wgrad(const SmallWgradArgs& a, void* work, hipStream_t s) {
   }
 #undef BSMS_SW
   BSMS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_small_reduce, dim3((unsigned)ceil_div((SW_MAXS + 2) * a.D, 8)), dim3(256), 0, s, a, (const float*)part, nwg);
-  BSMS_LAUNCH_CHECK();
-  BSMS_REQUIRE(!a.colsum_S || a.S, BSMS_E_INVALID_ARG, "small_wgrad: colsum_S needs an explicit narrow matrix");
-  return BSMS_OK;
+  return launch_small_reduce(a, part, nwg, s);
 }
 
 }  // namespace bsms
