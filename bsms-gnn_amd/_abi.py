@@ -81,10 +81,13 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsms_sim_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    "bsms_sim_unroll_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsms_error_sums_work_bytes": (c_size_t, [c_i64, c_i64]),
     "bsms_error_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "bsms_batch_assemble": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, C.c_double, c_void_p, c_i64, C.c_uint64, C.c_uint64,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsms_batch_targets": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p]),
     "bsms_hierarchy_create": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, PP]),
     "bsms_hierarchy_create_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, PP]),
     "bsms_hierarchy_destroy": (c_int, [c_void_p]),
@@ -95,6 +98,7 @@ SIGNATURES = {
     "bsms_adamw_work_bytes": (c_size_t, []),
     "bsms_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_float, c_i64, C.c_float, c_void_p, c_void_p, c_void_p]),
+    "bsms_grad_accumulate": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p]),
 }
 
 _ERRORS = {-1: "BSMS_E_INVALID_ARG", -2: "BSMS_E_SHAPE", -3: "BSMS_E_UNSUPPORTED", -4: "BSMS_E_HIP"}

@@ -180,3 +180,73 @@ extern "C" int bsms_batch_assemble(const bsms_batch_sample* samples, int64_t n_s
   }
   return BSMS_OK;
 }
+
+// ---- later targets of an unrolled (K-step) loss: frames t+2 .. t+K of every pick.  The resident state is [T, N, C], so frame
+// t+1+(j+1) lies (j+1) * n * C floats behind `state_tar`.  A sample is copied as a flat run of n * C floats (coalesced on both
+// sides); blockIdx.y is the later frame j.  No noise: only node_in / node_tar carry it.
+namespace {
+
+struct TargetsArgs {
+  const float* tar[kBatchSamples];
+  int64_t elem0[kBatchSamples];   // batch-global first element (row0 * C) of the sample
+  int64_t elems[kBatchSamples];   // n * C
+  int32_t blk0[kBatchSamples];    // first block of the sample in this launch (a block never straddles two samples)
+  int32_t n_samples;
+  int64_t frame;                  // elements of one later frame of the batch: R * C
+};
+
+__global__ __launch_bounds__(kRowsPerBlock) void k_batch_targets(const TargetsArgs a, float* __restrict__ later) {
+  int lo = 0, hi = a.n_samples - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.blk0[mid] <= int(blockIdx.x)) lo = mid; else hi = mid - 1;
+  }
+  const int64_t i = int64_t(int(blockIdx.x) - a.blk0[lo]) * kRowsPerBlock + int(threadIdx.x);   // element inside the sample
+  if (i >= a.elems[lo]) return;
+  const int64_t j = blockIdx.y;
+  later[j * a.frame + a.elem0[lo] + i] = a.tar[lo][(j + 1) * a.elems[lo] + i];
+}
+
+}  // namespace
+
+extern "C" int bsms_batch_targets(const bsms_batch_sample* samples, int64_t n_samples, int64_t C, int64_t n_later, float* later,
+                                  bsms_stream_t stream) {
+  BSMS_REQUIRE(C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "batch_targets: C=%lld (C in 1..8)", (long long)C);
+  BSMS_REQUIRE(n_samples >= 0 && n_later >= 0, BSMS_E_INVALID_ARG, "batch_targets: n_samples=%lld n_later=%lld", (long long)n_samples,
+               (long long)n_later);
+  BSMS_REQUIRE(n_later <= 65535, BSMS_E_UNSUPPORTED, "batch_targets: n_later=%lld (at most 65535 later frames)", (long long)n_later);
+  if (n_samples == 0 || n_later == 0) return BSMS_OK;
+  BSMS_REQUIRE(samples && later, BSMS_E_INVALID_ARG, "batch_targets: null argument");
+  constexpr int64_t kMaxRows = (int64_t(1) << 31) / kBatchSamples - kRowsPerBlock;   // as bsms_batch_assemble
+  int64_t rows = 0;
+  for (int64_t i = 0; i < n_samples; ++i) {
+    BSMS_REQUIRE(samples[i].n >= 0 && samples[i].n <= kMaxRows, BSMS_E_UNSUPPORTED, "batch_targets: sample %lld has %lld rows (at most %lld)",
+                 (long long)i, (long long)samples[i].n, (long long)kMaxRows);
+    BSMS_REQUIRE(samples[i].n == 0 || samples[i].state_tar, BSMS_E_INVALID_ARG, "batch_targets: sample %lld has a null state_tar", (long long)i);
+    rows += samples[i].n;
+  }
+  TargetsArgs a;
+  a.frame = rows * C;
+  hipStream_t s = as_stream(stream);
+  int64_t elem0 = 0;
+  for (int64_t first = 0; first < n_samples; first += kBatchSamples) {
+    const int cnt = int(std::min<int64_t>(kBatchSamples, n_samples - first));
+    int64_t blocks = 0;     // at most 64 * ceil(8 * kMaxRows / 256) < 2^27
+    for (int k = 0; k < kBatchSamples; ++k) {
+      const bsms_batch_sample& src = samples[first + std::min(k, cnt - 1)];
+      a.tar[k] = src.state_tar;
+      a.elem0[k] = elem0;
+      a.blk0[k] = int32_t(blocks);
+      a.elems[k] = k < cnt ? src.n * C : 0;
+      if (k < cnt) {
+        elem0 += src.n * C;
+        blocks += ceil_div(src.n * C, kRowsPerBlock);
+      }
+    }
+    a.n_samples = cnt;
+    if (blocks == 0) continue;
+    hipLaunchKernelGGL(k_batch_targets, dim3((unsigned)blocks, (unsigned)n_later), dim3(kRowsPerBlock), 0, s, a, later);
+    BSMS_LAUNCH_CHECK();
+  }
+  return BSMS_OK;
+}

@@ -87,3 +87,39 @@ extern "C" int bsms_adamw_step(float* params, const float* grads, float* exp_avg
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
+
+// ---- gradient accumulation over the steps of an unrolled loss (step.py).  The weight-gradient kernels OVERWRITE their slots, so
+// step k's backward writes a scratch flat buffer with the GradBuckets layout and this folds it into the real one:
+// acc[i] = first ? g[i] : acc[i] + g[i].  One read-modify-write stream over the flat buffer (7.7 MB at airfoil size), 16-byte
+// accesses; every element is touched by exactly one thread, so the sum is deterministic.
+namespace {
+__global__ __launch_bounds__(256) void k_grad_accumulate(float* __restrict__ acc, const float* __restrict__ g, int64_t n4,
+                                                         int64_t n, int first) {
+  const int64_t stride = int64_t(gridDim.x) * 256;
+  const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  float4* a4 = reinterpret_cast<float4*>(acc);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  for (int64_t i = t; i < n4; i += stride) {
+    float4 v = g4[i];
+    if (!first) {
+      const float4 o = a4[i];
+      v.x = o.x + v.x; v.y = o.y + v.y; v.z = o.z + v.z; v.w = o.w + v.w;
+    }
+    a4[i] = v;
+  }
+  for (int64_t i = 4 * n4 + t; i < n; i += stride) acc[i] = first ? g[i] : acc[i] + g[i];   // tail (and unaligned buffers: n4 = 0)
+}
+}  // namespace
+
+extern "C" int bsms_grad_accumulate(float* acc, const float* g, int64_t n, int first, bsms_stream_t stream) {
+  BSMS_REQUIRE(n >= 0, BSMS_E_SHAPE, "grad_accumulate: n=%lld", (long long)n);
+  if (n == 0) return BSMS_OK;
+  BSMS_REQUIRE(acc && g, BSMS_E_INVALID_ARG, "grad_accumulate: null argument");
+  BSMS_REQUIRE(acc != g, BSMS_E_INVALID_ARG, "grad_accumulate: acc and g are the same buffer");
+  const bool aligned = ((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+  const int64_t n4 = aligned ? n / 4 : 0;
+  const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(std::max<int64_t>(n4, n - 4 * n4), 256), 2048);
+  hipLaunchKernelGGL(k_grad_accumulate, dim3(grid), dim3(256), 0, as_stream(stream), acc, g, n4, n, first ? 1 : 0);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}

@@ -176,3 +176,61 @@ extern "C" int bsms_sim_loss_bwd(const float* pred, const float* target, const f
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
+
+namespace {
+
+// One step k of the unrolled (K-step) loss, backward: k_sim_loss_bwd with the step weight and the gradient carried back from step
+// k+1 through in_{k+1} = where(mask == 0, in_0, cat[pred_k, ...]) (utils/rollout_utils.py:57-62).  Step k+1's state columns
+// reach its loss twice: through the identity term of pred = state + delta * mask (g_pred_next) and through the encoder's
+// input, behind the fp64 input normalisation (g_norm_in_next / std_in).  Dirichlet rows took in_0, not pred_k: no carry.
+__global__ __launch_bounds__(256) void k_sim_unroll_bwd(const float* pred, const float* target, const float* mask, int64_t R,
+                                                        int C, const double* mean, const double* meansq, const double* eps,
+                                                        const double* in_mean, const double* in_meansq, const double* in_eps,
+                                                        const float* sums, float w, const float* g_pred_next,
+                                                        const float* g_norm_in_next, float* loss_out, float* g_pred,
+                                                        float* grad_norm_pred) {
+  const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  const float S = sums[0], M = sums[1];
+  const float loss = sqrtf(S / M / float(C));
+  if (r == 0 && loss_out) *loss_out = loss;
+  if (r >= R) return;
+  const double e = *eps;
+  const float m = mask[r];
+  const float coef = 1.f / (loss * M * float(C));
+  const bool carried = g_pred_next != nullptr && m != 0.f;
+  const double ie = g_pred_next ? *in_eps : 0.0;
+  for (int c = 0; c < C; ++c) {
+    float gp = (pred[r * C + c] - target[r * C + c]) * m * coef;          // as k_sim_loss_bwd forms it
+    gp = w * gp;
+    if (carried) {
+      const float through_norm = float(double(g_norm_in_next[r * (C + 1) + c]) / std_eps(in_mean[c], in_meansq[c], ie));
+      const float g_state = g_pred_next[r * C + c] + through_norm;
+      gp = gp + g_state;
+    }
+    if (g_pred) g_pred[r * C + c] = gp;
+    const float gd = gp * m;
+    grad_norm_pred[r * C + c] = float(double(gd) * std_eps(mean[c], meansq[c], e));
+  }
+}
+
+}  // namespace
+
+extern "C" int bsms_sim_unroll_bwd(const float* pred, const float* target, const float* mask, int64_t R, int64_t C,
+                                   const double* mean, const double* meansq, const double* std_eps_dev, const double* in_mean,
+                                   const double* in_meansq, const double* in_std_eps_dev, const float* sums, float w,
+                                   const float* g_pred_next, const float* g_norm_in_next, float* loss_out, float* g_pred,
+                                   float* grad_norm_pred, bsms_stream_t stream) {
+  BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "sim_unroll_bwd: R=%lld C=%lld", (long long)R, (long long)C);
+  BSMS_REQUIRE(pred && target && mask && mean && meansq && std_eps_dev && sums && grad_norm_pred, BSMS_E_INVALID_ARG,
+               "sim_unroll_bwd: null argument");
+  BSMS_REQUIRE((g_pred_next == nullptr) == (g_norm_in_next == nullptr), BSMS_E_INVALID_ARG,
+               "sim_unroll_bwd: the carried pair (g_pred_next, g_norm_in_next) is given together or not at all");
+  BSMS_REQUIRE(!g_pred_next || (in_mean && in_meansq && in_std_eps_dev), BSMS_E_INVALID_ARG,
+               "sim_unroll_bwd: a carried gradient needs the input normaliser's statistics");
+  BSMS_REQUIRE(!g_pred || (g_pred != g_pred_next), BSMS_E_INVALID_ARG, "sim_unroll_bwd: g_pred aliases g_pred_next");
+  hipLaunchKernelGGL(k_sim_unroll_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask, R,
+                     (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, w, g_pred_next, g_norm_in_next,
+                     loss_out, g_pred, grad_norm_pred);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}

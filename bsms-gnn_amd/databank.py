@@ -48,20 +48,30 @@ def epoch_picks(rng, lengths, order="trajectory"):
     return [pairs[k] for k in rng.permutation(len(pairs))]
 
 
+def pick_lengths(frames, horizon=1):
+    """Frames of each trajectory that may start a pick: frame t needs its targets t+1 .. t+horizon, so T - horizon of T."""
+    return [int(T) - int(horizon) for T in frames]
+
+
 class _Traj:
     __slots__ = ("state", "pos", "type", "pos_static", "type_static", "T", "N", "entry")
 
 
 class TrajectoryBank:
     """`cfg`: what datapipe.TrajectoryDataset takes (field_names, output_field_names, consist_mesh, unet_depth, mesh_type,
-    noise_level, noise_gamma).  `process`: the model's BSGMP, needed for variable meshes only (it builds the per-mesh plans)."""
+    noise_level, noise_gamma).  `process`: the model's BSGMP, needed for variable meshes only (it builds the per-mesh plans).
+    `horizon` = K > 1 serves an unrolled loss over K steps: a pick (trajectory, t) then needs the frames t+1 .. t+K, so the epoch
+    order stops K frames before the end, and `batch` also returns the later targets (frames t+2 .. t+K, without noise)."""
 
-    def __init__(self, cfg, dataset="airfoil", device=None, seed=0, process=None, max_bytes=None, order="trajectory", cache_dir=None):
+    def __init__(self, cfg, dataset="airfoil", device=None, seed=0, process=None, max_bytes=None, order="trajectory", cache_dir=None,
+                 horizon=1):
         if dataset not in VALID_TYPES:
             raise ValueError(f"dataset must be one of {sorted(VALID_TYPES)}, got {dataset!r}")
         if order not in ("trajectory", "global"):
             raise ValueError(f"order must be 'trajectory' or 'global', got {order!r}")
-        self.cfg, self.dataset, self.order, self.cache_dir = cfg, dataset, order, cache_dir
+        if int(horizon) < 1:
+            raise ValueError(f"horizon must be >= 1, got {horizon}")
+        self.cfg, self.dataset, self.order, self.cache_dir, self.horizon = cfg, dataset, order, cache_dir, int(horizon)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise _abi.BsmsError("TrajectoryBank needs a GPU device: trajectories are resident in HBM")
@@ -86,8 +96,8 @@ class TrajectoryBank:
 
     @property
     def lengths(self):
-        """Frames with a target per trajectory (T - 1)."""
-        return [tr.T - 1 for tr in self._trajs]
+        """Frames with all their targets per trajectory (T - horizon; T - 1 for the single-step loss)."""
+        return pick_lengths([tr.T for tr in self._trajs], self.horizon)
 
     # ------------------------------------------------------------------------------------------------ filling
     def _claim(self, nbytes):
@@ -115,6 +125,8 @@ class TrajectoryBank:
         tr.T, tr.N = int(state.shape[0]), int(state.shape[1])
         if tr.T < 2:
             raise ValueError("TrajectoryBank.add: a trajectory needs at least two frames")
+        if tr.T < self.horizon + 1:
+            raise ValueError(f"TrajectoryBank.add: horizon = {self.horizon} needs at least {self.horizon + 1} frames, this trajectory has {tr.T}")
         if state.shape[-1] != len(cfg.noise_level):
             raise ValueError(f"TrajectoryBank.add: {state.shape[-1]} state channels, cfg.noise_level has {len(cfg.noise_level)}")
         if typ.shape[-1] != 1:
@@ -150,14 +162,15 @@ class TrajectoryBank:
         return [self.add(s) for s in sources[lo:hi]]
 
     # ------------------------------------------------------------------------------------------------ batches
-    def _assemble(self, picks, noisy, draw, return_noise):
+    def _assemble(self, picks, noisy, draw, return_noise, horizon=1):
         cfg = self.cfg
         n_c, table = len(self._std), (_Sample * len(picks))()
         p, rows = None, 0
         for k, (si, ti) in enumerate(picks):
             tr = self._trajs[si]
-            if not 0 <= ti < tr.T - 1:
-                raise IndexError(f"frame {ti} of trajectory {si}: it has {tr.T - 1} frames with a target")
+            if not 0 <= ti < tr.T - horizon:
+                raise IndexError(f"frame {ti} of trajectory {si}: it has {tr.T - horizon} frames with " +
+                                 ("a target" if horizon == 1 else f"{horizon} targets"))
             frame = tr.N * 4
             s = table[k]
             s.state_in = tr.state.data_ptr() + ti * frame * n_c
@@ -173,13 +186,17 @@ class TrajectoryBank:
         new = lambda w: torch.empty(rows, w, device=self.device, dtype=torch.float32)
         node_in, node_tar, node_mask = new(n_c + p + 1), new(n_c), new(1)
         noise = new(n_c) if return_noise else None
+        later = torch.empty(horizon - 1, rows, n_c, device=self.device, dtype=torch.float32) if horizon > 1 else None
         with torch.cuda.device(self.device):
+            if later is not None:
+                _abi.check(_abi.lib().bsms_batch_targets(C.addressof(table), len(picks), n_c, horizon - 1, later.data_ptr(),
+                                                         torch.cuda.current_stream(self.device).cuda_stream), "bsms_batch_targets")
             _abi.check(_abi.lib().bsms_batch_assemble(
                 C.addressof(table), len(picks), n_c, p, C.addressof(self._std) if noisy else None, float(cfg.noise_gamma),
                 C.addressof(self._valid), len(self._valid), self.seed, int(draw) & _MASK64, node_in.data_ptr(), node_tar.data_ptr(),
                 node_mask.data_ptr(), None if noise is None else noise.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
                 "bsms_batch_assemble")
-        return node_in, node_tar, node_mask, noise
+        return node_in, node_tar, node_mask, noise, later
 
     def _hier_views(self, B):
         v = self._views.get(B)
@@ -188,24 +205,33 @@ class TrajectoryBank:
             v = self._views[B] = ([g.unsqueeze(0).expand(B, *g.shape) for g in m_gs], [i.unsqueeze(0).expand(B, *i.shape) for i in m_ids])
         return v
 
-    def batch(self, picks, train=True, draw=None, return_noise=False):
+    def batch(self, picks, train=True, draw=None, return_noise=False, horizon=None):
         """The device batch of `picks`, a list of (trajectory, frame).  `train`: inject the training noise; `draw` selects the
         noise of this batch (None: the bank's running batch counter, which then advances).  Consistent mesh:
         [node_in [B,N,C+p+1], node_tar [B,N,C], node_mask [B,N,1], m_gs, m_ids]; variable meshes: the per-level LevelData list.
-        `return_noise` appends the noise tensor that was added ([B,N,C] / [rows,C]; zeros when `train` is false)."""
+        `return_noise` appends the noise tensor that was added ([B,N,C] / [rows,C]; zeros when `train` is false).
+        `horizon` (None: the bank's) = K > 1 returns (batch, later) -- or (batch, later, noise) -- with the targets of the steps after
+        the first, later [K-1,B,N,C] / [K-1,rows,C] = frames t+2 .. t+K as they are resident: the noise (and its `gamma` correction
+        of node_tar) belongs to the first step alone, whose tensors are bit-equal to those of horizon = 1 for the same draw."""
+        horizon = self.horizon if horizon is None else int(horizon)
+        if horizon < 1:
+            raise ValueError(f"horizon must be >= 1, got {horizon}")
         picks = [(int(si), int(ti)) for si, ti in picks]
         if not picks:
             raise ValueError("TrajectoryBank.batch: no picks")
         if draw is None:
             draw, self._draw = self._draw, self._draw + 1
-        node_in, node_tar, node_mask, noise = self._assemble(picks, bool(train), draw, return_noise)
+        node_in, node_tar, node_mask, noise, later = self._assemble(picks, bool(train), draw, return_noise, horizon)
         if self.cfg.consist_mesh:
             B, N = len(picks), self._hier[2]
             m_gs, m_ids = self._hier_views(B)
             out = [node_in.view(B, N, -1), node_tar.view(B, N, -1), node_mask.view(B, N, 1), m_gs, m_ids]
             noise = None if noise is None else noise.view(B, N, -1)
+            later = None if later is None else later.view(horizon - 1, B, N, -1)
         else:
             out = self._meshes.assemble([self._trajs[si].entry for si, _ in picks], node_in, node_tar, node_mask)
+        if later is not None:
+            return (out, later, noise) if return_noise else (out, later)
         return (out, noise) if return_noise else out
 
     def next_picks(self, B):
@@ -240,7 +266,7 @@ class TrajectoryBank:
         """What datapipe.TrajectoryDataset(mode="rollout") yields for trajectory `i`, on the device and without noise:
         (node_in [T-1,N,C+p+1], node_tar [T-1,N,C], node_mask [T-1,N,1], m_gs, m_ids)."""
         tr = self._trajs[i]
-        node_in, node_tar, node_mask, _ = self._assemble([(i, t) for t in range(tr.T - 1)], False, 0, False)
+        node_in, node_tar, node_mask, _, _ = self._assemble([(i, t) for t in range(tr.T - 1)], False, 0, False)
         m_gs, m_ids = self.hierarchy(i)
         return node_in.view(tr.T - 1, tr.N, -1), node_tar.view(tr.T - 1, tr.N, -1), node_mask.view(tr.T - 1, tr.N, 1), m_gs, m_ids
 

@@ -128,8 +128,10 @@ def global_masked_rmse(pred, tar, mask, group=None):
 class DataParallel:
     """Wraps a replica: broadcast of parameters at construction, bucketed gradient all-reduce."""
 
-    def __init__(self, model, bucket_bytes=2 << 20, group=None):
-        self.model, self.group = model, group
+    def __init__(self, model, bucket_bytes=2 << 20, group=None, unroll=1, step_weights=None, detach=False):
+        """`unroll` > 1: the loss runs over that many autoregressive steps (step.FusedStep; `step_weights` default 1/unroll,
+        `detach` cuts the gradient between the steps).  Only the fused step implements it."""
+        self.model, self.group, self.unroll = model, group, int(unroll)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
             for t in list(model.parameters()) + list(model.buffers()):
                 dist.broadcast(t.data, src=0, group=group)
@@ -146,15 +148,21 @@ class DataParallel:
         from .step import FusedStep
         self.fused = None
         if os.environ.get("BSMS_FUSED_STEP", "1") == "1" and FusedStep.supports(model) and next(model.parameters()).is_cuda:
-            self.fused = FusedStep(model, self.grads, group, use_graph=os.environ.get("BSMS_STEP_GRAPH", "0") == "1")
+            self.fused = FusedStep(model, self.grads, group, use_graph=os.environ.get("BSMS_STEP_GRAPH", "0") == "1",   # with unroll > 1: ValueError
+                                   unroll=self.unroll, step_weights=step_weights, detach=detach)
+        if self.unroll > 1 and self.fused is None:
+            raise ValueError("DataParallel: unroll > 1 needs the fused step (a standard BSMS_Simulator on the GPU, BSMS_FUSED_STEP != 0)")
 
     def __call__(self, *a, **k):
         return self.model(*a, **k)
 
-    def step_loss_backward(self, data, consistent_mesh=True):
-        """One fwd + exact global loss + bwd + gradient reduction.  Returns the (global) loss."""
+    def step_loss_backward(self, data, consistent_mesh=True, later_targets=None):
+        """One fwd + exact global loss + bwd + gradient reduction.  Returns the (global) loss.  `later_targets`: the targets
+        of steps 1 .. unroll-1 of an unrolled loss (step.FusedStep.__call__)."""
         if self.fused is not None:
-            return self.fused(data, consistent_mesh)
+            return self.fused(data, consistent_mesh) if later_targets is None else self.fused(data, consistent_mesh, later_targets)
+        if later_targets is not None:
+            raise ValueError("DataParallel: later_targets need the fused step")
         self.grads.zero()
         pred = self.model(data, consistent_mesh, False)
         loss = global_masked_rmse(pred, data[1] if consistent_mesh else data[0].y.unsqueeze(0),

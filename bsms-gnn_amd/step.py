@@ -13,7 +13,12 @@ captured in a HIP graph.  Here the step is
 with every weight gradient written straight into its slot of the flat gradient buffer (`GradBuckets.flat`), which the
 parameters' `.grad` alias.  Same kernels as the autograd path for everything but the glue: U-Net / MLP gradients are
 bit-identical to it, the loss and its gradient agree to fp32 round-off (tests/test_hip_training.py).  With
-`use_graph=True` the two halves are captured into HIP graphs and replayed (inputs are copied into static buffers)."""
+`use_graph=True` the two halves are captured into HIP graphs and replayed (inputs are copied into static buffers).
+
+`unroll=K > 1` trains on K autoregressive steps: K forwards, each with its own saved activations, chained by
+the rollout rule (bsms_sim_epilogue's `next_in`), then K backwards in reverse order; bsms_sim_unroll_bwd carries the gradient
+from step k+1 into step k (or cuts it, `detach=True`), and every step but the last-run-first writes its weight gradients into a
+scratch flat buffer that bsms_grad_accumulate folds into `GradBuckets.flat`."""
 import os
 
 import torch
@@ -53,13 +58,25 @@ class _Arena:
 
 
 class FusedStep:
-    def __init__(self, model, grads, group=None, use_graph=False):
+    def __init__(self, model, grads, group=None, use_graph=False, unroll=1, step_weights=None, detach=False):
         from .model import BSMS_Simulator
         if not isinstance(model, BSMS_Simulator):
             raise TypeError("FusedStep drives a bsms_gnn_amd.BSMS_Simulator")
         if model.process.per_block:
             raise ValueError("FusedStep uses the one-call U-Net (BSGMP.per_block must be False)")
+        unroll = int(unroll)
+        if unroll < 1:
+            raise ValueError(f"FusedStep: unroll must be >= 1, got {unroll}")
+        if unroll > 1 and use_graph:
+            raise ValueError("FusedStep: the unrolled step (unroll > 1) is not captured into HIP graphs; use use_graph=False")
+        if step_weights is None:
+            step_weights = [1.0 / unroll] * unroll
+        step_weights = [float(w) for w in step_weights]
+        if len(step_weights) != unroll:
+            raise ValueError(f"FusedStep: {len(step_weights)} step_weights for unroll = {unroll}")
         self.model, self.grads, self.group, self.use_graph = model, grads, group, use_graph
+        self.unroll, self.step_weights, self.detach = unroll, step_weights, bool(detach)
+        self._gscratch, self._wts = None, None     # unroll > 1: scratch flat gradient buffer (GradBuckets layout), weights on the device
         self._shape_key, self._graphs, self._ptr_guard = None, None, None
         self._arena = _Arena()
         self._overlap = None          # bucket schedule of the overlapped gradient all-reduce (_bucket_schedule), built lazily
@@ -124,6 +141,11 @@ class FusedStep:
         if guard != self._ptr_guard:                # parameters were re-pointed (optimizer flat buffer, .to(), load)
             slot = lambda ps: [self.grads.flat[self.grads._slot[p][0]:].data_ptr() for p in ps]
             self._tabs = {k: (_param_ptrs(ps), _abi.ptr_array(slot(ps))) for k, ps in (("enc", enc), ("proc", proc), ("dec", dec))}
+            if self.unroll > 1:                     # the same slots in the scratch flat buffer: where all steps but the first-run write
+                if self._gscratch is None or self._gscratch.device != self.grads.flat.device:
+                    self._gscratch = torch.zeros_like(self.grads.flat)       # zeros: a slot no kernel writes adds nothing
+                scr = lambda ps: [self._gscratch[self.grads._slot[p][0]:].data_ptr() for p in ps]
+                self._tabs_scratch = {k: (self._tabs[k][0], _abi.ptr_array(scr(ps))) for k, ps in (("enc", enc), ("proc", proc), ("dec", dec))}
             self._ptr_guard = guard
             self._graphs = None
         return self._tabs
@@ -155,7 +177,8 @@ class FusedStep:
         return b
 
     # ------------------------------------------------------------------------------------------------ the two halves
-    def _forward(self, b, node_in, tar, mask, ews, B, N):
+    def _forward(self, b, node_in, tar, mask, ews, B, N, next_in=None, ic=None):
+        """`next_in` / `ic` (unrolled step only): the epilogue also writes the next step's input by the rollout rule."""
         m, L, s = self.model, _abi.lib(), _stream()
         C, p, D, H = m.cfg.out_dim, m.pos_dim, m.cfg.latent_dim, m.cfg.hidden_layer
         R, t = b["R"], self._tabs
@@ -173,19 +196,30 @@ class FusedStep:
                           work.data_ptr(), s), "bsms_mlp_fwd(decode)")
         ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), tar.data_ptr(), R, C, p,
                                no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["pred"].data_ptr(),
-                               None, None, b["sums"].data_ptr(), work.data_ptr(), s), "bsms_sim_epilogue")
+                               _ptr(next_in), _ptr(ic), b["sums"].data_ptr(), work.data_ptr(), s), "bsms_sim_epilogue")
 
-    def _backward(self, b, tar, mask, ews, B, N, events=None):
-        """`events`: (pointer array, keep-alive) of 2L+1 hipEvent_t for bsms_bsgmp_bwd_ev, or None."""
+    def _backward(self, b, tar, mask, ews, B, N, events=None, chain=None):
+        """`events`: (pointer array, keep-alive) of 2L+1 hipEvent_t for bsms_bsgmp_bwd_ev, or None.
+        `chain` (unrolled step only): dict(w, g_pred_next, g_nin_next, g_pred, grad_x, tabs) -- the loss gradient comes from
+        bsms_sim_unroll_bwd with the carried pair, the encoder's backward returns its input gradient into `grad_x`, and the
+        weight gradients go to the slots of `tabs`."""
         m, L, s = self.model, _abi.lib(), _stream()
         C, p, D, H = m.cfg.out_dim, m.pos_dim, m.cfg.latent_dim, m.cfg.hidden_layer
-        R, t = b["R"], self._tabs
+        R, t = b["R"], (self._tabs if chain is None else chain["tabs"])
         work = b["work"]
         no = m._targetNormalizer
         ck = _abi.check
-        ck(L.bsms_sim_loss_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), R, C, no._E_data.data_ptr(),
-                               no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["sums"].data_ptr(), b["loss"].data_ptr(),
-                               b["g_np"].data_ptr(), s), "bsms_sim_loss_bwd")
+        if chain is None:
+            ck(L.bsms_sim_loss_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), R, C, no._E_data.data_ptr(),
+                                   no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["sums"].data_ptr(), b["loss"].data_ptr(),
+                                   b["g_np"].data_ptr(), s), "bsms_sim_loss_bwd")
+        else:
+            ni = m._inputNormalizer
+            ck(L.bsms_sim_unroll_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), R, C, no._E_data.data_ptr(),
+                                     no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), ni._E_data.data_ptr(),
+                                     ni._E_data_squared.data_ptr(), ni.std_eps.data_ptr(), b["sums"].data_ptr(), chain["w"],
+                                     _ptr(chain["g_pred_next"]), _ptr(chain["g_nin_next"]), b["loss"].data_ptr(),
+                                     _ptr(chain["g_pred"]), b["g_np"].data_ptr(), s), "bsms_sim_unroll_bwd")
         ck(L.bsms_mlp_bwd_ex(b["h1"].data_ptr(), b["g_np"].data_ptr(), R, D, D, C, H, 0, t["dec"][0][0], b["s_dec"].data_ptr(),
                              b["work_dec"].data_ptr(), b["gh1"].data_ptr(), t["dec"][1][0], 1, s), "bsms_mlp_bwd(decode)")   # 1 = BSMS_BWD_DEFER_JOIN
         ewp, keep = _abi.ptr_array([e.data_ptr() for e in ews])
@@ -195,12 +229,17 @@ class FusedStep:
                                t["proc"][0][0], b["s_proc"].data_ptr(), work.data_ptr(), b["gh0"].data_ptr(), t["proc"][1][0],
                                PRECISIONS[b["prec"]], 1, None if events is None else events[0], s), "bsms_bsgmp_bwd")
         ck(L.bsms_mlp_bwd(b["norm_in"].data_ptr(), b["gh0"].data_ptr(), R, C + 1, D, D, H, 1, t["enc"][0][0], b["s_enc"].data_ptr(),
-                          b["work_enc"].data_ptr(), None, t["enc"][1][0], s), "bsms_mlp_bwd(encode)")
+                          b["work_enc"].data_ptr(), None if chain is None else _ptr(chain["grad_x"]), t["enc"][1][0], s),
+           "bsms_mlp_bwd(encode)")
         ck(L.bsms_side_lanes_join(s), "bsms_side_lanes_join")
 
     # ------------------------------------------------------------------------------------------------ the step
-    def __call__(self, data, consistent=True):
+    def __call__(self, data, consistent=True, later_targets=None):
+        """`later_targets` (unroll = K > 1 only): the targets of steps 1 .. K-1, [K-1, B, N, C] for consistent meshes and
+        [K-1, rows, C] for variable meshes (frames t+2 .. t+K; TrajectoryBank(horizon=K) hands them out)."""
         node_in, tar, mask, m_gs, m_ids = self._unpack(data, consistent)
+        if (self.unroll > 1) != (later_targets is not None):
+            raise ValueError(f"FusedStep: unroll = {self.unroll} " + ("needs later_targets" if self.unroll > 1 else "takes no later_targets"))
         if not node_in.is_cuda:
             raise _abi.BsmsError("FusedStep: the BSMS engine runs on the GPU only; there is no CPU fallback")
         B, N = node_in.shape[0], node_in.shape[1]
@@ -209,6 +248,8 @@ class FusedStep:
         self._pointer_tables()
         b = self._buffers(B, N, plans, node_in.device)
         world = self._world()
+        if self.unroll > 1:
+            return self._unrolled(b, node_in, tar, mask, later_targets, ews, B, N, world, consistent)
         if self.use_graph:
             return self._replay(b, node_in, tar, mask, ews, B, N, world)
         self._forward(b, node_in, tar, mask, ews, B, N)
@@ -222,6 +263,87 @@ class FusedStep:
                 dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         self._probe_end()
         return b["loss"][0].clone()       # the static buffer is overwritten by the next step: hand out a copy (4 bytes)
+
+    # ------------------------------------------------------------------------------------------------ the unrolled step
+    _PER_STEP = ("s_enc", "s_proc", "s_dec", "norm_in", "h0", "h1", "pred", "sums")     # saved per step; everything else is shared
+
+    def _unroll_buffers(self, b, B, N, dev):
+        """Step k's own buffers (`name@k` in the arena) on top of the shared ones of `_buffers`, which serve as step 0's."""
+        if b.get("steps") is not None:
+            return b["steps"]
+        m, K = self.model, self.unroll
+        C, p = m.cfg.out_dim, m.pos_dim
+        R, ar = b["R"], self._arena
+        sums = ar.f32("sums_all", dev, K, 2)              # ONE buffer: the data-parallel all-reduce of the sums is one message
+        losses = ar.f32("loss_all", dev, K)
+        steps = []
+        for k in range(K):
+            bk = dict(b)
+            for name in self._PER_STEP:
+                if name == "sums":
+                    bk[name] = sums[k]
+                elif k > 0:
+                    src = b[name]
+                    nbytes = src.numel() * src.element_size()
+                    bk[name] = ar.bytes(f"{name}@{k}", nbytes, dev) if src.dtype == torch.uint8 else ar.f32(f"{name}@{k}", dev, *src.shape)
+            bk["loss"] = losses[k:k + 1]
+            bk["in"] = None if k == 0 else ar.f32(f"in@{k}", dev, B, N, C + p + 1)
+            steps.append(bk)
+        b.update(steps=steps, pred=steps[K - 1]["pred"], sums_all=sums, loss_all=losses, g_pred=(ar.f32("g_pred@0", dev, R, C), ar.f32("g_pred@1", dev, R, C)),
+                 g_nin=ar.f32("g_nin", dev, R, C + 1))
+        if self._wts is None or self._wts.device != dev:
+            self._wts = torch.tensor(self.step_weights, device=dev, dtype=torch.float32)
+        return steps
+
+    def _later(self, later, node_in, consistent):
+        K, C = self.unroll, self.model.cfg.out_dim
+        B, N = node_in.shape[0], node_in.shape[1]
+        if not torch.is_tensor(later):
+            raise RuntimeError("later_targets must be a tensor")
+        if later.dim() == 3 and not consistent:          # variable meshes: [K-1, rows, C]
+            later = later.unsqueeze(1)
+        if tuple(later.shape) != (K - 1, B, N, C):
+            raise RuntimeError(f"later_targets must be [K-1, B, N, out_dim] = {(K - 1, B, N, C)} (or [K-1, rows, out_dim] for variable "
+                               f"meshes), got {tuple(later.shape)}")
+        if later.device != node_in.device:
+            raise RuntimeError(f"later_targets is on {later.device}, node_in on {node_in.device}")
+        return later if (later.is_contiguous() and later.dtype == torch.float32) else later.contiguous().float()
+
+    def _unrolled(self, b, node_in, tar, mask, later, ews, B, N, world, consistent):
+        K, L, s = self.unroll, _abi.lib(), _stream()
+        later = self._later(later, node_in, consistent)
+        steps = self._unroll_buffers(b, B, N, node_in.device)
+        tars = [tar, *(later[k] for k in range(K - 1))]
+        # K forwards: step k's epilogue writes in_{k+1} = where(mask == 0, in_0, cat[pred_k, mesh_pos | type])
+        for k, bk in enumerate(steps):
+            nxt = steps[k + 1]["in"] if k + 1 < K else None
+            self._forward(bk, node_in if k == 0 else bk["in"], tars[k], mask, ews, B, N, next_in=nxt, ic=None if nxt is None else node_in)
+        if world > 1:
+            dist.all_reduce(b["sums_all"], op=dist.ReduceOp.SUM, group=self.group)
+        # K backwards, k = K-1 .. 0.  The first one run writes grads.flat itself, the others the scratch buffer, folded in after
+        # the join: the deferred weight-gradient lanes of step k still write it (and read work / work_enc / work_dec) until then
+        n = self.grads.flat.numel()
+        for k in range(K - 1, -1, -1):
+            bk, last = steps[k], k == K - 1
+            carry = not last and not self.detach
+            chain = dict(w=self.step_weights[k], tabs=self._tabs if last else self._tabs_scratch,
+                         g_pred_next=b["g_pred"][(k + 1) & 1] if carry else None, g_nin_next=b["g_nin"] if carry else None,
+                         g_pred=b["g_pred"][k & 1] if (k > 0 and not self.detach) else None,
+                         grad_x=b["g_nin"] if (k > 0 and not self.detach) else None)
+            self._backward(bk, tars[k], mask, ews, B, N, chain=chain)          # ends with bsms_side_lanes_join
+            if not last:
+                _abi.check(L.bsms_grad_accumulate(self.grads.flat.data_ptr(), self._gscratch.data_ptr(), n, 0, s), "bsms_grad_accumulate")
+        if world > 1:
+            dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
+        return torch.dot(b["loss_all"], self._wts)
+
+    def predictions(self):
+        """The K predictions of the last step, [B,N,C] each (static buffers: clone to keep)."""
+        return [bk["pred"] for bk in self._buf["steps"]] if self.unroll > 1 else [self._buf["pred"]]
+
+    def step_losses(self):
+        """Device [K]: the masked RMSE of every step of the last call, unweighted (a copy)."""
+        return (self._buf["loss_all"] if self.unroll > 1 else self._buf["loss"]).clone()
 
     # ------------------------------------------------------------------------------------------------ overlapped all-reduce
     # False (BSMS_OVERLAP_ALLREDUCE=0): ONE all-reduce of the whole flat buffer after the backward (rounds 1-3)

@@ -149,13 +149,17 @@ class DevicePrefetcher:
 
 class Trainer:
     """src/trainer/trainer.py:9-229.  `model_cfg` needs consistent_mesh, accumulation_steps; `opt_cfg` needs
-    peak_lr, weight_decay, warmup_steps, decay_steps, gnorm_clip (configs/opt/default.yaml)."""
+    peak_lr, weight_decay, warmup_steps, decay_steps, gnorm_clip (configs/opt/default.yaml).  Optional in `model_cfg`:
+    unroll_steps (default 1: the reference's single-step loss), unroll_weights, unroll_detach -- the loss over that many
+    autoregressive steps (step.FusedStep); `iter` then takes `(batch, later_targets)`, what TrajectoryBank(horizon=K) hands out."""
 
     def __init__(self, model, model_cfg, opt_cfg):
         self.model_cfg, self.opt_cfg = model_cfg, opt_cfg
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.model = model.to(self.device)
-        self.dp = DataParallel(self.model)                       # world size 1: no collective is issued
+        self.unroll = int(getattr(model_cfg, "unroll_steps", 1) or 1)
+        self.dp = DataParallel(self.model, unroll=self.unroll, step_weights=getattr(model_cfg, "unroll_weights", None),
+                               detach=bool(getattr(model_cfg, "unroll_detach", False)))     # world size 1: no collective is issued
         self.optimizer = FusedAdamW(self.dp.grads, lr=opt_cfg.peak_lr, weight_decay=opt_cfg.weight_decay,
                                     max_grad_norm=opt_cfg.gnorm_clip)
         self.lr_scheduler = WarmupCosineDecay(opt_cfg.peak_lr, opt_cfg.warmup_steps, opt_cfg.decay_steps)
@@ -248,7 +252,13 @@ class Trainer:
 
     def iter(self, data):
         """One training iteration (trainer.py:134-156): statistics only during warm-up, otherwise
-        fwd + loss + bwd (+ gradient all-reduce) + clip + AdamW + LR schedule."""
+        fwd + loss + bwd (+ gradient all-reduce) + clip + AdamW + LR schedule.  With model_cfg.unroll_steps = K > 1 `data` is
+        `(batch, later_targets)`; the warm-up iterations look at the batch only."""
+        later = None
+        if self.unroll > 1:
+            if not (isinstance(data, (tuple, list)) and len(data) == 2 and torch.is_tensor(data[1]) and not torch.is_tensor(data[0])):
+                raise ValueError(f"Trainer.iter: unroll_steps = {self.unroll} takes (batch, later_targets)")
+            data, later = data[0], self.move_to_device(data[1])
         data = self.move_to_device(data)
         if self._warming_up():
             self._model_forward(data)
@@ -257,7 +267,7 @@ class Trainer:
             if not self._synced:                                  # merge normaliser statistics once (dp.py)
                 self.dp.sync_normalizers(self._norm_base)
                 self._synced, self._norm_base = True, None
-            loss = self.dp.step_loss_backward(data, self.model_cfg.consistent_mesh)
+            loss = self.dp.step_loss_backward(data, self.model_cfg.consistent_mesh, later)
             self.optimizer.step(self.lr_scheduler.lr())
             self.lr_scheduler.step()
         self.train_step += 1

@@ -348,6 +348,26 @@ int bsms_sim_epilogue(const float* norm_pred, const float* node_in, const float*
 int bsms_sim_loss_bwd(const float* pred, const float* target, const float* mask, int64_t R, int64_t C, const double* mean,
                       const double* meansq, const double* std_eps, const float* sums, float* loss_out /* nullable */,
                       float* grad_norm_pred, bsms_stream_t stream);
+/* One step k of an UNROLLED loss over K autoregressive steps (step.py), backward: bsms_sim_loss_bwd with the step weight `w`
+ * and the gradient carried back from step k+1, whose input was in_{k+1} = where(mask == 0, in_0, cat[pred_k, mesh_pos | type])
+ * (the rollout rule, utils/rollout_utils.py:57-62).  One launch per step, in the order k = K-1 .. 0:
+ *   loss_k        = sqrt(S_k / M_k / C) from `sums` (written to loss_out, nullable; NOT weighted)
+ *   g_pred_k      = w * ((pred_k - tar_k) * mask * coef_k) + carry_k          coef_k = 1 / (loss_k M_k C) as bsms_sim_loss_bwd forms it
+ *   carry_k       = mask != 0 ? g_pred_next + float(double(g_norm_in_next[:, c]) / std_in[c]) : 0         (c < C)
+ *   grad_norm_pred = float(double(g_pred_k * mask) * std_out)
+ * `g_pred_next` [R,C] is the g_pred this entry wrote for step k+1, `g_norm_in_next` [R,C+1] the input gradient of step k+1's
+ * encoder backward (bsms_mlp_bwd's grad_x; its node-type column is not used).  The pair is given together or not at all: both
+ * NULL for the last step and for a detached ("pushforward") chain -- then, with w = 1, the result is bit for bit that of
+ * bsms_sim_loss_bwd.  The identity term of pred = state + delta * mask acts on every row; the carry stops it on rows with
+ * mask == 0, which took in_0.  `g_pred` (nullable: nobody carries further) must not alias g_pred_next.  mean / meansq / std_eps are
+ * the TARGET normaliser's fields, in_* the INPUT normaliser's (needed with a carried pair only).  R >= 1 and C in 1..8
+ * (BSMS_E_UNSUPPORTED otherwise), null pointers give BSMS_E_INVALID_ARG, all before any device call; the call allocates
+ * nothing, does not synchronise and reads nothing back.  No atomics. */
+int bsms_sim_unroll_bwd(const float* pred, const float* target, const float* mask, int64_t R, int64_t C, const double* mean,
+                        const double* meansq, const double* std_eps, const double* in_mean /* nullable */,
+                        const double* in_meansq /* nullable */, const double* in_std_eps /* nullable */, const float* sums, float w,
+                        const float* g_pred_next /* nullable */, const float* g_norm_in_next /* nullable */,
+                        float* loss_out /* nullable */, float* g_pred /* nullable */, float* grad_norm_pred, bsms_stream_t stream);
 
 /* ---------------------------------------------------------------- evaluation: masked error sums ---
  * The reductions behind the reference's evaluation figures -- `Trainer.get_error` (trainer/trainer.py:254-269: per-sample
@@ -405,6 +425,15 @@ int bsms_batch_assemble(const bsms_batch_sample* samples, int64_t n_samples, int
                         const float* noise_std /* HOST [C], nullable */, double noise_gamma,
                         const float* valid_types /* HOST */, int64_t n_valid, uint64_t seed, uint64_t draw, float* node_in,
                         float* node_tar, float* node_mask, float* noise_out /* nullable */, bsms_stream_t stream);
+/* The LATER targets of an unrolled loss, from the same table: later [n_later, R, C] with
+ *   later[j, r, :] = (state_tar + (j + 1) * n * C)[row of r inside its sample, :]        j = 0 .. n_later - 1
+ * -- the resident state of a trajectory is [T, n, C], so the frames after `state_tar` follow it at a fixed stride; the CALLER
+ * guarantees that n_later more frames exist behind every sample's state_tar.  Copied bit for bit, no noise.  One launch per 64
+ * samples (the later frame is the grid's second axis), a block never straddles two samples.  n_later == 0 or n_samples == 0
+ * returns BSMS_OK and touches nothing; C in 1..8 (BSMS_E_UNSUPPORTED), n_later <= 65535, null pointers give
+ * BSMS_E_INVALID_ARG; all checked before any device call. */
+int bsms_batch_targets(const bsms_batch_sample* samples, int64_t n_samples, int64_t C, int64_t n_later, float* later,
+                       bsms_stream_t stream);
 
 /* ---------------------------------------------------------------- hierarchy builder (host) ---
  * BistrideMultiLayerGraph (graph_wrappers/bsms_graph_wrapper.py:8-154 + graph_wrapper.py:67-134): the
@@ -438,6 +467,12 @@ size_t bsms_adamw_work_bytes(void);
 int bsms_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                     float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                     float max_grad_norm, float* grad_norm_out, void* work, bsms_stream_t stream);
+/* acc[i] = first ? g[i] : acc[i] + g[i] over a flat gradient buffer of n floats (first != 0 overwrites whatever acc held).
+ * The weight-gradient kernels overwrite their slots, so every step of an unrolled loss writes a scratch buffer with the
+ * layout of the real one and this entry folds it in; fp32 adds in a fixed order, one thread per element.  16-byte accesses
+ * when both pointers are 16-byte aligned.  n == 0 returns BSMS_OK; n < 0 BSMS_E_SHAPE; null or identical pointers
+ * BSMS_E_INVALID_ARG. */
+int bsms_grad_accumulate(float* acc, const float* g, int64_t n, int first, bsms_stream_t stream);
 
 #ifdef __cplusplus
 }
