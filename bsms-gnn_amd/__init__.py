@@ -5,6 +5,7 @@ libbsms_hip.so (include/bsms_hip.h).  Import name: `bsms_gnn_amd` (directory: `b
 from . import _abi  # noqa: F401
 from .graph import LevelData, LevelPlan, MeshBank, clear_plan_cache, collate_variable_meshes, concat_plans, plan_for  # noqa: F401
 from .model import BSMS_Simulator, Normalizer, masked_rmse  # noqa: F401
+from .objective import Objective, masked_loss  # noqa: F401
 from .ops import BSGMP, GMP, MLP, InferenceSession, Unpool, WeightedEdgeConv, degree, error_sums, scatter_sum  # noqa: F401
 from .eval import error_mean_std  # noqa: F401
 from .databank import TrajectoryBank, epoch_picks  # noqa: F401

@@ -234,3 +234,77 @@ extern "C" int bsms_sim_unroll_bwd(const float* pred, const float* target, const
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
+
+namespace {
+
+// k_sim_unroll_bwd for the family of objectives (include/bsms_hip.h: bsms_sim_objective_bwd).  `sums` = [M | SE[0..C)] in fp64
+// (bsms_error_sums); every thread forms the C per-channel coefficients G * a_c from it in fp64 and rounds each to fp32 once.
+// The carry and the way out through the de-normalisation are those of k_sim_unroll_bwd, op for op.  No guard for M == 0 or
+// loss == 0, as in k_sim_loss_bwd: the non-finite coefficient reaches the output.
+__global__ __launch_bounds__(256) void k_sim_objective_bwd(const float* pred, const float* target, const float* mask, int64_t R,
+                                                           int C, const double* mean, const double* meansq, const double* eps,
+                                                           const double* in_mean, const double* in_meansq, const double* in_eps,
+                                                           const double* sums, const double* weights, int normalized, int rmse,
+                                                           float w, const float* g_pred_next, const float* g_norm_in_next,
+                                                           float* loss_out, float* chan_out, float* g_pred,
+                                                           float* grad_norm_pred) {
+  const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  const double e = *eps;
+  const double MC = sums[0] * double(C);
+  double sd[kMaxC], a[kMaxC];
+  double Q = 0.0;
+  for (int c = 0; c < C; ++c) {
+    sd[c] = std_eps(mean[c], meansq[c], e);
+    const double wc = weights ? weights[c] : 1.0;
+    a[c] = normalized ? wc / (sd[c] * sd[c]) : wc;
+    const double term = a[c] * sums[1 + c] / MC;
+    if (r == 0 && chan_out) chan_out[c] = float(term);
+    Q += term;
+  }
+  const double loss = rmse ? sqrt(Q) : Q;
+  if (r == 0 && loss_out) *loss_out = float(loss);
+  if (r >= R) return;
+  const double G = rmse ? 1.0 / (loss * MC) : 2.0 / MC;
+  const float m = mask[r];
+  const bool carried = g_pred_next != nullptr && m != 0.f;
+  const double ie = g_pred_next ? *in_eps : 0.0;
+  for (int c = 0; c < C; ++c) {
+    const float coef = float(G * a[c]);
+    float gp = (pred[r * C + c] - target[r * C + c]) * m * coef;
+    gp = w * gp;
+    if (carried) {
+      const float through_norm = float(double(g_norm_in_next[r * (C + 1) + c]) / std_eps(in_mean[c], in_meansq[c], ie));
+      const float g_state = g_pred_next[r * C + c] + through_norm;
+      gp = gp + g_state;
+    }
+    if (g_pred) g_pred[r * C + c] = gp;
+    const float gd = gp * m;
+    grad_norm_pred[r * C + c] = float(double(gd) * sd[c]);
+  }
+}
+
+}  // namespace
+
+extern "C" int bsms_sim_objective_bwd(const float* pred, const float* target, const float* mask, int64_t R, int64_t C,
+                                      const double* mean, const double* meansq, const double* std_eps_dev, const double* in_mean,
+                                      const double* in_meansq, const double* in_std_eps_dev, const double* sums,
+                                      const double* channel_weights, int space, int kind, float w, const float* g_pred_next,
+                                      const float* g_norm_in_next, float* loss_out, float* chan_out, float* g_pred,
+                                      float* grad_norm_pred, bsms_stream_t stream) {
+  BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "sim_objective_bwd: R=%lld C=%lld", (long long)R, (long long)C);
+  BSMS_REQUIRE((space == BSMS_LOSS_PHYSICAL || space == BSMS_LOSS_NORMALIZED) && (kind == BSMS_LOSS_MSE || kind == BSMS_LOSS_RMSE),
+               BSMS_E_UNSUPPORTED, "sim_objective_bwd: space=%d kind=%d (each 0 or 1)", space, kind);
+  BSMS_REQUIRE(pred && target && mask && mean && meansq && std_eps_dev && sums && grad_norm_pred, BSMS_E_INVALID_ARG,
+               "sim_objective_bwd: null argument");
+  BSMS_REQUIRE((g_pred_next == nullptr) == (g_norm_in_next == nullptr), BSMS_E_INVALID_ARG,
+               "sim_objective_bwd: the carried pair (g_pred_next, g_norm_in_next) is given together or not at all");
+  BSMS_REQUIRE(!g_pred_next || (in_mean && in_meansq && in_std_eps_dev), BSMS_E_INVALID_ARG,
+               "sim_objective_bwd: a carried gradient needs the input normaliser's statistics");
+  BSMS_REQUIRE(!g_pred || (g_pred != g_pred_next), BSMS_E_INVALID_ARG, "sim_objective_bwd: g_pred aliases g_pred_next");
+  hipLaunchKernelGGL(k_sim_objective_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask, R,
+                     (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, channel_weights,
+                     int(space == BSMS_LOSS_NORMALIZED), int(kind == BSMS_LOSS_RMSE), w, g_pred_next, g_norm_in_next, loss_out,
+                     chan_out, g_pred, grad_norm_pred);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}

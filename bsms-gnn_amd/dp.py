@@ -125,13 +125,35 @@ def global_masked_rmse(pred, tar, mask, group=None):
     return torch.sqrt(s / m / se.shape[-1])
 
 
+def global_masked_loss(pred, tar, mask, objective, std, group=None):
+    """objective.masked_loss under data parallelism: the 1 + C fp64 sums (M, SE_c) are all-reduced, the value is identical on all
+    ranks and the gradient flows through the local part only, as in global_masked_rmse (which the default objective is)."""
+    from .objective import channel_sums, finish_loss
+    if objective is None or objective.is_default:
+        return global_masked_rmse(pred, tar, mask, group)
+    objective.bind(pred.shape[-1])
+    M, SE = channel_sums(pred, tar, mask)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        tot = torch.cat([M.detach().reshape(1), SE.detach()])
+        dist.all_reduce(tot, op=dist.ReduceOp.SUM, group=group)
+        M, SE = tot[0], SE + (tot[1:] - SE.detach())
+    return finish_loss(M, SE, objective, std)[0]
+
+
 class DataParallel:
     """Wraps a replica: broadcast of parameters at construction, bucketed gradient all-reduce."""
 
-    def __init__(self, model, bucket_bytes=2 << 20, group=None, unroll=1, step_weights=None, detach=False):
+    def __init__(self, model, bucket_bytes=2 << 20, group=None, unroll=1, step_weights=None, detach=False, objective=None):
         """`unroll` > 1: the loss runs over that many autoregressive steps (step.FusedStep; `step_weights` default 1/unroll,
-        `detach` cuts the gradient between the steps).  Only the fused step implements it."""
+        `detach` cuts the gradient between the steps).  Only the fused step implements it.
+        `objective` (objective.Objective): None reads the optional loss_space / loss_kind / loss_channel_weights of `model.cfg`;
+        without them it is the reference's masked RMSE."""
+        from .objective import Objective
         self.model, self.group, self.unroll = model, group, int(unroll)
+        if objective is None:
+            objective = Objective.from_cfg(getattr(model, "cfg", None))
+        out_dim = getattr(getattr(model, "cfg", None), "out_dim", None)
+        self.objective = objective if out_dim is None else objective.bind(out_dim)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
             for t in list(model.parameters()) + list(model.buffers()):
                 dist.broadcast(t.data, src=0, group=group)
@@ -149,7 +171,7 @@ class DataParallel:
         self.fused = None
         if os.environ.get("BSMS_FUSED_STEP", "1") == "1" and FusedStep.supports(model) and next(model.parameters()).is_cuda:
             self.fused = FusedStep(model, self.grads, group, use_graph=os.environ.get("BSMS_STEP_GRAPH", "0") == "1",   # with unroll > 1: ValueError
-                                   unroll=self.unroll, step_weights=step_weights, detach=detach)
+                                   unroll=self.unroll, step_weights=step_weights, detach=detach, objective=self.objective)
         if self.unroll > 1 and self.fused is None:
             raise ValueError("DataParallel: unroll > 1 needs the fused step (a standard BSMS_Simulator on the GPU, BSMS_FUSED_STEP != 0)")
 
@@ -165,8 +187,12 @@ class DataParallel:
             raise ValueError("DataParallel: later_targets need the fused step")
         self.grads.zero()
         pred = self.model(data, consistent_mesh, False)
-        loss = global_masked_rmse(pred, data[1] if consistent_mesh else data[0].y.unsqueeze(0),
-                                  data[2] if consistent_mesh else data[0].mask.unsqueeze(0), self.group)
+        tar = data[1] if consistent_mesh else data[0].y.unsqueeze(0)
+        mask = data[2] if consistent_mesh else data[0].mask.unsqueeze(0)
+        if self.objective.is_default:
+            loss = global_masked_rmse(pred, tar, mask, self.group)
+        else:
+            loss = global_masked_loss(pred, tar, mask, self.objective, self.model._targetNormalizer.std_with_epsilon(), self.group)
         loss.backward()
         self.grads.finish()
         return loss

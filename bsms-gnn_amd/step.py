@@ -58,7 +58,9 @@ class _Arena:
 
 
 class FusedStep:
-    def __init__(self, model, grads, group=None, use_graph=False, unroll=1, step_weights=None, detach=False):
+    def __init__(self, model, grads, group=None, use_graph=False, unroll=1, step_weights=None, detach=False, objective=None):
+        """`objective` (objective.Objective): None or the default objective keeps the reference's masked RMSE on the kernels it
+        always ran on; any other runs bsms_error_sums after every forward and bsms_sim_objective_bwd in front of every backward."""
         from .model import BSMS_Simulator
         if not isinstance(model, BSMS_Simulator):
             raise TypeError("FusedStep drives a bsms_gnn_amd.BSMS_Simulator")
@@ -76,6 +78,10 @@ class FusedStep:
             raise ValueError(f"FusedStep: {len(step_weights)} step_weights for unroll = {unroll}")
         self.model, self.grads, self.group, self.use_graph = model, grads, group, use_graph
         self.unroll, self.step_weights, self.detach = unroll, step_weights, bool(detach)
+        from .objective import Objective
+        self.objective = (Objective() if objective is None else objective).bind(model.cfg.out_dim)
+        self._obj = None if self.objective.is_default else self.objective      # None: the default route, untouched
+        self._obj_w = None                          # the channel weights on the device (fp64 [C]), or None for unit weights
         self._gscratch, self._wts = None, None     # unroll > 1: scratch flat gradient buffer (GradBuckets layout), weights on the device
         self._shape_key, self._graphs, self._ptr_guard = None, None, None
         self._arena = _Arena()
@@ -173,8 +179,26 @@ class FusedStep:
                  work_enc=u8("work_enc", L.bsms_mlp_work_bytes(R, C + 1, D, D, H)),   # the encoder's backward overlaps the U-Net's last weight gradients
                  work_dec=u8("work_dec", L.bsms_mlp_work_bytes(R, D, D, C, H)),       # the decoder's weight gradients run under the U-Net's first block
                  in_static=None)
+        if self._obj is not None:                     # fp64 [M | SE | AE | TT] of bsms_error_sums, the per-channel terms, its scratch
+            b.update(osums=self._f64("osums", dev, 1, 1 + 3 * C)[0], chan=f("chan", 1, C)[0],
+                     work_obj=u8("work_obj", L.bsms_error_sums_work_bytes(1, R)))
+            if self._obj_w is None or self._obj_w.device != dev:
+                self._obj_w = self._obj.weights_tensor(dev)
         self._shape_key, self._buf, self._graphs = key, b, None
         return b
+
+    def _f64(self, name, dev, *shape):
+        n = 1
+        for d in shape:
+            n *= int(d)
+        return self._arena.bytes(name, 8 * n, dev).view(torch.float64).view(*shape)
+
+    def _loss_sums(self, b):
+        """What data parallelism all-reduces (SUM) between the forwards and the backwards: the fp32 pairs of the default route, or
+        the fp64 rows of bsms_error_sums (one contiguous message; the backward reads the 1 + C leading doubles of each row)."""
+        if self._obj is None:
+            return b["sums_all"] if self.unroll > 1 else b["sums"]
+        return b["osums_all"] if self.unroll > 1 else b["osums"]
 
     # ------------------------------------------------------------------------------------------------ the two halves
     def _forward(self, b, node_in, tar, mask, ews, B, N, next_in=None, ic=None):
@@ -194,9 +218,17 @@ class FusedStep:
                               b["h1"].data_ptr(), b["s_proc"].data_ptr(), work.data_ptr(), 0, PRECISIONS[b["prec"]], s), "bsms_bsgmp_fwd")
         ck(L.bsms_mlp_fwd(b["h1"].data_ptr(), R, D, D, C, H, 0, t["dec"][0][0], b["norm_pred"].data_ptr(), b["s_dec"].data_ptr(),
                           work.data_ptr(), s), "bsms_mlp_fwd(decode)")
-        ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), tar.data_ptr(), R, C, p,
+        if self._obj is None:
+            ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), tar.data_ptr(), R, C, p,
+                                   no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["pred"].data_ptr(),
+                                   _ptr(next_in), _ptr(ic), b["sums"].data_ptr(), work.data_ptr(), s), "bsms_sim_epilogue")
+            return
+        # another objective: no fp32 pair from the epilogue; one segment of R rows through bsms_error_sums instead (fp64, deterministic)
+        ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), None, R, C, p,
                                no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["pred"].data_ptr(),
-                               _ptr(next_in), _ptr(ic), b["sums"].data_ptr(), work.data_ptr(), s), "bsms_sim_epilogue")
+                               _ptr(next_in), _ptr(ic), None, work.data_ptr(), s), "bsms_sim_epilogue")
+        ck(L.bsms_error_sums(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), 1, R, C, R, R, R, b["osums"].data_ptr(),
+                             b["work_obj"].data_ptr(), s), "bsms_error_sums")
 
     def _backward(self, b, tar, mask, ews, B, N, events=None, chain=None):
         """`events`: (pointer array, keep-alive) of 2L+1 hipEvent_t for bsms_bsgmp_bwd_ev, or None.
@@ -209,7 +241,17 @@ class FusedStep:
         work = b["work"]
         no = m._targetNormalizer
         ck = _abi.check
-        if chain is None:
+        if self._obj is not None:
+            from .objective import KINDS, SPACES
+            ni, o = m._inputNormalizer, self._obj
+            c = chain or dict(w=1.0, g_pred_next=None, g_nin_next=None, g_pred=None)
+            ck(L.bsms_sim_objective_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), R, C, no._E_data.data_ptr(),
+                                        no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), ni._E_data.data_ptr(),
+                                        ni._E_data_squared.data_ptr(), ni.std_eps.data_ptr(), b["osums"].data_ptr(), _ptr(self._obj_w),
+                                        SPACES[o.space], KINDS[o.kind], c["w"], _ptr(c["g_pred_next"]), _ptr(c["g_nin_next"]),
+                                        b["loss"].data_ptr(), b["chan"].data_ptr(), _ptr(c["g_pred"]), b["g_np"].data_ptr(), s),
+               "bsms_sim_objective_bwd")
+        elif chain is None:
             ck(L.bsms_sim_loss_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), R, C, no._E_data.data_ptr(),
                                    no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["sums"].data_ptr(), b["loss"].data_ptr(),
                                    b["g_np"].data_ptr(), s), "bsms_sim_loss_bwd")
@@ -254,7 +296,7 @@ class FusedStep:
             return self._replay(b, node_in, tar, mask, ews, B, N, world)
         self._forward(b, node_in, tar, mask, ews, B, N)
         if world > 1:
-            dist.all_reduce(b["sums"], op=dist.ReduceOp.SUM, group=self.group)
+            dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
         if world > 1 and self._overlap_now():
             self._backward_overlapped(b, tar, mask, ews, B, N)
         else:
@@ -276,9 +318,13 @@ class FusedStep:
         R, ar = b["R"], self._arena
         sums = ar.f32("sums_all", dev, K, 2)              # ONE buffer: the data-parallel all-reduce of the sums is one message
         losses = ar.f32("loss_all", dev, K)
+        if self._obj is not None:
+            osums, chans = self._f64("osums_all", dev, K, 1 + 3 * C), ar.f32("chan_all", dev, K, C)
         steps = []
         for k in range(K):
             bk = dict(b)
+            if self._obj is not None:
+                bk["osums"], bk["chan"] = osums[k], chans[k]
             for name in self._PER_STEP:
                 if name == "sums":
                     bk[name] = sums[k]
@@ -291,6 +337,8 @@ class FusedStep:
             steps.append(bk)
         b.update(steps=steps, pred=steps[K - 1]["pred"], sums_all=sums, loss_all=losses, g_pred=(ar.f32("g_pred@0", dev, R, C), ar.f32("g_pred@1", dev, R, C)),
                  g_nin=ar.f32("g_nin", dev, R, C + 1))
+        if self._obj is not None:
+            b.update(osums_all=osums, chan_all=chans)
         if self._wts is None or self._wts.device != dev:
             self._wts = torch.tensor(self.step_weights, device=dev, dtype=torch.float32)
         return steps
@@ -319,7 +367,7 @@ class FusedStep:
             nxt = steps[k + 1]["in"] if k + 1 < K else None
             self._forward(bk, node_in if k == 0 else bk["in"], tars[k], mask, ews, B, N, next_in=nxt, ic=None if nxt is None else node_in)
         if world > 1:
-            dist.all_reduce(b["sums_all"], op=dist.ReduceOp.SUM, group=self.group)
+            dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
         # K backwards, k = K-1 .. 0.  The first one run writes grads.flat itself, the others the scratch buffer, folded in after
         # the join: the deferred weight-gradient lanes of step k still write it (and read work / work_enc / work_dec) until then
         n = self.grads.flat.numel()
@@ -342,8 +390,16 @@ class FusedStep:
         return [bk["pred"] for bk in self._buf["steps"]] if self.unroll > 1 else [self._buf["pred"]]
 
     def step_losses(self):
-        """Device [K]: the masked RMSE of every step of the last call, unweighted (a copy)."""
+        """Device [K]: the loss (the masked RMSE by default, else the objective) of every step of the last call, unweighted (a copy)."""
         return (self._buf["loss_all"] if self.unroll > 1 else self._buf["loss"]).clone()
+
+    def channel_losses(self):
+        """Device [K, C]: the per-channel terms a_c SE_c / (M C) of every step of the last call -- they add up to Q, the loss under
+        kind = "mse" and its square under "rmse" (a copy).  Only the objective route (bsms_sim_objective_bwd's `chan_out`) forms them."""
+        if self._obj is None:
+            raise ValueError("FusedStep.channel_losses: the default objective runs the reference's kernels, which form no per-channel "
+                             "terms; pass objective=Objective(channel_weights=[1.0] * out_dim) to get them for the same loss")
+        return (self._buf["chan_all"] if self.unroll > 1 else self._buf["chan"].reshape(1, -1)).clone()
 
     # ------------------------------------------------------------------------------------------------ overlapped all-reduce
     # False (BSMS_OVERLAP_ALLREDUCE=0): ONE all-reduce of the whole flat buffer after the backward (rounds 1-3)
@@ -494,7 +550,7 @@ class FusedStep:
         gf, gb, _ = self._graphs
         gf.replay()
         if world > 1:
-            dist.all_reduce(b["sums"], op=dist.ReduceOp.SUM, group=self.group)
+            dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
         gb.replay()
         if world > 1:
             dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)

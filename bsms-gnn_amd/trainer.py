@@ -151,15 +151,19 @@ class Trainer:
     """src/trainer/trainer.py:9-229.  `model_cfg` needs consistent_mesh, accumulation_steps; `opt_cfg` needs
     peak_lr, weight_decay, warmup_steps, decay_steps, gnorm_clip (configs/opt/default.yaml).  Optional in `model_cfg`:
     unroll_steps (default 1: the reference's single-step loss), unroll_weights, unroll_detach -- the loss over that many
-    autoregressive steps (step.FusedStep); `iter` then takes `(batch, later_targets)`, what TrajectoryBank(horizon=K) hands out."""
+    autoregressive steps (step.FusedStep); `iter` then takes `(batch, later_targets)`, what TrajectoryBank(horizon=K) hands out;
+    loss_space ("physical" / "normalized"), loss_kind ("rmse" / "mse"), loss_channel_weights -- the training objective
+    (objective.Objective; absent: the reference's masked RMSE in physical units), which `iter` trains on and `get_loss` reports."""
 
     def __init__(self, model, model_cfg, opt_cfg):
         self.model_cfg, self.opt_cfg = model_cfg, opt_cfg
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.model = model.to(self.device)
         self.unroll = int(getattr(model_cfg, "unroll_steps", 1) or 1)
+        from .objective import Objective
+        self.objective = Objective.from_cfg(model_cfg)
         self.dp = DataParallel(self.model, unroll=self.unroll, step_weights=getattr(model_cfg, "unroll_weights", None),
-                               detach=bool(getattr(model_cfg, "unroll_detach", False)))     # world size 1: no collective is issued
+                               detach=bool(getattr(model_cfg, "unroll_detach", False)), objective=self.objective)     # world size 1: no collective is issued
         self.optimizer = FusedAdamW(self.dp.grads, lr=opt_cfg.peak_lr, weight_decay=opt_cfg.weight_decay,
                                     max_grad_norm=opt_cfg.gnorm_clip)
         self.lr_scheduler = WarmupCosineDecay(opt_cfg.peak_lr, opt_cfg.warmup_steps, opt_cfg.decay_steps)
@@ -227,8 +231,9 @@ class Trainer:
         data = self.move_to_device(data)
         pred = self._model_forward(data)
         tar, mask = self.get_label_mask(data)
-        se = (pred - tar) ** 2
-        return torch.sqrt((se * mask).sum() / mask.sum() / se.shape[-1])
+        from .objective import masked_loss                    # the default objective: model.masked_rmse, the reference's formula
+        std = None if self.objective.space == "physical" else self.model._targetNormalizer.std_with_epsilon()
+        return masked_loss(pred, tar, mask, self.objective, std)
 
     def get_error(self, data, relative=True):
         """trainer/trainer.py:231-271: (error_mean, error_std) per channel as float32 NumPy arrays [C] -- the masked absolute

@@ -368,6 +368,35 @@ int bsms_sim_unroll_bwd(const float* pred, const float* target, const float* mas
                         const double* in_meansq /* nullable */, const double* in_std_eps /* nullable */, const float* sums, float w,
                         const float* g_pred_next /* nullable */, const float* g_norm_in_next /* nullable */,
                         float* loss_out /* nullable */, float* g_pred /* nullable */, float* grad_norm_pred, bsms_stream_t stream);
+/* bsms_sim_unroll_bwd for a FAMILY of masked objectives: the same step weight, the same carried pair, the same
+ * way out through the de-normalisation, with the loss chosen by `space`, `kind` and per-channel weights.  With d = fl32(pred - tar),
+ * m = mask and std_c the TARGET normaliser's std (formed from mean / meansq / std_eps as everywhere in this section):
+ *   sums            = [ M | SE[0..C) ]  DEVICE double, M = sum m, SE[c] = sum m d_c^2 -- the first 1 + C fields of a row of
+ *                     bsms_error_sums (under data parallelism the caller all-reduces them first: the loss is the exact global one)
+ *   a_c             = w_c (BSMS_LOSS_PHYSICAL)  or  w_c / std_c^2 (BSMS_LOSS_NORMALIZED); w = `channel_weights`, DEVICE double[C],
+ *                     NULL = all ones.  fp64.
+ *   Q               = sum_c a_c SE[c] / (M C)                                              (fp64)
+ *   loss            = Q (BSMS_LOSS_MSE)  or  sqrt(Q) (BSMS_LOSS_RMSE), written to loss_out (nullable; fp32, NOT weighted by `w`)
+ *   chan_out[c]     = a_c SE[c] / (M C)   (nullable float[C]: the per-channel terms of Q)
+ *   g_pred_k        = w * (d * m * fl32(G a_c)) + carry_k,   G = 2 / (M C) (mse)  or  1 / (loss M C) (rmse), G a_c formed in fp64
+ *   grad_norm_pred  = float(double(g_pred_k * mask) * std_c)
+ * carry_k, g_pred_next, g_norm_in_next, g_pred and the rule that the pair is given together or not at all are those of
+ * bsms_sim_unroll_bwd, as are in_mean / in_meansq / in_std_eps.  BSMS_LOSS_PHYSICAL + BSMS_LOSS_RMSE + unit weights is the loss of
+ * bsms_sim_loss_bwd, from fp64 sums instead of an fp32 pair (equal to fp32 round-off, not bit for bit).  M == 0, and loss == 0
+ * under rmse, are not guarded, as there: the non-finite coefficient shows in the outputs.
+ * One launch, thread r owns row r and recomputes the C coefficients from `sums`; no atomics, no allocation, no synchronisation,
+ * nothing read back: the call can be captured into a HIP graph.  R >= 1 and C in 1..8, then space and kind in {0, 1}
+ * (BSMS_E_UNSUPPORTED otherwise, checked in this order before any pointer is looked at); null required pointers and half a
+ * carried pair give BSMS_E_INVALID_ARG; all before any device call. */
+enum { BSMS_LOSS_PHYSICAL = 0, BSMS_LOSS_NORMALIZED = 1 };   /* space */
+enum { BSMS_LOSS_RMSE = 0, BSMS_LOSS_MSE = 1 };              /* kind */
+int bsms_sim_objective_bwd(const float* pred, const float* target, const float* mask, int64_t R, int64_t C, const double* mean,
+                           const double* meansq, const double* std_eps, const double* in_mean /* nullable */,
+                           const double* in_meansq /* nullable */, const double* in_std_eps /* nullable */, const double* sums,
+                           const double* channel_weights /* nullable */, int space, int kind, float w,
+                           const float* g_pred_next /* nullable */, const float* g_norm_in_next /* nullable */,
+                           float* loss_out /* nullable */, float* chan_out /* nullable */, float* g_pred /* nullable */,
+                           float* grad_norm_pred, bsms_stream_t stream);
 
 /* ---------------------------------------------------------------- evaluation: masked error sums ---
  * The reductions behind the reference's evaluation figures -- `Trainer.get_error` (trainer/trainer.py:254-269: per-sample
