@@ -73,6 +73,8 @@ SIGNATURES = {
     "bsms_bsgmp_pos_work_bytes": (c_size_t, [PP, c_int, c_i64, c_i64]),
     "bsms_bsgmp_bwd_pos": (c_int, [PP, PP, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, PP, c_void_p,
                                    c_void_p, c_void_p, PP, c_int, c_void_p, c_void_p, c_void_p]),
+    "bsms_bsgmp_bwd_pos_ev": (c_int, [PP, PP, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, PP, c_void_p,
+                                      c_void_p, c_void_p, PP, c_int, c_int, PP, c_void_p, c_void_p, c_void_p]),
     "bsms_side_lanes_join": (c_int, [c_void_p]),
     "bsms_streams_overlap": (c_int, [c_void_p, c_void_p]),
     "bsms_sim_work_bytes": (c_size_t, [c_i64]),
@@ -86,6 +88,8 @@ SIGNATURES = {
     "bsms_sim_objective_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_int, c_int, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
+    "bsms_sim_input_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_int, c_void_p, c_void_p]),
     "bsms_error_sums_work_bytes": (c_size_t, [c_i64, c_i64]),
     "bsms_error_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "bsms_batch_assemble": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, C.c_double, c_void_p, c_i64, C.c_uint64, C.c_uint64,

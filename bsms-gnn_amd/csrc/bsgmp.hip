@@ -334,6 +334,21 @@ extern "C" int bsms_bsgmp_bwd_ev(const bsms_plan_t* const* plans, const float* c
                         precision, flags, block_done_events, nullptr, nullptr, as_stream(stream));
 }
 
+// bsms_bsgmp_bwd_ev + bsms_bsgmp_bwd_pos in one call: the fused step keeps its deferred join and its bucket events when it also
+// wants the position gradient.  grad_pos == NULL is bsms_bsgmp_bwd_ev, argument checks included.
+extern "C" int bsms_bsgmp_bwd_pos_ev(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
+                                     const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
+                                     const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
+                                     int precision, int flags, void* const* block_done_events, float* grad_pos, void* pos_work,
+                                     bsms_stream_t stream) {
+  if (grad_pos) {
+    BSMS_REQUIRE(p >= 1 && p <= 7, BSMS_E_INVALID_ARG, "bsgmp_bwd_pos_ev: pos_dim=%lld (1..7)", (long long)p);
+    BSMS_REQUIRE(pos_work, BSMS_E_INVALID_ARG, "bsgmp_bwd_pos_ev: grad_pos needs pos_work (bsms_bsgmp_pos_work_bytes)");
+  }
+  return bsgmp_bwd_impl(plans, ew, L, h, pos, grad_out, B, D, p, pos_batch_stride, hidden, params, saved, work, grad_h, grads,
+                        precision, flags, block_done_events, grad_pos, grad_pos ? pos_work : nullptr, as_stream(stream));
+}
+
 namespace {
 int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
                    const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,

@@ -237,6 +237,55 @@ extern "C" int bsms_sim_unroll_bwd(const float* pred, const float* target, const
 
 namespace {
 
+// One step k of the K-step input gradient G = dJ / d in_0 (include/bsms_hip.h: bsms_sim_input_grad), folded into grad_in
+// [R, C+p+1] in the column layout of node_in.  t = float(double(g_norm_in) / std_in) is the way back through the fp64 input
+// normalisation, formed as k_sim_unroll_bwd forms its `through_norm`.  Thread r owns row r, the map of every k_sim_* kernel: a
+// row is at most 17 floats in and 16 out, a wave covers 64 consecutive rows, so every cache line it touches is used in full
+// over the column loop; the launch is glue (launch-bound), not a streaming kernel worth an element-per-lane map.
+__global__ __launch_bounds__(256) void k_sim_input_grad(const float* g_pred, const float* g_norm_in, const float* g_pos,
+                                                        const float* mask, int64_t R, int C, int p, const double* in_mean,
+                                                        const double* in_meansq, const double* in_eps, int first_step,
+                                                        int overwrite, float* grad_in) {
+  const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (r >= R) return;
+  const int W = C + p + 1;
+  const double ie = *in_eps;
+  const float m = mask[r];
+  float* out = grad_in + r * W;
+  for (int c = 0; c <= C; ++c) {
+    const float t = float(double(g_norm_in[r * (C + 1) + c]) / std_eps(in_mean[c], in_meansq[c], ie));
+    float contrib;
+    if (c == C) contrib = t;                                          // node type: every step, every row
+    else if (first_step) contrib = g_pred[r * C + c] + t;             // in_0 is step 0's input on every row
+    else contrib = (m == 0.f) ? t : 0.f;                              // later steps: only the rows that took in_0 again
+    float* o = out + (c < C ? c : W - 1);
+    *o = overwrite ? contrib : *o + contrib;
+  }
+  for (int c = 0; c < p; ++c) {                                       // positions: every step, every row
+    const float contrib = g_pos[r * p + c];
+    out[C + c] = overwrite ? contrib : out[C + c] + contrib;
+  }
+}
+
+}  // namespace
+
+extern "C" int bsms_sim_input_grad(const float* g_pred, const float* g_norm_in, const float* g_pos, const float* mask, int64_t R,
+                                   int64_t C, int64_t p, const double* in_mean, const double* in_meansq,
+                                   const double* in_std_eps_dev, int first_step, int overwrite, float* grad_in,
+                                   bsms_stream_t stream) {
+  BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC && p >= 1 && p <= 7, BSMS_E_UNSUPPORTED, "sim_input_grad: R=%lld C=%lld p=%lld",
+               (long long)R, (long long)C, (long long)p);
+  BSMS_REQUIRE(g_norm_in && g_pos && mask && in_mean && in_meansq && in_std_eps_dev && grad_in, BSMS_E_INVALID_ARG,
+               "sim_input_grad: null argument");
+  BSMS_REQUIRE(!first_step || g_pred, BSMS_E_INVALID_ARG, "sim_input_grad: the first step (k == 0) needs g_pred");
+  hipLaunchKernelGGL(k_sim_input_grad, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), g_pred, g_norm_in, g_pos,
+                     mask, R, (int)C, (int)p, in_mean, in_meansq, in_std_eps_dev, first_step ? 1 : 0, overwrite ? 1 : 0, grad_in);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}
+
+namespace {
+
 // k_sim_unroll_bwd for the family of objectives (include/bsms_hip.h: bsms_sim_objective_bwd).  `sums` = [M | SE[0..C)] in fp64
 // (bsms_error_sums); every thread forms the C per-channel coefficients G * a_c from it in fp64 and rounds each to fp32 once.
 // The carry and the way out through the de-normalisation are those of k_sim_unroll_bwd, op for op.  No guard for M == 0 or

@@ -143,11 +143,14 @@ def global_masked_loss(pred, tar, mask, objective, std, group=None):
 class DataParallel:
     """Wraps a replica: broadcast of parameters at construction, bucketed gradient all-reduce."""
 
-    def __init__(self, model, bucket_bytes=2 << 20, group=None, unroll=1, step_weights=None, detach=False, objective=None):
+    def __init__(self, model, bucket_bytes=2 << 20, group=None, unroll=1, step_weights=None, detach=False, objective=None,
+                 input_grad=False):
         """`unroll` > 1: the loss runs over that many autoregressive steps (step.FusedStep; `step_weights` default 1/unroll,
         `detach` cuts the gradient between the steps).  Only the fused step implements it.
         `objective` (objective.Objective): None reads the optional loss_space / loss_kind / loss_channel_weights of `model.cfg`;
-        without them it is the reference's masked RMSE."""
+        without them it is the reference's masked RMSE.
+        `input_grad`: the fused step also forms the gradient of the loss w.r.t. `node_in` (`engine.fused.input_grad()`, DESIGN.md
+        4.12) -- local to this rank's samples, no collective; only the fused step implements it."""
         from .objective import Objective
         self.model, self.group, self.unroll = model, group, int(unroll)
         if objective is None:
@@ -171,7 +174,12 @@ class DataParallel:
         self.fused = None
         if os.environ.get("BSMS_FUSED_STEP", "1") == "1" and FusedStep.supports(model) and next(model.parameters()).is_cuda:
             self.fused = FusedStep(model, self.grads, group, use_graph=os.environ.get("BSMS_STEP_GRAPH", "0") == "1",   # with unroll > 1: ValueError
-                                   unroll=self.unroll, step_weights=step_weights, detach=detach, objective=self.objective)
+                                   unroll=self.unroll, step_weights=step_weights, detach=detach, objective=self.objective,
+                                   input_grad=input_grad)
+        elif not isinstance(input_grad, bool):
+            raise TypeError(f"DataParallel: input_grad is a bool, got {type(input_grad).__name__}")
+        if input_grad and self.fused is None:
+            raise ValueError("DataParallel: input_grad needs the fused step (a standard BSMS_Simulator on the GPU, BSMS_FUSED_STEP != 0)")
         if self.unroll > 1 and self.fused is None:
             raise ValueError("DataParallel: unroll > 1 needs the fused step (a standard BSMS_Simulator on the GPU, BSMS_FUSED_STEP != 0)")
 

@@ -18,7 +18,11 @@ bit-identical to it, the loss and its gradient agree to fp32 round-off (tests/te
 `unroll=K > 1` trains on K autoregressive steps: K forwards, each with its own saved activations, chained by
 the rollout rule (bsms_sim_epilogue's `next_in`), then K backwards in reverse order; bsms_sim_unroll_bwd carries the gradient
 from step k+1 into step k (or cuts it, `detach=True`), and every step but the last-run-first writes its weight gradients into a
-scratch flat buffer that bsms_grad_accumulate folds into `GradBuckets.flat`."""
+scratch flat buffer that bsms_grad_accumulate folds into `GradBuckets.flat`.
+
+`input_grad=True` also forms the gradient w.r.t. `node_in`: the U-Net backward goes through bsms_bsgmp_bwd_pos_ev
+(the same schedule plus the position kernels), the encoder's backward returns its input gradient at every step, and one
+bsms_sim_input_grad launch per step folds them, with the step's g_pred, into a static [B, N, C+p+1] buffer (`input_grad()`)."""
 import os
 
 import torch
@@ -58,9 +62,12 @@ class _Arena:
 
 
 class FusedStep:
-    def __init__(self, model, grads, group=None, use_graph=False, unroll=1, step_weights=None, detach=False, objective=None):
+    def __init__(self, model, grads, group=None, use_graph=False, unroll=1, step_weights=None, detach=False, objective=None,
+                 input_grad=False):
         """`objective` (objective.Objective): None or the default objective keeps the reference's masked RMSE on the kernels it
-        always ran on; any other runs bsms_error_sums after every forward and bsms_sim_objective_bwd in front of every backward."""
+        always ran on; any other runs bsms_error_sums after every forward and bsms_sim_objective_bwd in front of every backward.
+        `input_grad`: every backward also forms the gradient of the (K-step) loss w.r.t. `node_in` -- state, mesh
+        positions and node type -- into a static [B, N, C+p+1] buffer, handed out by `input_grad()`.  Off: nothing changes."""
         from .model import BSMS_Simulator
         if not isinstance(model, BSMS_Simulator):
             raise TypeError("FusedStep drives a bsms_gnn_amd.BSMS_Simulator")
@@ -78,6 +85,9 @@ class FusedStep:
             raise ValueError(f"FusedStep: {len(step_weights)} step_weights for unroll = {unroll}")
         self.model, self.grads, self.group, self.use_graph = model, grads, group, use_graph
         self.unroll, self.step_weights, self.detach = unroll, step_weights, bool(detach)
+        if not isinstance(input_grad, bool):
+            raise TypeError(f"FusedStep: input_grad is a bool, got {type(input_grad).__name__}")
+        self._input_grad, self._ig_ran = input_grad, False
         from .objective import Objective
         self.objective = (Objective() if objective is None else objective).bind(model.cfg.out_dim)
         self._obj = None if self.objective.is_default else self.objective      # None: the default route, untouched
@@ -184,7 +194,10 @@ class FusedStep:
                      work_obj=u8("work_obj", L.bsms_error_sums_work_bytes(1, R)))
             if self._obj_w is None or self._obj_w.device != dev:
                 self._obj_w = self._obj.weights_tensor(dev)
-        self._shape_key, self._buf, self._graphs = key, b, None
+        if self._input_grad:                          # shared by the K steps: every launch that touches them is on the caller's stream
+            b["ig"] = dict(g_pos=f("g_pos", R, p), grad_in=f("grad_in", B, N, C + p + 1), g_pred=f("g_pred@0", R, C), g_nin=f("g_nin", R, C + 1),
+                           pos_work=u8("pos_work", L.bsms_bsgmp_pos_work_bytes(pl, depth, B, p)))
+        self._shape_key, self._buf, self._graphs, self._ig_ran = key, b, None, False
         return b
 
     def _f64(self, name, dev, *shape):
@@ -241,6 +254,9 @@ class FusedStep:
         work = b["work"]
         no = m._targetNormalizer
         ck = _abi.check
+        ig = b["ig"] if self._input_grad else None
+        if ig is not None and chain is None:          # the single step as a chain of one: w = 1, nothing carried, g_pred kept
+            chain = dict(w=1.0, tabs=t, g_pred_next=None, g_nin_next=None, g_pred=ig["g_pred"], grad_x=ig["g_nin"], first_step=1, overwrite=1)
         if self._obj is not None:
             from .objective import KINDS, SPACES
             ni, o = m._inputNormalizer, self._obj
@@ -267,12 +283,24 @@ class FusedStep:
         ewp, keep = _abi.ptr_array([e.data_ptr() for e in ews])
         # BSMS_BWD_DEFER_JOIN: the weight gradients of the last (level-0) block are still running on the engine's side
         # streams (~0.2 ms on half the chip) while the encoder's backward -- own scratch, own gradient slots -- runs here
-        ck(L.bsms_bsgmp_bwd_ev(b["pl"], ewp, b["depth"], b["h0"].data_ptr(), b["pos"].data_ptr(), b["gh1"].data_ptr(), B, D, p, N * p, H,
-                               t["proc"][0][0], b["s_proc"].data_ptr(), work.data_ptr(), b["gh0"].data_ptr(), t["proc"][1][0],
-                               PRECISIONS[b["prec"]], 1, None if events is None else events[0], s), "bsms_bsgmp_bwd")
+        if ig is None:
+            ck(L.bsms_bsgmp_bwd_ev(b["pl"], ewp, b["depth"], b["h0"].data_ptr(), b["pos"].data_ptr(), b["gh1"].data_ptr(), B, D, p, N * p, H,
+                                   t["proc"][0][0], b["s_proc"].data_ptr(), work.data_ptr(), b["gh0"].data_ptr(), t["proc"][1][0],
+                                   PRECISIONS[b["prec"]], 1, None if events is None else events[0], s), "bsms_bsgmp_bwd")
+        else:                                         # the same schedule, plus the position kernels on this stream (g_pos is complete on return)
+            ck(L.bsms_bsgmp_bwd_pos_ev(b["pl"], ewp, b["depth"], b["h0"].data_ptr(), b["pos"].data_ptr(), b["gh1"].data_ptr(), B, D, p, N * p, H,
+                                       t["proc"][0][0], b["s_proc"].data_ptr(), work.data_ptr(), b["gh0"].data_ptr(), t["proc"][1][0],
+                                       PRECISIONS[b["prec"]], 1, None if events is None else events[0], ig["g_pos"].data_ptr(),
+                                       ig["pos_work"].data_ptr(), s), "bsms_bsgmp_bwd_pos")
         ck(L.bsms_mlp_bwd(b["norm_in"].data_ptr(), b["gh0"].data_ptr(), R, C + 1, D, D, H, 1, t["enc"][0][0], b["s_enc"].data_ptr(),
                           b["work_enc"].data_ptr(), None if chain is None else _ptr(chain["grad_x"]), t["enc"][1][0], s),
            "bsms_mlp_bwd(encode)")
+        if ig is not None:                            # fold this step into dJ / d node_in: own buffers, no `work`, no `grads` -- before the join
+            ni = m._inputNormalizer
+            ck(L.bsms_sim_input_grad(chain["g_pred"].data_ptr(), chain["grad_x"].data_ptr(), ig["g_pos"].data_ptr(), mask.data_ptr(), R, C, p,
+                                     ni._E_data.data_ptr(), ni._E_data_squared.data_ptr(), ni.std_eps.data_ptr(), chain["first_step"],
+                                     chain["overwrite"], ig["grad_in"].data_ptr(), s), "bsms_sim_input_grad")
+            self._ig_ran = True
         ck(L.bsms_side_lanes_join(s), "bsms_side_lanes_join")
 
     # ------------------------------------------------------------------------------------------------ the step
@@ -374,10 +402,11 @@ class FusedStep:
         for k in range(K - 1, -1, -1):
             bk, last = steps[k], k == K - 1
             carry = not last and not self.detach
+            keep = self._input_grad or (k > 0 and not self.detach)      # input_grad: g_pred and the encoder's grad_x of EVERY step
             chain = dict(w=self.step_weights[k], tabs=self._tabs if last else self._tabs_scratch,
                          g_pred_next=b["g_pred"][(k + 1) & 1] if carry else None, g_nin_next=b["g_nin"] if carry else None,
-                         g_pred=b["g_pred"][k & 1] if (k > 0 and not self.detach) else None,
-                         grad_x=b["g_nin"] if (k > 0 and not self.detach) else None)
+                         g_pred=b["g_pred"][k & 1] if keep else None, grad_x=b["g_nin"] if keep else None,
+                         first_step=int(k == 0), overwrite=int(last))
             self._backward(bk, tars[k], mask, ews, B, N, chain=chain)          # ends with bsms_side_lanes_join
             if not last:
                 _abi.check(L.bsms_grad_accumulate(self.grads.flat.data_ptr(), self._gscratch.data_ptr(), n, 0, s), "bsms_grad_accumulate")
@@ -388,6 +417,17 @@ class FusedStep:
     def predictions(self):
         """The K predictions of the last step, [B,N,C] each (static buffers: clone to keep)."""
         return [bk["pred"] for bk in self._buf["steps"]] if self.unroll > 1 else [self._buf["pred"]]
+
+    def input_grad(self):
+        """dJ / d node_in of the last call, [B, N, C+p+1] in the column layout of `node_in` ([1, rows, .] for variable meshes): the
+        gradient of the weighted K-step loss w.r.t. the initial state, the mesh positions and the node type.  A
+        static buffer, overwritten by the next call: clone to keep.  Under data parallelism it covers this rank's samples, with the
+        global loss coefficient."""
+        if not self._input_grad:
+            raise ValueError("FusedStep.input_grad: the step was built without input_grad=True")
+        if not self._ig_ran:
+            raise RuntimeError("FusedStep.input_grad: the step has not run yet")
+        return self._buf["ig"]["grad_in"]
 
     def step_losses(self):
         """Device [K]: the loss (the masked RMSE by default, else the objective) of every step of the last call, unweighted (a copy)."""
@@ -555,3 +595,30 @@ class FusedStep:
         if world > 1:
             dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         return b["loss"][0].clone()
+
+
+def input_gradient(model, data, consistent=True, later_targets=None, step_weights=None, detach=False, objective=None):
+    """Sensitivity of a (rollout) objective of a trained `BSMS_Simulator`: returns `(loss, grad_node_in)`, the weighted K-step loss
+    and its gradient w.r.t. `node_in` -- initial state, mesh positions, node type; [B, N, C+p+1], or [1, rows, C+p+1] for variable
+    meshes.  K = 1 without `later_targets`, else `later_targets.shape[0] + 1`; `step_weights`, `detach` and
+    `objective` are FusedStep's.  The gradient is a clone: it stays valid after the next call.
+
+    A convenience over a `FusedStep(input_grad=True)` that is built once per (K, step_weights, detach, objective) and cached on the
+    model, together with ONE `GradBuckets` for all of them.  The parameters themselves are left untouched.  Their `.grad`s are
+    written as `GradBuckets` writes them: after the first call every `p.grad` is a view into the flat gradient buffer and holds
+    the weight gradients of the last call (the backward forms them anyway).  A model that a `Trainer` or `DataParallel` drives
+    owns its `GradBuckets` already: take `engine.fused.input_grad()` there (`DataParallel(input_grad=True)`) instead."""
+    from .dp import GradBuckets
+    from .objective import Objective
+    K = 1 if later_targets is None else int(later_targets.shape[0]) + 1
+    objective = Objective() if objective is None else objective
+    key = (K, None if step_weights is None else tuple(float(w) for w in step_weights), bool(detach), objective)
+    cache = model.__dict__.setdefault("_bsms_input_grad_steps", {})
+    step = cache.get(key)
+    if step is None:
+        if "grads" not in cache:
+            cache["grads"] = GradBuckets(list(model.parameters()))
+        step = cache[key] = FusedStep(model, cache["grads"], unroll=K, step_weights=step_weights, detach=detach, objective=objective,
+                                      input_grad=True)
+    loss = step(data, consistent, later_targets)
+    return loss, step.input_grad().clone()

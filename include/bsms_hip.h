@@ -309,6 +309,20 @@ int bsms_bsgmp_bwd_pos(const bsms_plan_t* const* plans, const float* const* ew, 
                        const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
                        const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
                        int precision, float* grad_pos, void* pos_work, bsms_stream_t stream);
+/* bsms_bsgmp_bwd_ev + the position gradient of bsms_bsgmp_bwd_pos in ONE call: `flags`, `block_done_events`, `grad_pos` and
+ * `pos_work` together, each with the meaning it has in the entry it comes from.  grad_pos = NULL is exactly bsms_bsgmp_bwd_ev
+ * (pos_work is ignored); flags = 0 with block_done_events = NULL is exactly bsms_bsgmp_bwd_pos.  With grad_pos: p in 1..7 and a
+ * non-null pos_work, else BSMS_E_INVALID_ARG, before anything else is looked at.
+ * The position kernels of a block run on the caller's stream before a later block reuses the scratch set, also under
+ * BSMS_BWD_DEFER_JOIN: a block's position kernel and the adjoint of the position pooling are queued on `stream` inside the
+ * block, behind its gradient strand; only the weight gradients go to the side lanes, and the deferred join leaves nothing but
+ * those outstanding.  So `grad_pos` -- like `grad_h` -- is complete in stream order when the call returns, and `pos_work` may be
+ * reused by the next call on the same stream without bsms_side_lanes_join in between. */
+int bsms_bsgmp_bwd_pos_ev(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
+                          const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
+                          const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
+                          int precision, int flags, void* const* block_done_events, float* grad_pos /* nullable */,
+                          void* pos_work /* nullable with grad_pos */, bsms_stream_t stream);
 int bsms_side_lanes_join(bsms_stream_t stream);
 /* Do two streams overlap?  HIP places its streams on a few hardware queues (four by default, by reference counts at creation time) and
  * two streams on one queue run in order, whatever their flags.  Returns 1 if work queued on `b` can overtake work queued on `a`, 0 if not
@@ -397,6 +411,30 @@ int bsms_sim_objective_bwd(const float* pred, const float* target, const float* 
                            const float* g_pred_next /* nullable */, const float* g_norm_in_next /* nullable */,
                            float* loss_out /* nullable */, float* chan_out /* nullable */, float* g_pred /* nullable */,
                            float* grad_norm_pred, bsms_stream_t stream);
+/* The gradient of the K-step objective w.r.t. its INPUT, G = dJ / d in_0: one launch folds step k into
+ * `grad_in` [R, C+p+1], which has the column layout of node_in = [state (C) | mesh_pos (p) | node_type].  in_0 reaches step k
+ * through its positions and node type on every row, through its state on every row at k = 0, and at k > 0 through its state
+ * on the rows with mask == 0 only (the rollout rule put in_0 there; the other rows took pred_{k-1}, and their gradient went
+ * into the carry of bsms_sim_unroll_bwd).  With t[r,c] = float(double(g_norm_in[r,c]) / std_in[c]), c = 0..C, std_in formed from
+ * in_mean / in_meansq / in_std_eps as everywhere in this section:
+ *   state columns c < C:   first_step ? g_pred[r,c] + t[r,c]  :  (mask[r] == 0 ? t[r,c] : 0)
+ *   position columns:      g_pos[r,:]
+ *   type column:           t[r,C]
+ *   grad_in = overwrite ? contribution : grad_in + contribution            (fp32)
+ * `g_pred` [R,C] is what bsms_sim_unroll_bwd / bsms_sim_objective_bwd wrote for this step (read with first_step only: it is 0 on
+ * rows with mask == 0, so the k = 0 line needs no row condition), `g_norm_in` [R,C+1] the grad_x of this step's encoder
+ * backward, `g_pos` [R,p] the grad_pos of its U-Net backward.  Call it once per step in the order k = K-1 .. 0, with `overwrite`
+ * on the first call (stale contents of grad_in, NaNs included, never reach the result) and `first_step` on the last; K = 1 is
+ * one call with both.  Per element: one fp64 division rounded once to fp32, at most two fp32 additions.
+ * One launch, thread r owns row r; no atomics, no allocation, no synchronisation, nothing read back: the call can be captured
+ * into a HIP graph.  Checked in this order, all before any device call: R >= 1, C in 1..8 and p in 1..7 (BSMS_E_UNSUPPORTED
+ * otherwise, before any pointer is looked at); then null required pointers -- a null g_pred with first_step is one of them --
+ * give BSMS_E_INVALID_ARG. */
+int bsms_sim_input_grad(const float* g_pred /* [R,C], required iff first_step */, const float* g_norm_in /* [R,C+1] */,
+                        const float* g_pos /* [R,p] */, const float* mask /* [R] */, int64_t R, int64_t C, int64_t p,
+                        const double* in_mean, const double* in_meansq, const double* in_std_eps,
+                        int first_step /* k == 0 */, int overwrite /* the launch of k = K-1 */,
+                        float* grad_in /* [R, C+p+1] */, bsms_stream_t stream);
 
 /* ---------------------------------------------------------------- evaluation: masked error sums ---
  * The reductions behind the reference's evaluation figures -- `Trainer.get_error` (trainer/trainer.py:254-269: per-sample
