@@ -303,7 +303,7 @@ def test_sim_unroll_bwd_kernel(eng, C):
 
 
 # ------------------------------------------------------------------------------------------------ 7: bsms_grad_accumulate alone
-@pytest.mark.parametrize("n", [1, 1023, (1 << 20) + 3])
+@pytest.mark.parametrize("n", [1, 1023, (1 << 20) + 3, 4 * 2048 * 256 + 4 * 300 + 3])   # the last: past the 2048 x 256 grid stride of float4s
 def test_grad_accumulate_kernel(eng, n):
     L, s = eng._abi.lib(), torch.cuda.current_stream().cuda_stream
     gen = torch.Generator().manual_seed(n)
