@@ -130,7 +130,7 @@ int make_shape(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int
 
 // parameters of block k: 4 (H + 1) pointers (mlp_node then mlp_edge), blocks ordered down 0..L-1, bottom, up 0..L-1
 inline const float* const* block(const float* const* params, int k, int H) { return params + size_t(k) * 4 * (H + 1); }
-inline float* const* block(float* const* grads, int k, int H) { return grads + size_t(k) * 4 * (H + 1); }
+inline float* const* block(float* const* grads, int k, int H) { return grads ? grads + size_t(k) * 4 * (H + 1) : nullptr; }   // null: every MLP frozen
 
 }  // namespace
 
@@ -273,8 +273,12 @@ extern "C" int bsms_side_lanes_join(bsms_stream_t stream) {
   int rc;
   hipStream_t st = as_stream(stream);
   if ((rc = side_lane(&lane0, 0, st)) || (rc = side_lane(&lane1, 1, st))) return rc;
-  for (int slot = 0; slot < 2; ++slot)   // a slot nobody marked is an event that was never recorded: the wait is a no-op
-    if ((!gmp_marks_chained() && (rc = side_wait_mark(lane0, slot, st))) || (rc = side_wait_mark(lane1, slot, st))) return rc;
+  // Only marks that are still open are waited for (side_wait_open_mark): a slot nobody has marked since its last wait holds a stale record,
+  // possibly from outside an ongoing graph capture.  Lane 1's mark of a block covers lane 0's (side_mark_chain); a mark lane 0 got on
+  // its own and that no block has covered since -- a deferred bsms_mlp_bwd_ex in front of a U-Net whose blocks are all frozen and
+  // run no lane -- is waited for as well.  With nothing frozen: the two waits on lane 1 this always issued.
+  for (int slot = 0; slot < 2; ++slot)
+    if ((rc = side_wait_open_mark(lane0, slot, st)) || (rc = side_wait_open_mark(lane1, slot, st))) return rc;
   return BSMS_OK;
 }
 
@@ -360,8 +364,16 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
   if (rc) return rc;
   BSMS_REQUIRE(precision == BSMS_F32 || precision == BSMS_BF16 || precision == BSMS_BF16_NODES, BSMS_E_UNSUPPORTED, "bsgmp_bwd: precision %d", precision);
   s.prec = precision;
-  BSMS_REQUIRE(h && pos && grad_out && params && saved && work && grad_h && grads && (ew || L == 0), BSMS_E_INVALID_ARG,
+  BSMS_REQUIRE(h && pos && grad_out && params && saved && work && grad_h && (ew || L == 0), BSMS_E_INVALID_ARG,
                "bsgmp_bwd: null argument");
+  // frozen MLPs: every block's entries are checked here, before the first launch of the call; lanes[k] = block k
+  // (storage order) has a weight gradient left and so runs its side lanes
+  bool lanes[2 * kMaxLevels + 1];
+  for (int k = 0; k <= 2 * L; ++k) {
+    bool nlive, elive;
+    if ((rc = gmp_check_grads(block(grads, k, hidden), hidden, precision, "bsgmp_bwd", &nlive, &elive))) return rc;
+    lanes[k] = nlive || elive;
+  }
   Work w = carve_work(work, s);
   Saved v = carve_saved(const_cast<void*>(saved), s, true);
   // position gradients (bsms_bsgmp_bwd_pos): gp[l] of level l collects its up block, the adjoint of restrict_l applied to
@@ -397,14 +409,18 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
     if (!own && marked[slot] && ((!gmp_marks_chained() && (r = side_wait_mark(lane0, slot, st))) || (r = side_wait_mark(lane1, slot, st)))) return r;
     const int order = nblk;   // position of this block in the backward's execution order
     ++nblk;
-    marked[slot] = true;
+    if (lanes[k]) marked[slot] = true;   // a block without lanes marks nothing
     if ((r = gmp_bwd_core(plans[level], x, pos_l[level], g_in, B, D, p, pstride_l[level], hidden, block(params, k, hidden), v.gmp[k],
                           own ? own : (slot ? w.gmp_b : w.gmp), gx, block(grads, k, hidden), slot, st, precision, gp[level],
                           pw.scratch, pos_acc))) return r;
     // Gradient-bucket hand-off (bsms_bsgmp_bwd_ev): lane 1's mark of this block covers lane 0's (gmp_marks_chained) and both
     // lanes are in-order streams, so an event recorded on lane 1 HERE completes when every weight gradient of this block,
     // of the blocks before it and of anything queued on the lanes earlier (a deferred bsms_mlp_bwd_ex) has been written.
-    if (block_done_events && block_done_events[order]) {
+    // A block whose MLPs are both frozen ran no lane: its entry is recorded on the caller's stream (the block itself is done; it has
+    // no weight gradient, and the event says nothing about the lanes).
+    if (block_done_events && block_done_events[order] && !lanes[k]) {
+      BSMS_HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(block_done_events[order]), st));
+    } else if (block_done_events && block_done_events[order]) {
       if (!gmp_marks_chained() && (r = side_wait_mark(lane0, slot, lane1->stream))) return r;
       BSMS_HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(block_done_events[order]), lane1->stream));
     }

@@ -203,7 +203,10 @@ struct WgradJob {
 };
 constexpr int kMaxWgradJobs = 20;
 size_t wgrad_work_bytes(int D, int njobs);
-int launch_wgrad(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t s);
+// `skip_mask` (bit j = job j): jobs of a frozen MLP -- not run, but counted when the launch shape is chosen, so that the jobs that remain are
+// partitioned (and rounded) exactly as in the launch with nothing frozen; a launch whose jobs are all skipped is not issued
+int launch_wgrad(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t s, unsigned skip_mask = 0);
+static_assert(kMaxWgradJobs <= 32, "launch_wgrad: one bit per job");
 
 // small-side weight gradients: out[s*os + f*of] = sum_r G[r][f] * S[r][s],  s < S (<= 8)
 struct SmallWgradArgs {

@@ -428,7 +428,11 @@ void k_edge_fwd(ChainFwdArgs a) {
   if (SAVE) flush_bounds(a.amax, kMaxStages + 1, brow, wave, lane);
 }
 
-template <int NB, int RB, bool LONE = false>
+// STORE = false (the edge MLP is frozen, gmp.hip): the layer gradients gstore[0 .. nstage-1] have no reader (only the weight-gradient
+// jobs read them) and are not written -- stage_rb<SAVE = 0>, the path of the inference forward with its shorter VALU step table;
+// the last gradient, gstore[nstage] = gE[0], is stored as always (the scatter and the position gradient read it).  Same products
+// in the same order: the gradients are bit-identical to the storing build's.
+template <int NB, int RB, bool LONE = false, bool STORE = true>
 __global__ __launch_bounds__(kChainMaxThreads) __attribute__((amdgpu_waves_per_eu(LONE ? 2 : EdgeTile<NB, RB>::waves_per_eu)))
 void k_edge_bwd(ChainBwdArgs a) {
   constexpr int D = NB * 16, W = mask_words<NB>();
@@ -486,7 +490,7 @@ void k_edge_bwd(ChainBwdArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) g[rb][t][r] = rs[rb] * (g[rb][t][r] - m1 - acc[rb][t][r] * m2);
     }
-    float* pending = a.gstore[0];   // uniform, non-null (launcher): the gradient entering a stage is stored inside it
+    float* pending = a.gstore[0];   // uniform, non-null when STORE (launcher): the gradient entering a stage is stored inside it
     for (int k = 0; k < a.nstage; ++k) {
       unsigned mbits[RB][W];   // ReLU sign bits of the activation that masks this stage's output, loaded ahead of the stage
 #pragma unroll
@@ -495,11 +499,11 @@ void k_edge_bwd(ChainBwdArgs a) {
         for (int w = 0; w < W; ++w)
           mbits[rb][w] = reinterpret_cast<const unsigned*>(a.mask[k] + pad_rows(a.R) * D)[rowc[rb] * (4 * W) + lg * W + w];
 #ifdef BSMS_EXPERIMENTS   // ablation bound of the fused dataflow (profiles/r05_fusion_bound.txt): the layer gradients of every tile land on tile 0
-      float* const gtile = pending + int64_t(a.ablate ? 0 : tile) * (tile_rows * D);
+      float* const gtile = STORE ? pending + int64_t(a.ablate ? 0 : tile) * (tile_rows * D) : nullptr;
 #else
-      float* const gtile = pending + int64_t(tile) * (tile_rows * D);
+      float* const gtile = STORE ? pending + int64_t(tile) * (tile_rows * D) : nullptr;
 #endif
-      stage_rb<NB, RB, 1, false, true, 1, LONE>(acc, g, ring, slot, lane, gtile, nullptr, off, moff, brow, k);
+      stage_rb<NB, RB, STORE ? 1 : 0, false, true, 1, LONE>(acc, g, ring, slot, lane, gtile, nullptr, off, moff, brow, k);
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb)
 #pragma unroll

@@ -166,7 +166,7 @@ bool launch_edge_fwd(ChainFwdArgs& a, hipStream_t s, int& rc) {
   return true;
 }
 
-template <int NB, int RB>
+template <int NB, int RB, bool STORE>
 int launch_edge_bwd_t(ChainBwdArgs& a, hipStream_t s) {
   const int cw = pick_edge_waves<NB, RB>(a.R);
   a.ntiles = (int)ceil_div(a.R, 16 * RB * cw);
@@ -176,19 +176,24 @@ int launch_edge_bwd_t(ChainBwdArgs& a, hipStream_t s) {
   const size_t lds = Ring<NB>::lds_bytes(a.nring);
   static const int lone = knob("BSMS_EDGE_LONE", 1);
   if (lone && a.ntiles <= device_cu_count())   // see launch_edge_fwd_t
-    return launch_dyn_lds<k_edge_bwd<NB, RB, true>>("edge_bwd", "single-round build", grid, threads, lds, ring_lds_max<NB>(), a, s);
-  return launch_dyn_lds<k_edge_bwd<NB, RB>>("edge_bwd", nullptr, grid, threads, lds, ring_lds_max<NB>(), a, s);
+    return launch_dyn_lds<k_edge_bwd<NB, RB, true, STORE>>("edge_bwd", STORE ? "single-round build" : "single-round no-store build", grid, threads, lds, ring_lds_max<NB>(), a, s);
+  return launch_dyn_lds<k_edge_bwd<NB, RB, false, STORE>>("edge_bwd", STORE ? nullptr : "no-store build", grid, threads, lds, ring_lds_max<NB>(), a, s);
 }
 
 template <int NB>
 bool launch_edge_bwd(ChainBwdArgs& a, hipStream_t s, int& rc) {
   if (a.bf16 || a.nstage < 1 || a.store_mode != 1 || edge_rb_mode() == 0 || a.R >= (int64_t(1) << 31)) return false;
-  for (int k = 0; k <= a.nstage; ++k)
-    if (!a.gstore[k] || (k < a.nstage && !a.mask[k])) return false;
+  // the layer gradients gstore[0 .. nstage-1]: all kept, or none (a frozen edge MLP: the no-store build; tile, ring and single-round
+  // choices are the storing launch's).  The last gradient, gstore[nstage], always has a reader.
+  if (!a.gstore[a.nstage]) return false;
+  const bool store = a.gstore[0] != nullptr;
+  for (int k = 0; k < a.nstage; ++k)
+    if ((a.gstore[k] != nullptr) != store || !a.mask[k]) return false;
   constexpr int RBIG = NB == 8 ? 2 : 1;
   bool big = RBIG == 2 && a.R >= int64_t(device_cu_count()) * 16 * edge_compute_waves<NB>();   // see launch_edge_fwd
   if (edge_rb_mode() > 0) big = RBIG == 2 && edge_rb_mode() == 2;
-  rc = big ? launch_edge_bwd_t<NB, RBIG>(a, s) : launch_edge_bwd_t<NB, 1>(a, s);
+  if (store) rc = big ? launch_edge_bwd_t<NB, RBIG, true>(a, s) : launch_edge_bwd_t<NB, 1, true>(a, s);
+  else rc = big ? launch_edge_bwd_t<NB, RBIG, false>(a, s) : launch_edge_bwd_t<NB, 1, false>(a, s);
   return true;
 }
 
@@ -293,7 +298,8 @@ int launch_fwd_n(int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s
 
 // Which kernel runs a backward chain, first match wins:
 //   1. the feature-split kernel (NB = 8, fp32, at most kFsMaxRowsBwd rows);
-//   2. the pipelined edge kernel (launch_edge_bwd: NB = 8 / 16, fp32 edge MLP in its production configuration);
+//   2. the pipelined edge kernel (launch_edge_bwd: NB = 8 / 16, fp32 edge MLP in its production configuration; its no-store
+//      build when the layer gradients gstore[0 .. nstage-1] are all null);
 //   3. the bf16 variant (edge MLP; node MLP of BSMS_BF16_NODES; NB = 8 / 16; bf16 anywhere else is an error);
 //   4. the single-round (LONE) variant, NB >= 8, when the launch fits one workgroup per CU;
 //   5. the ring kernel.

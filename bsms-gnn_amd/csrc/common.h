@@ -46,6 +46,7 @@ struct SideLane {
   hipStream_t stream = nullptr;
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;
   hipEvent_t done_ev[2] = {nullptr, nullptr};   // "everything queued on the lane up to here has run", two slots
+  bool uncovered[2] = {false, false};           // the slot has been marked and neither waited for nor covered by a chained mark since
 };
 constexpr int kSideLanes = 2;
 int side_lane(SideLane** out, int which, hipStream_t caller);   // for the current device; `which` < kSideLanes; `caller`: see plan.hip (capture)
@@ -58,6 +59,12 @@ int side_join(SideLane* lane, hipStream_t main);     // main waits for side
 int side_mark(SideLane* lane, int slot);
 int side_wait_mark(SideLane* lane, int slot, hipStream_t main);
 int side_mark_chain(SideLane* a, SideLane* b, int slot);   // b's mark covers a's: wait for b only
+// side_wait_mark, but only if the lane's `slot` holds an OPEN mark: one that no wait and no later chained mark covers yet (a deferred
+// bsms_mlp_bwd_ex marks lane 0 alone; the U-Net blocks behind it normally cover that mark -- unless they are all frozen and run no
+// lane).  Test and wait are one critical section.  SideLane::uncovered is HOST state: it follows the order of the calls on the host,
+// not stream order, and is shared by every caller of the device like the lanes themselves.  A call that fails between a mark and its
+// join leaves the flag set; the next bsms_side_lanes_join then waits for that (recorded) event once more, which is harmless.
+int side_wait_open_mark(SideLane* lane, int slot, hipStream_t main);
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Per-DEVICE launch state: hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the device that is current
@@ -120,6 +127,10 @@ int gmp_fwd_core(const bsms_plan* plan, const float* x, const float* pos, int64_
                  void* packs_base, bool do_prepack, const float* resid2, hipStream_t stream, int precision = BSMS_F32);
 // `defer_slot` < 0: the side lanes are joined before returning (ABI semantics).  0/1: they are only MARKED in that slot;
 // the caller joins later with side_wait_mark on both lanes and must not touch `work` or read `grads` before that.
+// gmp.hip: the `grads` table of one block: 2 (H + 1) node-MLP entries, then 2 (H + 1) edge-MLP entries; each group
+// all there or all null (the MLP is frozen), `grads` == NULL = both frozen.  BSMS_E_INVALID_ARG for a partly null group,
+// BSMS_E_UNSUPPORTED for null entries in a bf16 precision.  A host check: nothing is launched.
+int gmp_check_grads(float* const* grads, int hidden, int precision, const char* who, bool* node_live, bool* edge_live);
 bool gmp_marks_chained();   // gmp.hip: waiting for lane 1's mark of a slot is enough
 int gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, const float* grad_out, int64_t B, int64_t D,
                  int64_t p, int64_t pos_bstride, int hidden, const float* const* params, const void* saved, void* work,

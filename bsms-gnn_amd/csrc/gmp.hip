@@ -185,7 +185,28 @@ int check_gmp(const bsms_plan_t* plan, int64_t B, int64_t D, int64_t p, int H, c
   return BSMS_OK;
 }
 
+// the 2 (H + 1) gradient entries of one MLP: 1 all there, 0 all null (the MLP is frozen), -1 some of each
+int grads_state(float* const* g, int n) {
+  if (!g) return 0;
+  int live = 0;
+  for (int i = 0; i < n; ++i) live += g[i] != nullptr;
+  return live == n ? 1 : (live == 0 ? 0 : -1);
+}
+
 }  // namespace
+
+// Frozen MLPs: which of a block's two MLPs get their weight gradients.  A host check, before any launch.
+int bsms::gmp_check_grads(float* const* grads, int H, int precision, const char* who, bool* node_live, bool* edge_live) {
+  const int n = 2 * (H + 1);
+  const int ns = grads_state(grads, n), es = grads_state(grads ? grads + n : nullptr, n);
+  BSMS_REQUIRE(ns >= 0 && es >= 0, BSMS_E_INVALID_ARG, "%s: the gradient entries of the %s MLP are partly null (an MLP is frozen as a whole: all "
+               "%d entries null, or none)", who, ns < 0 ? "node" : "edge", n);
+  BSMS_REQUIRE(precision == BSMS_F32 || (ns == 1 && es == 1), BSMS_E_UNSUPPORTED, "%s: null gradient entries (a frozen MLP) need the fp32 "
+               "precision: the fused edge backward of the bf16 precisions forms its weight gradients on chip", who);
+  *node_live = ns == 1;
+  *edge_live = es == 1;
+  return BSMS_OK;
+}
 
 // =================================================================================== GMP entries
 #ifdef BSMS_EXPERIMENTS
@@ -413,12 +434,15 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
   if (rc) return rc;
   const bool bf = precision != BSMS_F32, bfn = precision == BSMS_BF16_NODES;
   BSMS_REQUIRE(!bf || ((D == 128 || D == 256) && p <= 3), BSMS_E_UNSUPPORTED, "gmp_bwd: bf16 precision needs D = 128 / 256 and pos_dim <= 3");
-  BSMS_REQUIRE(x && pos && grad_out && params && saved && work && grad_x && grads, BSMS_E_INVALID_ARG,
-               "gmp_bwd: null argument");
+  BSMS_REQUIRE(x && pos && grad_out && params && saved && work && grad_x, BSMS_E_INVALID_ARG, "gmp_bwd: null argument");
+  // frozen MLPs: `nlive` / `elive` = the node / edge MLP gets its weight gradients.  Nothing that only serves a frozen MLP's dW / db
+  // is launched, and the backward chains do not store the layer gradients that only those launches read
+  bool nlive = true, elive = true;
+  if ((rc = gmp_check_grads(grads, H, precision, "gmp_bwd", &nlive, &elive))) return rc;
   const int64_t N = plan->N, E = plan->E;
   const int nl = H + 1;
-  float* const* gn = grads;
-  float* const* ge = grads + 2 * nl;
+  float* const* gn = nlive ? grads : nullptr;
+  float* const* ge = elive ? grads + 2 * nl : nullptr;
   const int ldE0 = int(2 * D + p + 1);
   const bool fused = use_edge_fused(D, H, precision);
   GmpSaved sv = carve_gmp_saved(const_cast<void*>(saved), B, N, E, D, H, true, nullptr, bf, bfn, fused);
@@ -430,17 +454,17 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
     ChainBwdArgs a{};
     a.R = B * N; a.dy = grad_out; a.yln = sv.n_yln; a.rstd = sv.n_rstd; a.store_mode = 1;
     a.nstage = H;
-    a.gstore[0] = wk.gN[H];
+    a.gstore[0] = nlive ? wk.gN[H] : nullptr;   // frozen: no gN[l] has a reader (dx / dx2 leave the heads from registers)
     for (int k = 0; k < H; ++k) {
       a.wpt[k] = reinterpret_cast<const float4*>(sv.n_wt[H - k]);
       a.mask[k] = sv.n_act[H - k - 1];
-      a.gstore[k + 1] = wk.gN[H - k - 1];
+      a.gstore[k + 1] = nlive ? wk.gN[H - k - 1] : nullptr;
     }
     a.wh0 = reinterpret_cast<const float4*>(sv.n_w0xt);
     a.wh1 = reinterpret_cast<const float4*>(sv.n_w0at);
     a.dx = grad_x; a.dx2 = wk.daggr; a.dres = grad_out;
     a.bf16 = bfn;
-    if (g_node_bf3 < 2) {
+    if (g_node_bf3 < 2 && nlive) {   // (only weight-gradient jobs read the bounds)
       if (!bfn) for (int k = 0; k <= H; ++k) a.gmax[k] = sv.bound + size_t(24 + k) * kBoundWidth;
       else a.gmax[H] = sv.bound + size_t(24 + H) * kBoundWidth;   // BSMS_BF16_NODES: only gN[0] (fp32) feeds an fp32 weight-gradient job
     }
@@ -464,14 +488,15 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
     a.dst = plan->dst; a.E = (int32_t)E; a.N = (int32_t)N;
     a.bf16 = bf;
     a.nstage = H;
-    a.gstore[0] = wk.gE[H];
+    a.gstore[0] = elive ? wk.gE[H] : nullptr;   // frozen: gE[1..H] have no reader; gE[0] keeps two (the scatter, the position gradient)
     for (int k = 0; k < H; ++k) {
       a.wpt[k] = reinterpret_cast<const float4*>(sv.e_wt[H - k]);
       a.mask[k] = sv.e_act[H - k - 1];
-      a.gstore[k + 1] = wk.gE[H - k - 1];
+      a.gstore[k + 1] = (elive || k + 1 == H) ? wk.gE[H - k - 1] : nullptr;
     }
-    if (!bf) for (int k = 0; k <= (g_node_bf3 ? H - 1 : H); ++k) a.gmax[k] = sv.bound + size_t(16 + k) * kBoundWidth;   // gE[0] feeds only the projections' jobs
-    else if (!g_node_bf3) a.gmax[H] = sv.bound + size_t(16 + H) * kBoundWidth;   // bf16 precision: only gE[0] (fp32 scatter sums dPs / dPd feed fp32 weight-gradient jobs)
+    // (a frozen edge MLP notes no bounds: the jobs that read them, the projections' included, are gone)
+    if (elive && !bf) for (int k = 0; k <= (g_node_bf3 ? H - 1 : H); ++k) a.gmax[k] = sv.bound + size_t(16 + k) * kBoundWidth;   // gE[0] feeds only the projections' jobs
+    else if (elive && !g_node_bf3) a.gmax[H] = sv.bound + size_t(16 + H) * kBoundWidth;   // bf16 precision: only gE[0] (fp32 scatter sums dPs / dPd feed fp32 weight-gradient jobs)
     a.ablate = (g_debug_flags & 2048) ? 1 : 0;   // experiments: bit 11 = no stream of gE[1..H] (with bits 0 and 10: the traffic a fused backward would not have)
     if ((rc = launch_chain_bwd((int)D, G_EDGE_LN, F_NONE, a, s))) return rc;
   }
@@ -482,18 +507,22 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
   // They touch disjoint outputs; main joins the side stream before returning, so callers see ordinary semantics.
   // (Forking the node-layer gradients earlier, against the edge backward chain, measured SLOWER: two MFMA-bound
   // kernels contend; an MFMA-bound kernel against HBM-bound ones is the pairing that pays: +5.6 % steps/s.)
+  // A lane with nothing to run (frozen MLPs) is neither forked nor joined.
   SideLane* lane = nullptr;
   const bool overlap = !(g_debug_flags & 8);
   hipStream_t ws = s;
   LaneScope scope1(s, defer_slot), scope2(s, defer_slot);
-  if (overlap) {
+  if (overlap && (nlive || elive)) {
     if ((rc = side_lane(&lane, 0, s)) || (rc = side_fork(lane, s))) return rc;
     ws = lane->stream;
     scope1.lane = lane;
   }
-  {
+  auto GN = [&](int i) { return gn ? gn[i] : nullptr; };   // a frozen MLP's jobs stay in the tables (they shape the launch, chain.h:
+  auto GE = [&](int i) { return ge ? ge[i] : nullptr; };   // launch_wgrad `skip_mask`) but are not run and have no target
+  if (nlive || elive) {
     WgradJob jobs[kMaxWgradJobs] = {};
     int nj = 0;
+    unsigned skip = 0;
     // every operand comes with a magnitude bound from the chain kernel that produced or consumed it (GmpSaved::bound)
     auto add_job = [&](const float* G, const float* A, float* dW, float* db, int64_t R, int ldw, int col0, const float* gb, const float* ab) {
       WgradJob& j = jobs[nj++];
@@ -501,34 +530,41 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
       j.g_bound = gb; j.a_bound = ab; j.g_mul = j.a_mul = 1.f;
     };
     auto bd = [&](int slot) { return sv.bound + size_t(slot) * kBoundWidth; };
-    if (fused) {   // the edge Linears' gradients were accumulated by the fused kernel: only the fixed-order sum of its partials is left
+    if (fused && elive) {   // the edge Linears' gradients were accumulated by the fused kernel: only the fixed-order sum of its partials is left
       float* const dWs[3] = {ge[2], ge[4], ge[6]};
       float* const dbs[3] = {ge[3], ge[5], ge[7]};
       if ((rc = launch_edge_fused_reduce(wk.ef_part, ef_nwg, dWs, dbs, ws))) return rc;
     }
     for (int l = 1; l <= H && !fused && !(g_debug_flags & 1024); ++l) {   // edge Linears: bf16 gradient and activation tensors in the bf16 precision (experiments: bit 10 drops these jobs)
-      add_job(wk.gE[l], sv.e_act[l - 1], ge[2 * l], ge[2 * l + 1], B * E, (int)D, 0, bd(16 + (H - l)), bd(l - 1));
+      add_job(wk.gE[l], sv.e_act[l - 1], GE(2 * l), GE(2 * l + 1), B * E, (int)D, 0, bd(16 + (H - l)), bd(l - 1));
       jobs[nj - 1].bf16 = bf;
+      if (!elive) skip |= 1u << (nj - 1);
     }
     // no bounds = the range-free arithmetic: the job over the caller's x (g_node_bf3 >= 1), every node-level job (2)
     auto nbd = [&](int slot, int level) -> const float* { return g_node_bf3 >= level ? nullptr : bd(slot); };
     for (int l = 1; l <= H; ++l) {   // node Linears 1..H: bf16 tensors in BSMS_BF16_NODES
-      add_job(wk.gN[l], sv.n_act[l - 1], gn[2 * l], gn[2 * l + 1], B * N, (int)D, 0, nbd(24 + (H - l), 2), nbd(8 + l, 2));
+      add_job(wk.gN[l], sv.n_act[l - 1], GN(2 * l), GN(2 * l + 1), B * N, (int)D, 0, nbd(24 + (H - l), 2), nbd(8 + l, 2));
       jobs[nj - 1].bf16 = bfn;
+      if (!nlive) skip |= 1u << (nj - 1);
     }
     // the job over the caller's x (with the first node Linear's bias gradient): range-free arithmetic = another launch, so
     // at level 1 it rides in lane 2's launch with the two projections (all three range-free) and this lane stays ONE launch of
     // three-product jobs -- two launches here cost the cylinder steps 1.6 % / 6 % (side lane co-critical, r05_node_bf3_ab.txt)
-    if (g_node_bf3 != 1) add_job(wk.gN[0], x, gn[0], gn[1], B * N, int(2 * D), 0, nbd(24 + H, 1), nbd(8, 1));
-    add_job(wk.gN[0], sv.aggr, gn[0], nullptr, B * N, int(2 * D), (int)D, nbd(24 + H, 2), nbd(8, 2));
-    if ((rc = launch_wgrad((int)D, jobs, nj, wk.wg, ws))) return rc;
+    if (g_node_bf3 != 1) {
+      add_job(wk.gN[0], x, GN(0), GN(1), B * N, int(2 * D), 0, nbd(24 + H, 1), nbd(8, 1));
+      if (!nlive) skip |= 1u << (nj - 1);
+    }
+    add_job(wk.gN[0], sv.aggr, GN(0), nullptr, B * N, int(2 * D), (int)D, nbd(24 + H, 2), nbd(8, 2));
+    if (!nlive) skip |= 1u << (nj - 1);
+    if ((rc = launch_wgrad((int)D, jobs, nj, wk.wg, ws, skip))) return rc;
   }
   // a second side stream takes the remaining weight gradients of the first edge Linear (fiber columns + bias now,
   // the x-columns once dPs/dPd exist), so that the caller's stream only carries what grad_x depends on:
   // gE[0] -> dPs, dPd -> grad_x
   SideLane* lane2 = nullptr;
   hipStream_t s2 = s;
-  const bool overlap2 = overlap && !(g_debug_flags & 32);
+  const bool x_job_on_lane2 = nlive && g_node_bf3 == 1;   // the x half of the first node Linear (see above)
+  const bool overlap2 = overlap && !(g_debug_flags & 32) && (elive || x_job_on_lane2);
   bool lane2_forked = false;   // its first fork is only needed by the unfused small-wgrad path; the fused path forks once, below
   if (overlap2) {
     if ((rc = side_lane(&lane2, 1, s))) return rc;
@@ -539,13 +575,18 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
   SmallWgradArgs sw{};
   sw.G = wk.gE[0]; sw.S = sv.e_fiber; sw.S_cols = int(p + 1); sw.S_ld = fiber_ld(p);   // the fiber rows the forward kept
   sw.p = (int)p;
-  sw.out = ge[0]; sw.os = 1; sw.of = ldE0; sw.colsum = ge[1];
+  if (elive) { sw.out = ge[0]; sw.colsum = ge[1]; }
+  sw.os = 1; sw.of = ldE0;
   sw.R = B * E; sw.D = (int)D;
   int nwg = 0;
-  if ((rc = rowsum_source_target_fiber(plan, wk.gE[0], B, D, wk.dPs, wk.dPd, sv.e_fiber, fiber_ld(p), int(p + 1),
+  // a frozen edge MLP: only the scatter is left -- the plain pair, which sums every row's slots in the same order as the fused
+  // kernel (rowsum.hip: rowsum_body / fiber_batch), so dPs / dPd are bit-identical
+  if (!elive) {
+    if ((rc = rowsum_source_and_target(plan, wk.gE[0], B, D, wk.dPs, wk.dPd, s))) return rc;
+  } else if ((rc = rowsum_source_target_fiber(plan, wk.gE[0], B, D, wk.dPs, wk.dPd, sv.e_fiber, fiber_ld(p), int(p + 1),
                                        reinterpret_cast<float*>(wk.sw), small_wgrad_part_blocks(wk.sw_bytes, (int)D), &nwg, s, bf))) return rc;
   BSMS_REQUIRE(nwg > 0 || !bf, BSMS_E_UNSUPPORTED, "gmp_bwd: bf16 precision needs the fused scatter kernel (D = 128 / 256, pos_dim <= 3)");
-  if (nwg == 0) {   // shape not built into the fused kernel (D < 128, pos_dim > 3): separate passes
+  if (nwg == 0 && elive) {   // shape not built into the fused kernel (D < 128, pos_dim > 3): separate passes
     if (overlap2) {
       if ((rc = side_fork(lane2, s))) return rc;
       scope2.lane = lane2;
@@ -561,10 +602,10 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
     scope2.lane = lane2;
   }
   if (nwg > 0 && (rc = launch_small_reduce(sw, wk.sw, nwg, s2))) return rc;
-  {
+  if (elive || x_job_on_lane2) {
     WgradJob jobs[3] = {};
     auto set = [&](WgradJob& j, const float* G, int col0) {
-      j.G = G; j.A = x; j.dW = ge[0]; j.db = nullptr; j.R = B * N; j.ldg = (int)D; j.lda = (int)D; j.ldw = ldE0; j.col0 = col0; j.bf16 = 0;
+      j.G = G; j.A = x; j.dW = GE(0); j.db = nullptr; j.R = B * N; j.ldg = (int)D; j.lda = (int)D; j.ldw = ldE0; j.col0 = col0; j.bf16 = 0;
       // dPs / dPd are sums of at most max-degree rows of gE[0]; x is covered by the joint bound of the node chain's input
       j.g_bound = g_node_bf3 ? nullptr : sv.bound + size_t(16 + H) * kBoundWidth;
       j.a_bound = g_node_bf3 ? nullptr : sv.bound + size_t(8) * kBoundWidth; j.a_mul = 1.f;
@@ -574,12 +615,14 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
     jobs[0].g_mul = float(std::max<int64_t>(plan->max_out_degree, 1));   // scatter by source
     jobs[1].g_mul = float(std::max<int64_t>(plan->max_in_degree, 1));    // scatter by target
     int nj2 = 2;
+    unsigned skip2 = elive ? 0u : 3u;   // a frozen edge MLP: the two projection jobs only shape the launch
     if (g_node_bf3 == 1) {   // + the x half of the first node Linear (see above)
       WgradJob& j = jobs[nj2++];
-      j.G = wk.gN[0]; j.A = x; j.dW = gn[0]; j.db = gn[1]; j.R = B * N; j.ldg = (int)D; j.lda = (int)D; j.ldw = int(2 * D); j.col0 = 0;
+      if (!nlive) skip2 |= 1u << (nj2 - 1);
+      j.G = wk.gN[0]; j.A = x; j.dW = GN(0); j.db = GN(1); j.R = B * N; j.ldg = (int)D; j.lda = (int)D; j.ldw = int(2 * D); j.col0 = 0;
       j.bf16 = 0; j.g_bound = j.a_bound = nullptr; j.g_mul = j.a_mul = 1.f;
     }
-    if ((rc = launch_wgrad((int)D, jobs, nj2, wk.wg2, s2))) return rc;
+    if ((rc = launch_wgrad((int)D, jobs, nj2, wk.wg2, s2, skip2))) return rc;
   }
   // grad_x += dPs Wi + dPd Wj
   {
@@ -593,8 +636,12 @@ int bsms::gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, 
   // position gradient (posgrad.hip): on the caller's stream, so gE[0] is read before a later block reuses this scratch set
   if (grad_pos && (rc = gmp_pos_grad(plan, wk.gE[0], bf, sv.e_fiber, params[2 * nl], B, D, p, pos_bstride, grad_pos, pos_accumulate,
                                      reinterpret_cast<float*>(pos_work), s))) return rc;
-  if (defer_slot >= 0 && scope1.lane && scope2.lane) {   // deferred join: one event covers both lanes (lane 2's mark waits for lane 1's)
+  // deferred join: one event covers both lanes (lane 2's mark waits for lane 1's).  The mark covers whichever lanes ran: none
+  // (everything frozen) marks nothing; lane 1 alone -- experiment builds only -- is chained into lane 2's slot all the same, since
+  // callers wait for lane 2's mark (gmp_marks_chained)
+  if (defer_slot >= 0 && scope1.lane) {
     SideLane *a = scope1.lane, *b = scope2.lane;
+    if (!b && (rc = side_lane(&b, 1, s))) return rc;
     scope1.lane = scope2.lane = nullptr;
     return side_mark_chain(a, b, defer_slot);
   }
@@ -731,8 +778,14 @@ extern "C" int bsms_mlp_bwd_ex(const float* x, const float* grad_y, int64_t R, i
                                float* grad_x, float* const* grads, int flags, bsms_stream_t stream) {
   int rc = check_mlp(R, in_dim, D, out_dim, H, layer_norm, "mlp_bwd");
   if (rc) return rc;
-  BSMS_REQUIRE(params && grads && saved && work, BSMS_E_INVALID_ARG, "mlp_bwd: null argument");
+  BSMS_REQUIRE(params && saved && work, BSMS_E_INVALID_ARG, "mlp_bwd: null argument");
   BSMS_REQUIRE((x && grad_y) || R == 0, BSMS_E_INVALID_ARG, "mlp_bwd: null tensor");
+  // grads == NULL (or every entry null): the MLP is frozen -- only the input gradient is formed
+  const int gstate = grads_state(grads, 2 * (H + 1));
+  BSMS_REQUIRE(gstate >= 0, BSMS_E_INVALID_ARG, "mlp_bwd: the gradient entries are partly null (an MLP is frozen as a whole: all %d "
+               "entries null, or none)", 2 * (H + 1));
+  const bool live = gstate == 1;
+  if (!live && !grad_x) return BSMS_OK;   // nothing to compute
   hipStream_t s = as_stream(stream);
   const MlpKind kind = mlp_kind(in_dim, D, out_dim, layer_norm);
   BSMS_REQUIRE(kind == MLP_SMALL_LN || grad_x, BSMS_E_INVALID_ARG, "mlp_bwd: grad_x is null");
@@ -751,15 +804,16 @@ extern "C" int bsms_mlp_bwd_ex(const float* x, const float* grad_y, int64_t R, i
     top = H;
   }
   const int bottom = (kind == MLP_SMALL_LN) ? 1 : 1;  // dgrad stages run Linear_top .. Linear_1
-  a.gstore[0] = wk.g[top];
+  // frozen: the layer gradients have no reader -- but g[0] of the encoder shape, which the narrow input gradient multiplies
+  a.gstore[0] = live ? wk.g[top] : nullptr;
   int k = 0;
   for (int l = top; l >= bottom; --l, ++k) {
     a.wpt[k] = reinterpret_cast<const float4*>(sv.wt[l]);
     a.mask[k] = sv.act[l - 1];
-    a.gstore[k + 1] = wk.g[l - 1];
+    a.gstore[k + 1] = (live || (l == 1 && kind == MLP_SMALL_LN)) ? wk.g[l - 1] : nullptr;
   }
   a.nstage = k;
-  if (!g_node_bf3) for (int q = 0; q <= k; ++q) a.gmax[q] = sv.bound + size_t(16 + q) * kBoundWidth;
+  if (!g_node_bf3 && live) for (int q = 0; q <= k; ++q) a.gmax[q] = sv.bound + size_t(16 + q) * kBoundWidth;
   if (kind == MLP_SMALL_LN) {
     rc = launch_chain_bwd((int)D, G_ROWS_LN, F_NONE, a, s);
     // optional input gradient (a caller differentiating w.r.t. the encoder's input): g0 . W0, narrow (posgrad.hip)
@@ -769,7 +823,7 @@ extern "C" int bsms_mlp_bwd_ex(const float* x, const float* grad_y, int64_t R, i
     a.dx = grad_x;
     rc = launch_chain_bwd((int)D, kind == MLP_ROWS_SMALL ? G_SMALL : G_ROWS_LN, F_HEADS1, a, s);
   }
-  if (rc) return rc;
+  if (rc || !live) return rc;   // frozen: no weight gradient, no side lane, no mark
 
   // BSMS_BWD_DEFER_JOIN: grad_x is complete in stream order here; the weight gradients go to side lane 0 and the caller
   // joins later (bsms_side_lanes_join) -- the fused step runs the decoder's weight gradients under the U-Net's first block

@@ -134,6 +134,14 @@ int side_join(SideLane* lane, hipStream_t main) {
 int side_mark(SideLane* lane, int slot) {
   std::lock_guard<std::mutex> lock(g_lane_mu);
   BSMS_HIP_CHECK(hipEventRecord(lane->done_ev[slot & 1], lane->stream));
+  lane->uncovered[slot & 1] = true;
+  return BSMS_OK;
+}
+int side_wait_open_mark(SideLane* lane, int slot, hipStream_t main) {
+  std::lock_guard<std::mutex> lock(g_lane_mu);
+  if (!lane->uncovered[slot & 1]) return BSMS_OK;
+  BSMS_HIP_CHECK(hipStreamWaitEvent(main, lane->done_ev[slot & 1], 0));
+  lane->uncovered[slot & 1] = false;
   return BSMS_OK;
 }
 // both lanes' work so far as ONE event: lane `b` waits for lane `a`'s mark and records its own; a later
@@ -143,11 +151,14 @@ int side_mark_chain(SideLane* a, SideLane* b, int slot) {
   BSMS_HIP_CHECK(hipEventRecord(a->done_ev[slot & 1], a->stream));
   BSMS_HIP_CHECK(hipStreamWaitEvent(b->stream, a->done_ev[slot & 1], 0));
   BSMS_HIP_CHECK(hipEventRecord(b->done_ev[slot & 1], b->stream));
+  a->uncovered[0] = a->uncovered[1] = false;   // lane a is in order: b's mark covers everything a has marked so far
+  b->uncovered[slot & 1] = true;
   return BSMS_OK;
 }
 int side_wait_mark(SideLane* lane, int slot, hipStream_t main) {
   std::lock_guard<std::mutex> lock(g_lane_mu);
   BSMS_HIP_CHECK(hipStreamWaitEvent(main, lane->done_ev[slot & 1], 0));
+  lane->uncovered[slot & 1] = false;
   return BSMS_OK;
 }
 }  // namespace bsms

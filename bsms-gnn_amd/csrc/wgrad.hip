@@ -919,7 +919,10 @@ static int64_t knob_rows(const char* name, int64_t dflt) {   // experiment build
   return dflt;
 #endif
 }
-static int launch_wgrad_same(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t s, bool bf, bool h2) {
+// `skip_mask` (bit j = job j): jobs of a frozen MLP.  They are not run -- no tile, no reduction -- but the launch shape (slab length, tile
+// kind) is decided as if they were: the split-K partition of the remaining jobs, and so every bit of their sums, is that of the
+// launch with nothing frozen.
+static int launch_wgrad_same(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t s, bool bf, bool h2, unsigned skip_mask) {
   BSMS_REQUIRE(njobs >= 0 && njobs <= kMaxWgradJobs, BSMS_E_INVALID_ARG, "wgrad: %d jobs (max %d)", njobs, kMaxWgradJobs);
   BSMS_REQUIRE(D % 4 == 0 && D <= 256, BSMS_E_UNSUPPORTED, "wgrad: D=%d", D);
   if (njobs == 0) return BSMS_OK;
@@ -961,14 +964,18 @@ static int launch_wgrad_same(int D, const WgradJob* jobs, int njobs, void* work,
     if (tiles * tile_units <= kMaxTiles) break;
     rows_per *= 2;
   }
-  int first = 0;
+  int first = 0, nrun = 0;
   for (int j = 0; j < njobs; ++j) {
-    tab.job[j] = jobs[j];
-    tab.rows_per_wg[j] = (int)rows_per;
-    tab.nsplit[j] = (int)std::max<int64_t>(1, ceil_div(jobs[j].R, rows_per));
-    tab.first_tile[j] = first;
-    first += tab.nsplit[j] * blocks;
+    if (skip_mask >> j & 1u) continue;
+    tab.job[nrun] = jobs[j];
+    tab.rows_per_wg[nrun] = (int)rows_per;
+    tab.nsplit[nrun] = (int)std::max<int64_t>(1, ceil_div(jobs[j].R, rows_per));
+    tab.first_tile[nrun] = first;
+    first += tab.nsplit[nrun] * blocks;
+    ++nrun;
   }
+  if (nrun == 0) return BSMS_OK;   // a launch without jobs is not issued
+  tab.njobs = njobs = nrun;
   tab.first_tile[njobs] = first;
   tab.partials = reinterpret_cast<float*>(work);
   tab.colsums = tab.partials + size_t(kMaxTiles) * TB * TB;
@@ -998,7 +1005,7 @@ static int launch_wgrad_same(int D, const WgradJob* jobs, int njobs, void* work,
 
 // jobs of both storage types may be mixed in one call: they go out as (at most) two launches on the same stream, the
 // second reusing the partial-block workspace after the first one's reduction
-int launch_wgrad(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t s) {
+int launch_wgrad(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t s, unsigned skip_mask) {
   BSMS_REQUIRE(njobs >= 0 && njobs <= kMaxWgradJobs, BSMS_E_INVALID_ARG, "wgrad: %d jobs (max %d)", njobs, kMaxWgradJobs);
 #ifdef BSMS_EXPERIMENTS
   static const bool skip = getenv("BSMS_SKIP_WGRAD") != nullptr;   // timing experiments: what do the weight gradients cost the step?
@@ -1012,12 +1019,15 @@ int launch_wgrad(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t
 #endif
   for (int mode = 0; mode < 3; ++mode) {   // 0: fp32 with bounds (fp16 x 2), 1: fp32 without (bf16 x 3), 2: bf16 tensors
     int n = 0;
+    unsigned part_skip = 0;
     for (int j = 0; j < njobs; ++j) {
       const int m = jobs[j].bf16 ? 2 : ((jobs[j].g_bound && jobs[j].a_bound && !force_bf3) ? 0 : 1);
-      if (m == mode) part[n++] = jobs[j];
+      if (m != mode) continue;
+      if (skip_mask >> j & 1u) part_skip |= 1u << n;
+      part[n++] = jobs[j];
     }
     if (n) {
-      int rc = launch_wgrad_same(D, part, n, work, s, mode == 2, mode == 0);
+      int rc = launch_wgrad_same(D, part, n, work, s, mode == 2, mode == 0, part_skip);
       if (rc) return rc;
     }
   }

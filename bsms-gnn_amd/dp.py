@@ -26,10 +26,12 @@ class GradBuckets:
     def __init__(self, params, bucket_bytes=2 << 20, group=None, overlap=True):
         self.group = group
         self.overlap = overlap   # False: every bucket is reduced in finish() (after backward)
+        params = list(params)
         self.params = [p for p in params if p.requires_grad]
         order = list(reversed(self.params))  # roughly the order backward produces them
         total = sum(p.numel() for p in order)
-        dev, dt = order[0].device, order[0].dtype
+        ref = order[0] if order else (params[0] if params else torch.zeros(0))      # nothing trainable: an empty buffer (a data-only step)
+        dev, dt = ref.device, ref.dtype
         self.flat = torch.zeros(total, device=dev, dtype=dt)
         self.buckets, self._bucket_of, self._slot = [], {}, {}
         off, start, cur = 0, 0, []
@@ -150,7 +152,9 @@ class DataParallel:
         `objective` (objective.Objective): None reads the optional loss_space / loss_kind / loss_channel_weights of `model.cfg`;
         without them it is the reference's masked RMSE.
         `input_grad`: the fused step also forms the gradient of the loss w.r.t. `node_in` (`engine.fused.input_grad()`, DESIGN.md
-        4.12) -- local to this rank's samples, no collective; only the fused step implements it."""
+        4.12) -- local to this rank's samples, no collective; only the fused step implements it.
+        Frozen parameters: freeze whole MLPs with requires_grad_(False) BEFORE constructing this.  A model with
+        nothing trainable is a data-only step and needs `input_grad=True`: without it the constructor raises ValueError."""
         from .objective import Objective
         self.model, self.group, self.unroll = model, group, int(unroll)
         if objective is None:

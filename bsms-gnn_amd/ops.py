@@ -76,6 +76,23 @@ def _grad_targets(params):
     return out
 
 
+def _grad_targets_by_mlp(params, needs, group):
+    """`_grad_targets` with frozen MLPs left out.  `params` is cut into MLPs of `group` tensors each and `needs` says,
+    per tensor, whether autograd wants its gradient.  An MLP none of whose tensors needs one gets NULL entries at the C ABI -- the
+    backward then launches nothing for its dW / db -- and `None` gradients; an MLP with some frozen and some trainable tensors keeps
+    every gradient.  Returns (entries for the pointer table, what backward() hands to autograd)."""
+    entries, out = [], []
+    for i in range(0, len(params), group):
+        if any(needs[i:i + group]):
+            g = _grad_targets(params[i:i + group])
+            entries += [t.data_ptr() for t in g]
+            out += g
+        else:
+            entries += [None] * group
+            out += [None] * group
+    return entries, out
+
+
 # --------------------------------------------------------------------------------- evaluation sums
 def _segment_view(t, what, S, seg_rows, width, stride):
     """(tensor whose data_ptr is row 0 of segment 0, rows between segments) of a float32 device tensor read as S segments of
@@ -273,10 +290,10 @@ class _MLPFunction(torch.autograd.Function):
         gy = gy.contiguous()
         need_dx = ctx.needs_input_grad[0]
         gx = torch.empty_like(x) if (need_dx or in_dim == D) else None
-        grads = _grad_targets(params)
+        entries, grads = _grad_targets_by_mlp(params, ctx.needs_input_grad[4:], len(params))
         work = _workspace(x.device, L.bsms_mlp_work_bytes(R, in_dim, D, out_dim, hidden))
         pp, keep = _param_ptrs(params)
-        gp, keep2 = _param_ptrs(grads)
+        gp, keep2 = _abi.ptr_array(entries)
         _abi.check(L.bsms_mlp_bwd(x.data_ptr(), gy.data_ptr(), R, in_dim, D, out_dim, hidden, int(layer_norm), pp,
                                   saved.data_ptr(), work.data_ptr(), gx.data_ptr() if gx is not None else None, gp,
                                   _stream()), "bsms_mlp_bwd")
@@ -373,10 +390,10 @@ class _GMPFunction(torch.autograd.Function):
         L = _abi.lib()
         gout = gout.contiguous()
         gx = torch.empty_like(x)
-        grads = _grad_targets(params)
+        entries, grads = _grad_targets_by_mlp(params, ctx.needs_input_grad[4:], 2 * (hidden + 1))   # node MLP, edge MLP
         work = _workspace(x.device, L.bsms_gmp_work_bytes(B, N, plan.E, D, hidden))
         pp, keep = _param_ptrs(params)
-        gp, keep2 = _param_ptrs(grads)
+        gp, keep2 = _abi.ptr_array(entries)
         gpos = None
         if ctx.needs_input_grad[1]:   # positions as an autograd input (shape sensitivity): bsms_gmp_bwd + grad_pos
             gpos = torch.empty_like(pos)
@@ -582,10 +599,14 @@ class _BSGMPFunction(torch.autograd.Function):
         ewp, keep_ew = _abi.ptr_array([e.data_ptr() for e in ews])
         gout = gout.contiguous()
         gh = torch.empty_like(h)
-        grads = _grad_targets(params)
+        if ctx.prec == 0:     # fp32: a frozen MLP (node / edge MLP of a block) gets no weight gradient at all
+            entries, grads = _grad_targets_by_mlp(params, ctx.needs_input_grad[6:], 2 * (hidden + 1))
+        else:                 # the bf16 precisions form every weight gradient (frozen parameters: throwaway storage)
+            grads = _grad_targets(params)
+            entries = [t.data_ptr() for t in grads]
         work = _workspace(h.device, L.bsms_bsgmp_work_bytes(pl, depth, B, D, p, hidden))
         pp, keep = _param_ptrs(params)
-        gp, keep2 = _param_ptrs(grads)
+        gp, keep2 = _abi.ptr_array(entries)
         gpos = None
         if ctx.needs_input_grad[1]:   # positions as an autograd input: through every block and the pooling of the positions
             gpos = torch.empty_like(pos)

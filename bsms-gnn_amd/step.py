@@ -22,7 +22,11 @@ scratch flat buffer that bsms_grad_accumulate folds into `GradBuckets.flat`.
 
 `input_grad=True` also forms the gradient w.r.t. `node_in`: the U-Net backward goes through bsms_bsgmp_bwd_pos_ev
 (the same schedule plus the position kernels), the encoder's backward returns its input gradient at every step, and one
-bsms_sim_input_grad launch per step folds them, with the step's g_pred, into a static [B, N, C+p+1] buffer (`input_grad()`)."""
+bsms_sim_input_grad launch per step folds them, with the step's g_pred, into a static [B, N, C+p+1] buffer (`input_grad()`).
+
+Frozen parameters: an MLP -- encoder, decoder, a block's node or edge MLP -- all of whose parameters have
+`requires_grad == False` gets NULL entries in the gradient tables; the backward then launches nothing for its weight gradients.
+With nothing trainable (or `param_grad=False`) and `input_grad=True` the backward is data-only."""
 import os
 
 import torch
@@ -34,6 +38,19 @@ from .ops import PRECISIONS, _param_ptrs, _stream
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def _mlps(model):
+    """The units of freezing, in the order (encoder, U-Net blocks in storage order: node MLP then edge MLP, decoder)."""
+    proc = model.process
+    blocks = [*proc.down_gmps, proc.bottom_gmp, *proc.up_gmps]
+    return [model.encode, *(q for b in blocks for q in (b.mlp_node, b.mlp_edge)), model.decode]
+
+
+def _freeze_state(mlp):
+    """True: every parameter trainable; False: every parameter frozen; None: some of each."""
+    req = [p.requires_grad for p in mlp.flat_params()]
+    return True if all(req) else (False if not any(req) else None)
 
 
 class _Arena:
@@ -63,11 +80,13 @@ class _Arena:
 
 class FusedStep:
     def __init__(self, model, grads, group=None, use_graph=False, unroll=1, step_weights=None, detach=False, objective=None,
-                 input_grad=False):
+                 input_grad=False, param_grad=True):
         """`objective` (objective.Objective): None or the default objective keeps the reference's masked RMSE on the kernels it
         always ran on; any other runs bsms_error_sums after every forward and bsms_sim_objective_bwd in front of every backward.
         `input_grad`: every backward also forms the gradient of the (K-step) loss w.r.t. `node_in` -- state, mesh
-        positions and node type -- into a static [B, N, C+p+1] buffer, handed out by `input_grad()`.  Off: nothing changes."""
+        positions and node type -- into a static [B, N, C+p+1] buffer, handed out by `input_grad()`.  Off: nothing changes.
+        `param_grad=False` (with `input_grad=True`): the backward is data-only whatever `requires_grad` says -- no weight gradient is
+        formed, `grads` may be None and no `p.grad` is touched."""
         from .model import BSMS_Simulator
         if not isinstance(model, BSMS_Simulator):
             raise TypeError("FusedStep drives a bsms_gnn_amd.BSMS_Simulator")
@@ -88,6 +107,15 @@ class FusedStep:
         if not isinstance(input_grad, bool):
             raise TypeError(f"FusedStep: input_grad is a bool, got {type(input_grad).__name__}")
         self._input_grad, self._ig_ran = input_grad, False
+        self._param_grad = bool(param_grad)
+        if not self._param_grad and not input_grad:
+            raise ValueError("FusedStep: param_grad=False without input_grad=True would compute nothing")
+        if grads is None and self._param_grad:
+            raise ValueError("FusedStep: weight gradients need a GradBuckets (grads=None goes with param_grad=False)")
+        self._any_live = False                      # some MLP gets weight gradients (set by _pointer_tables)
+        if not input_grad and not any(p.requires_grad for q in _mlps(model) for p in q.flat_params()):
+            raise ValueError("FusedStep: nothing is trainable and input_grad is off: the step would compute nothing")
+        self._guard_params = [q.flat_params()[0] for q in _mlps(model)]
         from .objective import Objective
         self.objective = (Objective() if objective is None else objective).bind(model.cfg.out_dim)
         self._obj = None if self.objective.is_default else self.objective      # None: the default route, untouched
@@ -97,16 +125,20 @@ class FusedStep:
         self._arena = _Arena()
         self._overlap = None          # bucket schedule of the overlapped gradient all-reduce (_bucket_schedule), built lazily
         self._comm = None             # communication stream the bucket all-reduces are issued from
-        for p in grads.params:                      # .grad aliases the flat buffer once and for all
+        for p in (grads.params if self._param_grad else ()):      # .grad aliases the flat buffer once and for all
             off, n = grads._slot[p]
             p.grad = grads.flat[off:off + n].view_as(p)
 
     # ------------------------------------------------------------------------------------------------ helpers
     @staticmethod
     def supports(model):
+        """A standard one-call BSMS_Simulator whose MLPs (encoder, decoder, each block's node and edge MLP) are each all-trainable
+        or all-frozen; anything frozen needs the fp32 precision."""
         from .model import BSMS_Simulator
-        return (isinstance(model, BSMS_Simulator) and not model.process.per_block
-                and all(p.requires_grad for p in [*model.encode.parameters(), *model.process.parameters(), *model.decode.parameters()]))
+        if not isinstance(model, BSMS_Simulator) or model.process.per_block:
+            return False
+        states = [_freeze_state(q) for q in _mlps(model)]
+        return None not in states and (all(states) or model.process.precision == "f32")
 
     collectives_at_world_one = False     # tests: issue the step's collectives in a process group of ONE rank as well (a sum over one
                                          # rank is the identity) -- the only way to run the RCCL path on a single-GPU box
@@ -153,17 +185,39 @@ class FusedStep:
     def _pointer_tables(self):
         m = self.model
         enc, proc, dec = m.encode.flat_params(), m.process.block_params(), m.decode.flat_params()
-        guard = (enc[0].data_ptr(), proc[-1].data_ptr(), dec[-1].data_ptr())
-        if guard != self._ptr_guard:                # parameters were re-pointed (optimizer flat buffer, .to(), load)
-            slot = lambda ps: [self.grads.flat[self.grads._slot[p][0]:].data_ptr() for p in ps]
-            self._tabs = {k: (_param_ptrs(ps), _abi.ptr_array(slot(ps))) for k, ps in (("enc", enc), ("proc", proc), ("dec", dec))}
-            if self.unroll > 1:                     # the same slots in the scratch flat buffer: where all steps but the first-run write
-                if self._gscratch is None or self._gscratch.device != self.grads.flat.device:
+        # which MLPs get weight gradients: part of the guard, so a requires_grad_() between two calls rebuilds the tables
+        states = tuple(_freeze_state(q) if self._param_grad else False for q in _mlps(m))
+        # (one pointer per MLP: an optimizer re-points the trainable MLPs only, which may be any subset)
+        guard = (enc[0].data_ptr(), proc[-1].data_ptr(), dec[-1].data_ptr(), *(t.data_ptr() for t in self._guard_params), states)
+        if guard != self._ptr_guard:                # parameters were re-pointed (optimizer flat buffer, .to(), load) or (un)frozen
+            if None in states:
+                raise ValueError("FusedStep: an MLP with some frozen and some trainable parameters (an MLP is frozen as a whole)")
+            if not all(states) and m.process.precision != "f32":
+                raise ValueError("FusedStep: frozen parameters need the fp32 precision")
+            if not any(states) and not self._input_grad:
+                raise ValueError("FusedStep: nothing is trainable and input_grad is off: the step would compute nothing")
+            live = {}
+            for q, st in zip(_mlps(m), states):
+                for t in q.flat_params():
+                    live[t] = st
+                    if st and t not in self.grads._slot:
+                        raise ValueError("FusedStep: a trainable parameter has no slot in `grads` (it was frozen when the GradBuckets "
+                                         "was built: build the GradBuckets after requires_grad_())")
+            # NULL entries for frozen MLPs: the backward launches nothing for their weight gradients
+            table = lambda flat, ps: _abi.ptr_array([flat[self.grads._slot[t][0]:].data_ptr() if live[t] else None for t in ps])
+            groups = (("enc", enc), ("proc", proc), ("dec", dec))
+            self._any_live = any(states)
+            self._tabs = {k: (_param_ptrs(ps), table(self.grads.flat if self._any_live else None, ps)) for k, ps in groups}
+            self._tabs_scratch = None
+            if self.unroll > 1 and self._any_live:  # the same slots in the scratch flat buffer: where all steps but the first-run write
+                if self._gscratch is None or self._gscratch.device != self.grads.flat.device or self._gscratch.numel() != self.grads.flat.numel():
                     self._gscratch = torch.zeros_like(self.grads.flat)       # zeros: a slot no kernel writes adds nothing
-                scr = lambda ps: [self._gscratch[self.grads._slot[p][0]:].data_ptr() for p in ps]
-                self._tabs_scratch = {k: (self._tabs[k][0], _abi.ptr_array(scr(ps))) for k, ps in (("enc", enc), ("proc", proc), ("dec", dec))}
+                self._tabs_scratch = {k: (self._tabs[k][0], table(self._gscratch, ps)) for k, ps in groups}
+            elif self.unroll > 1:                   # nothing trainable: every table is NULLs, no scratch buffer
+                self._tabs_scratch = self._tabs
             self._ptr_guard = guard
             self._graphs = None
+            self._overlap = None                    # the bucket schedule depends on which blocks run side lanes
         return self._tabs
 
     def _buffers(self, B, N, plans, dev):
@@ -325,11 +379,11 @@ class FusedStep:
         self._forward(b, node_in, tar, mask, ews, B, N)
         if world > 1:
             dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
-        if world > 1 and self._overlap_now():
+        if world > 1 and self._any_live and self._overlap_now():
             self._backward_overlapped(b, tar, mask, ews, B, N)
         else:
             self._backward(b, tar, mask, ews, B, N)
-            if world > 1:
+            if world > 1 and self._any_live:
                 dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         self._probe_end()
         return b["loss"][0].clone()       # the static buffer is overwritten by the next step: hand out a copy (4 bytes)
@@ -398,7 +452,7 @@ class FusedStep:
             dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
         # K backwards, k = K-1 .. 0.  The first one run writes grads.flat itself, the others the scratch buffer, folded in after
         # the join: the deferred weight-gradient lanes of step k still write it (and read work / work_enc / work_dec) until then
-        n = self.grads.flat.numel()
+        n = self.grads.flat.numel() if self._any_live else 0
         for k in range(K - 1, -1, -1):
             bk, last = steps[k], k == K - 1
             carry = not last and not self.detach
@@ -408,9 +462,9 @@ class FusedStep:
                          g_pred=b["g_pred"][k & 1] if keep else None, grad_x=b["g_nin"] if keep else None,
                          first_step=int(k == 0), overwrite=int(last))
             self._backward(bk, tars[k], mask, ews, B, N, chain=chain)          # ends with bsms_side_lanes_join
-            if not last:
+            if not last and self._any_live:
                 _abi.check(L.bsms_grad_accumulate(self.grads.flat.data_ptr(), self._gscratch.data_ptr(), n, 0, s), "bsms_grad_accumulate")
-        if world > 1:
+        if world > 1 and self._any_live:
             dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         return torch.dot(b["loss_all"], self._wts)
 
@@ -505,13 +559,18 @@ class FusedStep:
         final join (encoder, and whatever shares a bucket with it)."""
         m, L = self.model, depth
         stage = {}
-        for q in m.decode.flat_params():
-            stage[q] = 0                                          # covered by the first block's event (in-order lanes)
         blocks = [*m.process.down_gmps, m.process.bottom_gmp, *m.process.up_gmps]
+        with_lanes = []                                           # execution indices of the blocks that run side lanes
         for k, blk in enumerate(blocks):
             e = (2 * L - k) if k < L else (L if k == L else L - 1 - (k - (L + 1)))     # storage index -> execution index
             for q in (*blk.mlp_node.flat_params(), *blk.mlp_edge.flat_params()):
                 stage[q] = e
+            if _freeze_state(blk.mlp_node) or _freeze_state(blk.mlp_edge):
+                with_lanes.append(e)
+        # the decoder: covered by the event of the first block that runs side lanes (in-order lanes); a block with both MLPs frozen
+        # records its event on the caller's stream, which says nothing about the lanes -- with every block frozen, the final join
+        for q in m.decode.flat_params():
+            stage[q] = min(with_lanes) if with_lanes else None
         out = []
         for bk in self.grads.buckets:
             st = [stage.get(q) for q in bk["params"]]
@@ -592,12 +651,17 @@ class FusedStep:
         if world > 1:
             dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
         gb.replay()
-        if world > 1:
+        if world > 1 and self._any_live:
             dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         return b["loss"][0].clone()
 
 
-def input_gradient(model, data, consistent=True, later_targets=None, step_weights=None, detach=False, objective=None):
+def _input_gradient_key(K, step_weights, detach, objective, param_grad):
+    """Cache key of `input_gradient`'s steps: one FusedStep per (K, step_weights, detach, objective, param_grad)."""
+    return (int(K), None if step_weights is None else tuple(float(w) for w in step_weights), bool(detach), objective, bool(param_grad))
+
+
+def input_gradient(model, data, consistent=True, later_targets=None, step_weights=None, detach=False, objective=None, param_grad=True):
     """Sensitivity of a (rollout) objective of a trained `BSMS_Simulator`: returns `(loss, grad_node_in)`, the weighted K-step loss
     and its gradient w.r.t. `node_in` -- initial state, mesh positions, node type; [B, N, C+p+1], or [1, rows, C+p+1] for variable
     meshes.  K = 1 without `later_targets`, else `later_targets.shape[0] + 1`; `step_weights`, `detach` and
@@ -607,18 +671,22 @@ def input_gradient(model, data, consistent=True, later_targets=None, step_weight
     model, together with ONE `GradBuckets` for all of them.  The parameters themselves are left untouched.  Their `.grad`s are
     written as `GradBuckets` writes them: after the first call every `p.grad` is a view into the flat gradient buffer and holds
     the weight gradients of the last call (the backward forms them anyway).  A model that a `Trainer` or `DataParallel` drives
-    owns its `GradBuckets` already: take `engine.fused.input_grad()` there (`DataParallel(input_grad=True)`) instead."""
+    owns its `GradBuckets` already: take `engine.fused.input_grad()` there (`DataParallel(input_grad=True)`) instead.
+
+    `param_grad=False`: the backward is data-only whatever `requires_grad` says -- no weight gradient is formed,
+    no `GradBuckets` is created and no `p.grad` is touched or created; loss and gradient are bit-identical to `param_grad=True`'s.
+    fp32 precision only."""
     from .dp import GradBuckets
     from .objective import Objective
     K = 1 if later_targets is None else int(later_targets.shape[0]) + 1
     objective = Objective() if objective is None else objective
-    key = (K, None if step_weights is None else tuple(float(w) for w in step_weights), bool(detach), objective)
+    key = _input_gradient_key(K, step_weights, detach, objective, param_grad)
     cache = model.__dict__.setdefault("_bsms_input_grad_steps", {})
     step = cache.get(key)
     if step is None:
-        if "grads" not in cache:
+        if param_grad and "grads" not in cache:
             cache["grads"] = GradBuckets(list(model.parameters()))
-        step = cache[key] = FusedStep(model, cache["grads"], unroll=K, step_weights=step_weights, detach=detach, objective=objective,
-                                      input_grad=True)
+        step = cache[key] = FusedStep(model, cache["grads"] if param_grad else None, unroll=K, step_weights=step_weights, detach=detach,
+                                      objective=objective, input_grad=True, param_grad=bool(param_grad))
     loss = step(data, consistent, later_targets)
     return loss, step.input_grad().clone()

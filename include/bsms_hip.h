@@ -190,7 +190,11 @@ int bsms_gather_rows(const float* x, int64_t B, int64_t N, int64_t D, const int6
  * must then be non-NULL).  Supported shapes: (in_dim <= 8 or in_dim == D) and
  * (out_dim == D with layer_norm, or out_dim <= 8 without).  `saved` keeps the activations the backward
  * needs.  bsms_mlp_bwd: grad_x = NULL skips the input gradient (the encoder's input is data); a non-null grad_x gets it for
- * every supported shape, the narrow first Linear (in_dim <= 8) included -- a caller differentiating w.r.t. node_in. */
+ * every supported shape, the narrow first Linear (in_dim <= 8) included -- a caller differentiating w.r.t. node_in.
+ * FROZEN MLP (bsms_mlp_bwd / bsms_mlp_bwd_ex): `grads` = NULL, or all of its 2*(hidden+1) entries NULL, forms no
+ * weight gradient -- only the backward chain (which then stores no layer gradient) and grad_x; no side lane is used or marked.
+ * Some entries NULL and some not: BSMS_E_INVALID_ARG, checked on the host before any launch.  `grads` = NULL with grad_x = NULL
+ * does nothing and returns BSMS_OK.  grad_x is bit-identical to the call with every gradient. */
 size_t bsms_mlp_saved_bytes(int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int hidden);
 size_t bsms_mlp_work_bytes(int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int hidden);
 int bsms_mlp_fwd(const float* x, int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int hidden,
@@ -217,7 +221,13 @@ int bsms_mlp_fwd_ex(const float* x, int64_t R, int64_t in_dim, int64_t D, int64_
  * followed by 2*(hidden+1) of mlp_edge (state_dict order of a GMP module).  bsms_gmp_bwd gives no gradient w.r.t. pos (the
  * reference's training loop never asks for one); bsms_gmp_bwd_pos below does.  `saved` = NULL in
  * bsms_gmp_fwd selects INFERENCE (rollout, utils/rollout_utils.py:14-64): no activation is written for a backward, the
- * messages live in `work`. */
+ * messages live in `work`.
+ * FROZEN MLPs (bsms_gmp_bwd / bsms_gmp_bwd_pos): the 2*(hidden+1) `grads` entries of mlp_node, and those of
+ * mlp_edge, may be NULL -- all of an MLP's entries or none; `grads` = NULL freezes both.  Nothing that only serves a frozen MLP's
+ * weight gradients is launched (its split-K jobs, the fiber / bias sums of the first edge Linear, the two projection jobs), a
+ * side lane with nothing to run is not used, and the backward chains do not store the layer gradients that only those launches
+ * read (D = 128 / 256: the no-store build of the edge kernel).  grad_x, grad_pos and the other MLP's gradients are bit-identical
+ * to the call with every entry.  A partly null MLP: BSMS_E_INVALID_ARG, on the host, before any launch.  fp32 only. */
 size_t bsms_gmp_saved_bytes(int64_t B, int64_t N, int64_t E, int64_t D, int hidden);
 size_t bsms_gmp_work_bytes(int64_t B, int64_t N, int64_t E, int64_t D, int hidden);
 int bsms_gmp_fwd(const bsms_plan_t* plan, const float* x, const float* pos, int64_t B, int64_t D,
@@ -247,7 +257,15 @@ int bsms_gmp_bwd_pos(const bsms_plan_t* plan, const float* x, const float* pos, 
  * (cal_ew chain, BSMS.py:64,73,89 -- mesh-static, the caller caches them).  h,out [B,N_0,D]; pos [B,N_0,p]
  * (pos_batch_stride = N_0*p) or [N_0,p] (0).  `params`/`grads`: HOST arrays of (2L+1) x 4 (hidden+1) device
  * pointers, blocks in the order down_gmps[0..L-1], bottom_gmp, up_gmps[0..L-1] (up_gmps[i] acts on level L-1-i,
- * BSMS.py:96-101), each block laid out as for bsms_gmp_fwd.  `saved` = NULL selects inference. */
+ * BSMS.py:96-101), each block laid out as for bsms_gmp_fwd.  `saved` = NULL selects inference.
+ * FROZEN MLPs (every bsms_bsgmp_bwd* entry): per block as for bsms_gmp_bwd -- the node MLP's and the edge MLP's
+ * `grads` entries all there or all NULL; `grads` = NULL freezes the whole U-Net (a data-only backward: grad_h, grad_pos).  Every
+ * block's entries are checked on the host before the first launch: a partly null MLP is BSMS_E_INVALID_ARG, null entries with a
+ * bf16 precision are BSMS_E_UNSUPPORTED.  grad_h, grad_pos and the remaining gradients are bit-identical to the call with every
+ * entry.  A block whose two MLPs are frozen runs no side lane: under BSMS_BWD_DEFER_JOIN it marks nothing, and its
+ * `block_done_events` entry (bsms_bsgmp_bwd_ev) is recorded on the CALLER's stream -- it orders the block itself, not the weight
+ * gradients of earlier blocks or of a deferred bsms_mlp_bwd_ex; wait for the entry of a block that has weight gradients, or for
+ * bsms_side_lanes_join. */
 size_t bsms_bsgmp_saved_bytes(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden);
 size_t bsms_bsgmp_work_bytes(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden);
 /* `work` size for callers that only ever run INFERENCE forwards (saved == NULL; rollout_utils.py:14-64) with this buffer:
