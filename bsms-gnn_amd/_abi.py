@@ -106,7 +106,21 @@ SIGNATURES = {
     "bsms_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_float, c_i64, C.c_float, c_void_p, c_void_p, c_void_p]),
     "bsms_grad_accumulate": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p]),
+    "bsms_wgrad_bound_width": (c_size_t, []),
+    "bsms_wgrad_work_bytes": (c_size_t, [c_i64, c_int]),
+    "bsms_wgrad": (c_int, [c_void_p, c_int, c_i64, C.c_uint, c_void_p, c_size_t, c_void_p]),
+    "bsms_small_wgrad_work_bytes": (c_size_t, [c_i64]),
+    "bsms_small_wgrad": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_i64, c_i64, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
 }
+
+
+class WgradJob(C.Structure):
+    """bsms_wgrad_job (include/bsms_hip.h)."""
+    _fields_ = [("G", c_void_p), ("A", c_void_p), ("dW", c_void_p), ("db", c_void_p), ("R", c_i64),
+                ("ldg", c_int), ("lda", c_int), ("ldw", c_int), ("col0", c_int), ("bf16", c_int),
+                ("g_bound", c_void_p), ("a_bound", c_void_p), ("g_mul", C.c_float), ("a_mul", C.c_float)]
+
 
 _ERRORS = {-1: "BSMS_E_INVALID_ARG", -2: "BSMS_E_SHAPE", -3: "BSMS_E_UNSUPPORTED", -4: "BSMS_E_HIP"}
 _lib = None

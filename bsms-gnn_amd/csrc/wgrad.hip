@@ -1072,3 +1072,87 @@ int launch_small_wgrad(const SmallWgradArgs& a, void* work, hipStream_t s) {
 }
 
 }  // namespace bsms
+
+// ------------------------------------------------------------------ C ABI: the two launchers as primitives (include/bsms_hip.h)
+// Host-side validation only; the launches are launch_wgrad / launch_small_wgrad unchanged.
+namespace {
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool envelope_width(int64_t D) { return D >= 32 && D <= 256 && D % 32 == 0; }
+constexpr int64_t kMaxPrimitiveRows = 2147483647;   // row counts and row pitches are ints in the job tables
+constexpr int64_t kMaxPrimitivePitch = 1 << 20;
+}  // namespace
+
+extern "C" size_t bsms_wgrad_bound_width(void) { return size_t(kBoundWidth); }
+
+extern "C" size_t bsms_wgrad_work_bytes(int64_t D, int njobs) {
+  if (!envelope_width(D) || njobs < 0 || njobs > kMaxWgradJobs) return 0;
+  return wgrad_work_bytes((int)D, njobs);
+}
+
+extern "C" int bsms_wgrad(const bsms_wgrad_job* jobs, int njobs, int64_t D, unsigned skip_mask, void* work, size_t work_bytes,
+                          bsms_stream_t stream) {
+  BSMS_REQUIRE(njobs >= 0 && njobs <= kMaxWgradJobs, BSMS_E_INVALID_ARG, "bsms_wgrad: %d jobs (0..%d)", njobs, kMaxWgradJobs);
+  BSMS_REQUIRE(envelope_width(D), BSMS_E_UNSUPPORTED, "bsms_wgrad: D=%lld is not supported (multiples of 32 up to 256)", (long long)D);
+  if (njobs == 0) return BSMS_OK;
+  BSMS_REQUIRE(jobs != nullptr, BSMS_E_INVALID_ARG, "bsms_wgrad: jobs is null");
+  BSMS_REQUIRE(work != nullptr && aligned16(work), BSMS_E_INVALID_ARG, "bsms_wgrad: work is null or not 16-byte aligned");
+  BSMS_REQUIRE(work_bytes >= wgrad_work_bytes((int)D, njobs), BSMS_E_INVALID_ARG, "bsms_wgrad: work holds %zu bytes, %zu needed", work_bytes,
+               wgrad_work_bytes((int)D, njobs));
+  for (int j = 0; j < njobs; ++j)   // the row count of a skipped job still shapes the launch of the others
+    BSMS_REQUIRE(jobs[j].R >= 0 && jobs[j].R <= kMaxPrimitiveRows, BSMS_E_SHAPE, "bsms_wgrad: job %d: R=%lld out of range", j,
+                 (long long)jobs[j].R);
+  WgradJob tab[kMaxWgradJobs];
+  for (int j = 0; j < njobs; ++j) {
+    const bsms_wgrad_job& q = jobs[j];
+    WgradJob& w = tab[j];
+    w.G = reinterpret_cast<const float*>(q.G);
+    w.A = reinterpret_cast<const float*>(q.A);
+    w.dW = q.dW; w.db = q.db; w.R = q.R;
+    w.ldg = q.ldg; w.lda = q.lda; w.ldw = q.ldw; w.col0 = q.col0;
+    w.bf16 = q.bf16 ? 1 : 0;
+    w.g_bound = q.g_bound; w.a_bound = q.a_bound; w.g_mul = q.g_mul; w.a_mul = q.a_mul;
+    if (skip_mask >> j & 1u) continue;
+    const int per16 = q.bf16 ? 8 : 4;   // elements of a 16-byte row load
+    BSMS_REQUIRE(q.ldg >= D && q.ldg <= kMaxPrimitivePitch && q.ldg % per16 == 0, BSMS_E_SHAPE,
+                 "bsms_wgrad: job %d: ldg=%d (at least D, a multiple of %d elements)", j, q.ldg, per16);
+    BSMS_REQUIRE(q.lda >= D && q.lda <= kMaxPrimitivePitch && q.lda % per16 == 0, BSMS_E_SHAPE,
+                 "bsms_wgrad: job %d: lda=%d (at least D, a multiple of %d elements)", j, q.lda, per16);
+    BSMS_REQUIRE(q.col0 >= 0 && q.ldw <= kMaxPrimitivePitch && int64_t(q.ldw) >= int64_t(q.col0) + D, BSMS_E_SHAPE,
+                 "bsms_wgrad: job %d: ldw=%d, col0=%d (ldw >= col0 + D)", j, q.ldw, q.col0);
+    BSMS_REQUIRE(q.dW != nullptr, BSMS_E_INVALID_ARG, "bsms_wgrad: job %d: dW is null", j);
+    BSMS_REQUIRE(q.R == 0 || (q.G != nullptr && q.A != nullptr), BSMS_E_INVALID_ARG, "bsms_wgrad: job %d: G or A is null", j);
+    BSMS_REQUIRE(aligned16(q.G) && aligned16(q.A) && aligned16(q.db) && aligned16(q.g_bound) && aligned16(q.a_bound), BSMS_E_INVALID_ARG,
+                 "bsms_wgrad: job %d: G, A, db and the bound slots must be 16-byte aligned", j);
+    const bool quad_store = ((q.ldw | q.col0) & 3) == 0;
+    BSMS_REQUIRE((reinterpret_cast<uintptr_t>(q.dW) & (quad_store ? 15 : 3)) == 0, BSMS_E_INVALID_ARG,
+                 "bsms_wgrad: job %d: dW must be %d-byte aligned", j, quad_store ? 16 : 4);
+    if (!q.bf16 && q.g_bound && q.a_bound)
+      BSMS_REQUIRE(q.g_mul > 0.f && q.a_mul > 0.f && q.g_mul <= 3.0e38f && q.a_mul <= 3.0e38f, BSMS_E_INVALID_ARG,
+                   "bsms_wgrad: job %d: g_mul / a_mul must be positive and finite", j);
+  }
+  return launch_wgrad((int)D, tab, njobs, work, as_stream(stream), skip_mask);
+}
+
+extern "C" size_t bsms_small_wgrad_work_bytes(int64_t D) { return envelope_width(D) ? small_wgrad_work_bytes((int)D) : 0; }
+
+extern "C" int bsms_small_wgrad(const float* G, const float* S, int64_t R, int64_t D, int S_cols, int S_ld, float* out, int64_t os,
+                                int64_t of, float* colsum, float* colsum_S, void* work, size_t work_bytes, bsms_stream_t stream) {
+  BSMS_REQUIRE(envelope_width(D), BSMS_E_UNSUPPORTED, "bsms_small_wgrad: D=%lld is not supported (multiples of 32 up to 256)", (long long)D);
+  BSMS_REQUIRE(S_cols >= 1 && S_cols <= SW_MAXS, BSMS_E_UNSUPPORTED, "bsms_small_wgrad: narrow width %d (1..%d)", S_cols, SW_MAXS);
+  BSMS_REQUIRE(R >= 0 && R <= kMaxPrimitiveRows, BSMS_E_SHAPE, "bsms_small_wgrad: R=%lld out of range", (long long)R);
+  BSMS_REQUIRE(S_ld == 0 || (S_ld >= S_cols && S_ld <= kMaxPrimitivePitch), BSMS_E_SHAPE, "bsms_small_wgrad: S_ld=%d (0, or at least S_cols=%d)",
+               S_ld, S_cols);
+  BSMS_REQUIRE(os >= 1 && of >= 1, BSMS_E_SHAPE, "bsms_small_wgrad: os=%lld, of=%lld (positive strides)", (long long)os, (long long)of);
+  BSMS_REQUIRE(out != nullptr && work != nullptr, BSMS_E_INVALID_ARG, "bsms_small_wgrad: out or work is null");
+  BSMS_REQUIRE(G != nullptr && S != nullptr, BSMS_E_INVALID_ARG, "bsms_small_wgrad: G or S is null (fiber mode is internal)");
+  const int ld = S_ld ? S_ld : S_cols;
+  BSMS_REQUIRE(aligned16(G) && aligned16(work) && ((ld & 3) != 0 || aligned16(S)), BSMS_E_INVALID_ARG,
+               "bsms_small_wgrad: G, work and (with a row pitch that is a multiple of 4) S must be 16-byte aligned");
+  BSMS_REQUIRE(work_bytes >= small_wgrad_work_bytes((int)D), BSMS_E_INVALID_ARG, "bsms_small_wgrad: work holds %zu bytes, %zu needed",
+               work_bytes, small_wgrad_work_bytes((int)D));
+  SmallWgradArgs a{};
+  a.G = G; a.S = S; a.S_cols = S_cols; a.S_ld = S_ld;
+  a.out = out; a.os = os; a.of = of; a.colsum = colsum; a.colsum_S = colsum_S;
+  a.R = R; a.D = (int)D;
+  return launch_small_wgrad(a, work, as_stream(stream));
+}

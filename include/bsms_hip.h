@@ -559,6 +559,60 @@ int bsms_adamw_step(float* params, const float* grads, float* exp_avg, float* ex
  * BSMS_E_INVALID_ARG. */
 int bsms_grad_accumulate(float* acc, const float* g, int64_t n, int first, bsms_stream_t stream);
 
+/* ---------------------------------------------------------------- weight-gradient primitives ---
+ * The batched weight gradient of D x D Linears, the launcher every MLP / GMP backward uses, as an entry of its own:
+ *   job j:  dW[n * ldw + col0 + k] = sum_{r < R} G[r][n] * A[r][k]   (n, k < D),   db[n] = sum_{r < R} G[r][n]   (db nullable)
+ * -- autograd's grad of nn.Linear.weight / .bias for y = A W^T + b with G = dL/dy (ops/basic.py:6-23); dW may be a column
+ * block of a wider matrix (the first edge Linear: ldw = 2D + p + 1).  Outputs are OVERWRITTEN.  G [R, ldg] and A [R, lda] are
+ * fp32, or bf16 when `bf16` != 0 (pitches in ELEMENTS, at least D, a multiple of 4 / 8 so that every row starts on 16 bytes).
+ * Arithmetic, chosen per job (see "Arithmetic" at the top):
+ *   bf16 != 0                     the stored bf16 values, one product, fp32 accumulation;
+ *   g_bound and a_bound given     fp16 x 2 pieces, one power-of-two scale per operand TENSOR.  A bound slot is an array of
+ *                                 bsms_wgrad_bound_width() floats (non-negative, 16-byte aligned); the operand's bound is
+ *                                 max(slot) * mul and the caller guarantees bound >= max |value| (a larger value overflows fp16:
+ *                                 the result is then inf / NaN).  An element within 2^-18 of the bound keeps 22 bits, below that
+ *                                 one bit is lost per octave -- the envelope of the edge-level jobs;
+ *   otherwise                     the range-free three-way bf16 split, six products: fp32-accurate over the whole fp32 range.
+ * Jobs of the three kinds may be mixed; each kind is one launch + one reduction on `stream`, sharing `work`
+ * (bsms_wgrad_work_bytes(D, njobs) bytes, 16-byte aligned).  `skip_mask` bit j: job j is not run and its outputs are not
+ * touched (its pointers may be NULL), but its R still counts when the launch shape is chosen.
+ * SPLIT-K CONTRACT: the rows of a job are cut into slabs whose length depends on D and on the row counts of ALL jobs of the
+ * same kind in the call (skipped ones included); the slabs are summed in slab order by a second kernel, no atomics.  So
+ * the result of a job is bit-identical from run to run for the same call (same D, same kinds, same R's), and may differ in
+ * the last bits between calls that batch it with different jobs.  A job with R == 0 writes zeros.
+ * Checked on the host before any launch: njobs in 0..20 (BSMS_E_INVALID_ARG; 0 returns BSMS_OK), D a multiple of 32 in
+ * 32..256 (BSMS_E_UNSUPPORTED), null `jobs`, null or short `work` (BSMS_E_INVALID_ARG), R in 0..2^31-1 for every job and, for
+ * the jobs that run, the pitches and col0 + D <= ldw (BSMS_E_SHAPE), null dW, null G / A with R > 0, pointers not aligned
+ * for their 16-byte accesses (dW: 16 bytes when ldw and col0 are multiples of 4, else 4) and non-positive or non-finite
+ * g_mul / a_mul of a bounded job (BSMS_E_INVALID_ARG). */
+typedef struct {
+  const void *G, *A;              /* DEVICE [R, ldg], [R, lda]: fp32, or bf16 when bf16 != 0 */
+  float *dW, *db;                 /* DEVICE; db nullable */
+  int64_t R;
+  int ldg, lda, ldw, col0;
+  int bf16;
+  const float *g_bound, *a_bound; /* DEVICE, nullable: one bound slot each */
+  float g_mul, a_mul;
+} bsms_wgrad_job;
+size_t bsms_wgrad_bound_width(void);
+size_t bsms_wgrad_work_bytes(int64_t D, int njobs);   /* 0 outside the envelope */
+int bsms_wgrad(const bsms_wgrad_job* jobs, int njobs, int64_t D, unsigned skip_mask, void* work, size_t work_bytes,
+               bsms_stream_t stream);
+/* The narrow side: out[s * os + f * of] = sum_{r < R} G[r][f] * S[r][s] for the s < S_cols <= 8 columns of a narrow matrix
+ * S [R, S_ld] (S_ld = 0: S_cols) against G [R, D] (dense) -- the weight gradient of the encoder's first Linear (os = 1,
+ * of = S_cols), of the decoder's last (os = D, of = 1) and of the fiber columns of the first edge Linear (os = 1,
+ * of = 2D + p + 1, S_ld = 4 or 8).  `colsum` (nullable, [D]) receives sum_r G[r][:], `colsum_S` (nullable, [S_cols])
+ * sum_r S[r][:].  fp32 fused multiply-adds: each of at most 512 workgroups sums a contiguous slab of rows in row order per
+ * row lane, the partial blocks are added in a fixed order by a second kernel; no atomics, bit-identical from run to run.
+ * A row pitch of S that is a multiple of 4 is read with 16-byte loads (S 16-byte aligned; columns past S_cols are read
+ * and ignored).  `work`: bsms_small_wgrad_work_bytes(D) bytes.  Checked on the host before any launch: D as above and
+ * S_cols in 1..8 (BSMS_E_UNSUPPORTED), R in 0..2^31-1, S_ld, os, of >= 1 (BSMS_E_SHAPE), null G / S / out / work, alignment,
+ * short work (BSMS_E_INVALID_ARG).  R == 0 writes zeros. */
+size_t bsms_small_wgrad_work_bytes(int64_t D);        /* 0 outside the envelope */
+int bsms_small_wgrad(const float* G, const float* S, int64_t R, int64_t D, int S_cols, int S_ld, float* out, int64_t os,
+                     int64_t of, float* colsum /* nullable */, float* colsum_S /* nullable */, void* work, size_t work_bytes,
+                     bsms_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
