@@ -11,7 +11,7 @@
 // caller's stream -- no new arithmetic -- so that a training step costs the host two calls instead of ~60 autograd
 // nodes (the Python mirror of the reference's module tree needed 5.4 ms per step to enqueue what the GPU runs in
 // 7.6 ms at airfoil size and was the limit outright at cylinder size).
-#include "common.h"
+#include "chain.h"
 
 using namespace bsms;
 
@@ -192,10 +192,12 @@ extern "C" int bsms_bsgmp_fwd_p(const bsms_plan_t* const* plans, const float* co
   const float* pos_l[kMaxLevels + 1];
   int64_t pstride_l[kMaxLevels + 1];
   pos_l[0] = pos; pstride_l[0] = pos_batch_stride;
-  // `reuse` (inference only; the caller passes the SAME work buffer as in its previous call and nothing else wrote to
-  // it): bit 0 = the weights have not changed, the packs in `work` are still valid; bit 1 = pos and the mesh have not
-  // changed, the coarse positions in `work` are still valid.  An autoregressive rollout sets both after its first step.
-  const bool packs_ok = !training && (reuse & 1), pos_ok = !training && (reuse & 2);
+  // `reuse`, inference (the caller passes the SAME work buffer as in its previous call and nothing else wrote to it): bit 0 = the
+  // weights have not changed, the packs in `work` are still valid; bit 1 = pos and the mesh have not changed, the coarse
+  // positions in `work` are still valid.  An autoregressive rollout sets both after its first step.
+  // Training: bit 0 = the packs and the cleared bound slots are in `saved` already (a pack group, launched since the weights last
+  // changed and in front of this call in stream order); no prepack is launched and lane 0 is neither forked nor joined.
+  const bool packs_ok = reuse & 1, pos_ok = !training && (reuse & 2);
   SideLane *lane = nullptr, *lane0 = nullptr;
   auto packs_of = [&](int k) { return training ? nullptr : w.packs[k]; };
   for (int i = 0; i < L; ++i) {
@@ -248,6 +250,32 @@ extern "C" int bsms_bsgmp_fwd_p(const bsms_plan_t* const* plans, const float* co
     if ((rc = gmp_fwd_core(plans[d], v.upin[d], pos_l[d], B, D, p, pstride_l[d], hidden, block(params, L + 1 + i, hidden), nxt,
                            v.gmp[L + 1 + i], w.gmp, packs_of(L + 1 + i), false, w.skip[d], st, precision))) return rc;
     cur = nxt;
+  }
+  return BSMS_OK;
+}
+
+// The packs of all 2L + 1 blocks, where bsms_bsgmp_fwd_p (same plans, shape, precision, `saved` / `work`) reads them: in the blocks'
+// saved blobs (training), or in the pack area of `work` (inference, saved == NULL).  Host code only; nothing is added unless every
+// block passes its checks.
+extern "C" int bsms_pack_group_add_bsgmp(bsms_pack_group_t* group, const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p,
+                                         int hidden, const float* const* params, void* saved, void* work, int precision) {
+  PackGroup* g;
+  int rc = pack_group_open(group, "pack_group_add_bsgmp", &g);
+  if (rc) return rc;
+  Shape s;
+  if ((rc = make_shape(plans, L, B, D, p, hidden, &s, "pack_group_add_bsgmp"))) return rc;
+  BSMS_REQUIRE(precision == BSMS_F32 || precision == BSMS_BF16 || precision == BSMS_BF16_NODES, BSMS_E_UNSUPPORTED, "pack_group_add_bsgmp: precision %d", precision);
+  s.prec = precision;
+  BSMS_REQUIRE(params != nullptr && (saved != nullptr || work != nullptr), BSMS_E_INVALID_ARG, "pack_group_add_bsgmp: null argument");
+  const bool training = saved != nullptr;
+  for (int pass = 0; pass < 2; ++pass) {   // every block is checked before the first one is added (the carvers only add up sizes)
+    Work w = carve_work(work, s);
+    Saved v = carve_saved(saved, s, training);
+    for (int k = 0; k <= 2 * L; ++k) {
+      const int lv = level_of_block(k, L);
+      if ((rc = gmp_pack_group_add(pass ? g : nullptr, B, s.N[lv], s.E[lv], D, p, hidden, block(params, k, hidden), v.gmp[k], w.gmp,
+                                   training ? nullptr : w.packs[k], precision))) return rc;
+    }
   }
   return BSMS_OK;
 }

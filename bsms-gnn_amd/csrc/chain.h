@@ -177,6 +177,25 @@ struct PackTable {
 };
 int launch_prepack(const PackTable& t, hipStream_t s);
 
+// Pack group (bsms_pack_group_*): the pack tables of every MLP / GMP block of a training step, concatenated, in ONE launch.
+// The descriptors (13 tables x 21 at the airfoil step: too many for a kernarg) and the list of bound-slot arrays to clear live in
+// device memory, uploaded by the first launch; from then on the group is sealed (a caller whose pointers, shapes or precision
+// change builds a new group).  Every pack comes out byte for byte as launch_prepack writes it: the two kernels share their body.
+struct PackGroup {
+  std::vector<PackDesc> descs;   // `mate` re-based to this list
+  std::vector<float*> zeros;     // kBoundSlots x kBoundWidth floats each
+  int biggest = 0;               // largest N * K of a member (the launch shape)
+  void* dev = nullptr;           // device image: the descriptors, then the pointer list; null until the first launch
+  int device = -1;               // where `dev` lives
+};
+void pack_group_append(PackGroup& g, const PackTable& t);
+int launch_prepack_group(PackGroup& g, hipStream_t s);
+// gmp.hip: the group behind an ABI handle, refused (BSMS_E_INVALID_ARG) when null or sealed; and one GMP block's packs added to a group
+// (arguments as gmp_prepack; `g` == null: the checks only, so that a caller can check every block before it adds the first)
+int pack_group_open(bsms_pack_group_t* group, const char* who, PackGroup** g);
+int gmp_pack_group_add(PackGroup* g, int64_t B, int64_t N, int64_t E, int64_t D, int64_t p, int hidden, const float* const* params,
+                       void* saved, void* work, void* packs_base, int precision);
+
 int launch_chain_fwd(int D, int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s);
 int launch_chain_bwd(int D, int gin_mode, int first_mode, const ChainBwdArgs& a, hipStream_t s);
 // the chain kernels of one width, NB = D / 16 = 2, 4, ... 16: defined in chain_launch.h, instantiated by one translation unit each (chain_d*.hip)

@@ -46,11 +46,25 @@ bool supported_D(int64_t D) { return D % 32 == 0 && D >= 32 && D <= 256; }
 #ifdef BSMS_EXPERIMENTS
 static int env_flags() { const char* e = getenv("BSMS_DEBUG_FLAGS"); return e ? atoi(e) : 0; }
 unsigned long long* g_timing = nullptr;
-int g_debug_flags = env_flags();  // bit0 skip fwd activation stores, bit1 plain (not nt) stores, bit2 nt final y, bit3 no side lanes, ...
+int g_debug_flags = env_flags();  // bit0 skip fwd activation stores, bit1 plain (not nt) stores, bit2 nt final y, bit3 no side lanes, ... bit12 no prepack kernels
 #else
 constexpr unsigned long long* g_timing = nullptr;
 constexpr int g_debug_flags = 0;
 #endif
+
+// The per-call prepack of one table.  Experiment builds, bit 4096 (the ceiling of the pack group, profiles/pack_group_rates.txt): no
+// prepack kernel -- the packs of an earlier step stay where they are, stale but valid -- while the bound slots are still cleared.
+// The bit skips EVERY prepack from the moment it is set: set it with bsms_debug_set_flags after a first step has written the packs,
+// never through BSMS_DEBUG_FLAGS at start-up (the packs would never be written).
+int prepack_table(const PackTable& t, hipStream_t s) {
+#ifdef BSMS_EXPERIMENTS
+  if (g_debug_flags & 4096) {
+    if (t.zero) BSMS_HIP_CHECK(hipMemsetAsync(t.zero, 0, size_t(kBoundSlots) * kBoundWidth * sizeof(float), s));
+    return BSMS_OK;
+  }
+#endif
+  return launch_prepack(t, s);
+}
 
 void add_pack(PackTable& t, const float* W, int ld, int row0, int col0, int N, int K, int kind, float* dst,
               const float* bias = nullptr) {
@@ -231,8 +245,9 @@ GmpSaved locate_saved(void* saved, const GmpWork& wk, int64_t B, int64_t N, int6
                : carve_gmp_saved(wk.gN[0], B, N, E, D, H, false, packs_base, bf, bfn);  // inference: lives in the gradient scratch
 }
 
-int prepack_block(const GmpSaved& sv, int64_t D, int64_t p, int H, bool training, const float* const* params, hipStream_t s,
-                  bool bf = false, bool bfn = false) {
+// THE definition of "which packs a GMP block has" (the per-call prepack and the pack group both build their tables here)
+PackTable block_pack_table(const GmpSaved& sv, int64_t D, int64_t p, int H, bool training, const float* const* params,
+                           bool bf = false, bool bfn = false) {
   const int nl = H + 1;
   const float* const* pn = params;            // mlp_node: W_l = pn[2l], b_l = pn[2l+1]
   const float* const* pe = params + 2 * nl;   // mlp_edge
@@ -272,7 +287,11 @@ int prepack_block(const GmpSaved& sv, int64_t D, int64_t p, int H, bool training
     if (training) { add_pack(t, pn[2 * l], (int)D, 0, 0, (int)D, (int)D, PACK_FRAG_T, sv.n_wt[l]); t.d[t.n - 1].bf16 = bfn; }
   }
   t.zero = training ? sv.bound : nullptr;
-  return launch_prepack(t, s);
+  return t;
+}
+int prepack_block(const GmpSaved& sv, int64_t D, int64_t p, int H, bool training, const float* const* params, hipStream_t s,
+                  bool bf = false, bool bfn = false) {
+  return prepack_table(block_pack_table(sv, D, p, H, training, params, bf, bfn), s);
 }
 }  // namespace
 
@@ -285,6 +304,22 @@ int bsms::gmp_prepack(int64_t B, int64_t N, int64_t E, int64_t D, int64_t p, int
   GmpWork wk = carve_gmp_work(work, B, N, E, D, H);
   GmpSaved sv = locate_saved(saved, wk, B, N, E, D, H, packs_base, precision != BSMS_F32, precision == BSMS_BF16_NODES);
   return prepack_block(sv, D, p, H, saved != nullptr, params, s, precision != BSMS_F32, precision == BSMS_BF16_NODES);
+}
+int bsms::gmp_pack_group_add(PackGroup* g, int64_t B, int64_t N, int64_t E, int64_t D, int64_t p, int H, const float* const* params,
+                             void* saved, void* work, void* packs_base, int precision) {
+  BSMS_REQUIRE(supported_D(D), BSMS_E_UNSUPPORTED, "pack_group_add_bsgmp: latent width D=%lld not supported (a multiple of 32, 32..256)", (long long)D);
+  BSMS_REQUIRE(p >= 1 && p <= 7, BSMS_E_UNSUPPORTED, "pack_group_add_bsgmp: pos_dim=%lld (1..7)", (long long)p);
+  BSMS_REQUIRE(H >= 1 && H < kMaxStages, BSMS_E_UNSUPPORTED, "pack_group_add_bsgmp: hidden=%d (1..%d)", H, kMaxStages - 1);
+  BSMS_REQUIRE(B >= 0, BSMS_E_SHAPE, "pack_group_add_bsgmp: B=%lld", (long long)B);
+  const bool bf = precision != BSMS_F32, bfn = precision == BSMS_BF16_NODES;
+  BSMS_REQUIRE(!bf || ((D == 128 || D == 256) && p <= 3), BSMS_E_UNSUPPORTED, "pack_group_add_bsgmp: bf16 precision needs D = 128 / 256 and pos_dim <= 3");
+  for (int i = 0; i < 4 * (H + 1); ++i)
+    BSMS_REQUIRE(params[i] != nullptr, BSMS_E_INVALID_ARG, "pack_group_add_bsgmp: parameter %d of a block is null", i);
+  if (!g) return BSMS_OK;   // checks only
+  GmpWork wk = carve_gmp_work(work, B, N, E, D, H);
+  GmpSaved sv = locate_saved(saved, wk, B, N, E, D, H, packs_base, bf, bfn);
+  pack_group_append(*g, block_pack_table(sv, D, p, H, saved != nullptr, params, bf, bfn));
+  return BSMS_OK;
 }
 size_t bsms::gmp_saved_bytes_p(int64_t B, int64_t N, int64_t E, int64_t D, int hidden, int precision) {
   if (hidden < 1 || hidden >= kMaxStages) return 0;
@@ -705,6 +740,20 @@ int check_mlp(int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int H, int 
   return BSMS_OK;
 }
 
+// THE definition of "which packs an MLP has" (bsms_mlp_fwd_ex and the pack group)
+PackTable mlp_pack_table(const MlpSaved& sv, MlpKind kind, int64_t in_dim, int64_t D, int H, bool training, const float* const* params) {
+  PackTable t{};
+  const int lfirst = (kind == MLP_SMALL_LN) ? 1 : 0;          // first Linear that runs on the MFMA
+  const int llast = (kind == MLP_ROWS_SMALL) ? H - 1 : H;     // last one
+  if (kind == MLP_SMALL_LN) add_pack(t, params[0], (int)in_dim, 0, 0, (int)D, (int)in_dim, PACK_TRANSPOSE, sv.w0t);
+  for (int l = lfirst; l <= llast; ++l) {
+    add_pack(t, params[2 * l], (int)D, 0, 0, (int)D, (int)D, PACK_FRAG, sv.w[l], params[2 * l + 1]);
+    if (training) add_pack(t, params[2 * l], (int)D, 0, 0, (int)D, (int)D, PACK_FRAG_T, sv.wt[l]);
+  }
+  t.zero = training ? sv.bound : nullptr;
+  return t;
+}
+
 }  // namespace
 
 extern "C" size_t bsms_mlp_saved_bytes(int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int hidden) {
@@ -734,17 +783,10 @@ extern "C" int bsms_mlp_fwd_ex(const float* x, int64_t R, int64_t in_dim, int64_
   const bool training = saved != nullptr;     // saved == NULL: inference (packs live in `work`)
   MlpSaved sv = training ? carve_mlp_saved(saved, R, D, H, true) : carve_mlp_saved(work, R, D, H, false);
 
-  PackTable t{};
   const int lfirst = (kind == MLP_SMALL_LN) ? 1 : 0;          // first Linear that runs on the MFMA
   const int llast = (kind == MLP_ROWS_SMALL) ? H - 1 : H;     // last one
-  if (kind == MLP_SMALL_LN) add_pack(t, params[0], (int)in_dim, 0, 0, (int)D, (int)in_dim, PACK_TRANSPOSE, sv.w0t);
-  for (int l = lfirst; l <= llast; ++l) {
-    add_pack(t, params[2 * l], (int)D, 0, 0, (int)D, (int)D, PACK_FRAG, sv.w[l], params[2 * l + 1]);
-    if (training) add_pack(t, params[2 * l], (int)D, 0, 0, (int)D, (int)D, PACK_FRAG_T, sv.wt[l]);
-  }
-  t.zero = training ? sv.bound : nullptr;
-  BSMS_REQUIRE(!(flags & BSMS_MLP_REUSE_PACKS) || !training, BSMS_E_INVALID_ARG, "mlp_fwd: BSMS_MLP_REUSE_PACKS is an inference flag (saved must be NULL)");
-  if (!(flags & BSMS_MLP_REUSE_PACKS) && (rc = launch_prepack(t, s))) return rc;
+  // BSMS_MLP_REUSE_PACKS: the packs are there already (and, in training, the bound slots cleared): an earlier inference call, or a pack group
+  if (!(flags & BSMS_MLP_REUSE_PACKS) && (rc = prepack_table(mlp_pack_table(sv, kind, in_dim, D, H, training, params), s))) return rc;
 
   ChainFwdArgs a{};
   a.R = R; a.x = x;
@@ -765,6 +807,49 @@ extern "C" int bsms_mlp_fwd_ex(const float* x, int64_t R, int64_t in_dim, int64_
   }
   a.yln = training ? sv.yln : nullptr; a.rstd = training ? sv.rstd : nullptr;
   return launch_chain_fwd((int)D, kind == MLP_SMALL_LN ? IN_SMALL : IN_ROWS, OUT_LN, a, s);
+}
+
+// ================================================================================== pack groups
+struct bsms_pack_group {
+  PackGroup g;
+};
+
+extern "C" int bsms_pack_group_create(bsms_pack_group_t** out) {
+  BSMS_REQUIRE(out != nullptr, BSMS_E_INVALID_ARG, "pack_group_create: null argument");
+  *out = new bsms_pack_group();   // host state only: the device image is made by the first launch
+  return BSMS_OK;
+}
+
+extern "C" void bsms_pack_group_destroy(bsms_pack_group_t* group) {
+  if (!group) return;
+  if (group->g.dev) (void)hipFree(group->g.dev);   // waits for a launch still reading the tables
+  delete group;
+}
+
+int bsms::pack_group_open(bsms_pack_group_t* group, const char* who, PackGroup** g) {
+  BSMS_REQUIRE(group != nullptr, BSMS_E_INVALID_ARG, "%s: the group is null", who);
+  BSMS_REQUIRE(group->g.dev == nullptr, BSMS_E_INVALID_ARG, "%s: the group has been launched and is sealed (other pointers, shapes or "
+               "precision: build a new group)", who);
+  *g = &group->g;
+  return BSMS_OK;
+}
+
+extern "C" int bsms_pack_group_add_mlp(bsms_pack_group_t* group, int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int H,
+                                       int layer_norm, const float* const* params, void* saved, void* work) {
+  PackGroup* g;
+  int rc = pack_group_open(group, "pack_group_add_mlp", &g);
+  if (rc || (rc = check_mlp(R, in_dim, D, out_dim, H, layer_norm, "pack_group_add_mlp"))) return rc;
+  BSMS_REQUIRE(params != nullptr && (saved != nullptr || work != nullptr), BSMS_E_INVALID_ARG, "pack_group_add_mlp: null argument");
+  for (int i = 0; i < 2 * (H + 1); ++i) BSMS_REQUIRE(params[i] != nullptr, BSMS_E_INVALID_ARG, "pack_group_add_mlp: parameter %d is null", i);
+  const bool training = saved != nullptr;
+  MlpSaved sv = training ? carve_mlp_saved(saved, R, D, H, true) : carve_mlp_saved(work, R, D, H, false);
+  pack_group_append(*g, mlp_pack_table(sv, mlp_kind(in_dim, D, out_dim, layer_norm), in_dim, D, H, training, params));
+  return BSMS_OK;
+}
+
+extern "C" int bsms_pack_group_launch(bsms_pack_group_t* group, bsms_stream_t stream) {
+  BSMS_REQUIRE(group != nullptr, BSMS_E_INVALID_ARG, "pack_group_launch: the group is null");
+  return launch_prepack_group(group->g, as_stream(stream));
 }
 
 extern "C" int bsms_mlp_bwd(const float* x, const float* grad_y, int64_t R, int64_t in_dim, int64_t D, int64_t out_dim,

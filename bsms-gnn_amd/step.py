@@ -5,7 +5,7 @@ Why: the autograd mirror of the reference (model.py / ops.py) spends ~40 tiny el
 normaliser and the loss, re-creates ~190 gradient views and pointer tables in Python every backward, and cannot be
 captured in a HIP graph.  Here the step is
 
-    bsms_sim_prologue -> bsms_mlp_fwd (encode) -> bsms_bsgmp_fwd (process) -> bsms_mlp_fwd (decode) -> bsms_sim_epilogue
+    bsms_pack_group_launch -> bsms_sim_prologue -> bsms_mlp_fwd (encode) -> bsms_bsgmp_fwd (process) -> bsms_mlp_fwd (decode) -> bsms_sim_epilogue
     [data parallel: all-reduce of the two loss sums]
     bsms_sim_loss_bwd -> bsms_mlp_bwd (decode) -> bsms_bsgmp_bwd (process) -> bsms_mlp_bwd (encode)
     [data parallel: all-reduce of the flat gradient buffer]
@@ -14,6 +14,13 @@ with every weight gradient written straight into its slot of the flat gradient b
 parameters' `.grad` alias.  Same kernels as the autograd path for everything but the glue: U-Net / MLP gradients are
 bit-identical to it, the loss and its gradient agree to fp32 round-off (tests/test_hip_training.py).  With
 `use_graph=True` the two halves are captured into HIP graphs and replayed (inputs are copied into static buffers).
+
+The weights change once per step, so the step packs them once: ONE bsms_pack_group_launch at its head writes the weight packs of the
+encoder, every U-Net block and the decoder (and clears their bound slots) straight into the saved buffers, and the three forwards run
+with their `reuse` flags -- instead of 13 prepack launches inside them.  A group belongs to one set of pointer tables and
+buffers, and building one costs an allocation and blocking copies: it is built only when a step meets the tables and buffers of the step
+before it.  While they keep changing (a new mesh combination every step) the forwards pack per call, as they always did, and the host
+never waits for the device.
 
 `unroll=K > 1` trains on K autoregressive steps: K forwards, each with its own saved activations, chained by
 the rollout rule (bsms_sim_epilogue's `next_in`), then K backwards in reverse order; bsms_sim_unroll_bwd carries the gradient
@@ -28,6 +35,7 @@ Frozen parameters: an MLP -- encoder, decoder, a block's node o
 `requires_grad == False` gets NULL entries in the gradient tables; the backward then launches nothing for its weight gradients.
 With nothing trainable (or `param_grad=False`) and `input_grad=True` the backward is data-only."""
 import os
+import sys
 
 import torch
 import torch.distributed as dist
@@ -122,6 +130,8 @@ class FusedStep:
         self._obj_w = None                          # the channel weights on the device (fp64 [C]), or None for unit weights
         self._gscratch, self._wts = None, None     # unroll > 1: scratch flat gradient buffer (GradBuckets layout), weights on the device
         self._shape_key, self._graphs, self._ptr_guard = None, None, None
+        self._pg, self._pg_builds = None, 0   # pack group of the current pointer tables and buffers (_pack_group), built lazily; how often
+        self._pg_key, self._use_group = None, False   # tables + buffers of the previous step; this step packs through the group
         self._arena = _Arena()
         self._overlap = None          # bucket schedule of the overlapped gradient all-reduce (_bucket_schedule), built lazily
         self._comm = None             # communication stream the bucket all-reduces are issued from
@@ -142,6 +152,9 @@ class FusedStep:
 
     collectives_at_world_one = False     # tests: issue the step's collectives in a process group of ONE rank as well (a sum over one
                                          # rank is the identity) -- the only way to run the RCCL path on a single-GPU box
+
+    pack_group = True                    # tests and A/B runs: False keeps the per-call prepacks inside the three forwards at every step (13
+                                         # launches per step instead of one); every pack, and so every result, is the same bit for bit
 
     def _world(self):
         w = dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
@@ -217,6 +230,7 @@ class FusedStep:
                 self._tabs_scratch = self._tabs
             self._ptr_guard = guard
             self._graphs = None
+            self._drop_pack_group()
             self._overlap = None                    # the bucket schedule depends on which blocks run side lanes
         return self._tabs
 
@@ -252,7 +266,57 @@ class FusedStep:
             b["ig"] = dict(g_pos=f("g_pos", R, p), grad_in=f("grad_in", B, N, C + p + 1), g_pred=f("g_pred@0", R, C), g_nin=f("g_nin", R, C + 1),
                            pos_work=u8("pos_work", L.bsms_bsgmp_pos_work_bytes(pl, depth, B, p)))
         self._shape_key, self._buf, self._graphs, self._ig_ran = key, b, None, False
+        self._drop_pack_group()
         return b
+
+    # ------------------------------------------------------------------------------------------------ the step's weight packs
+    def _drop_pack_group(self):
+        if getattr(self, "_pg", None) is not None:     # (a graph that captured its launch was dropped with it: _graphs is None here)
+            _abi.lib().bsms_pack_group_destroy(self._pg)
+        self._pg = None
+
+    def __del__(self):
+        if sys is None or sys.is_finalizing():        # interpreter shutdown: the process frees the device
+            return
+        try:
+            self._graphs = None
+            self._drop_pack_group()
+        except Exception:
+            pass
+
+    def _pack_group(self, b, B):
+        """The packs of every buffer set of the step (one set, or the K sets of the unrolled step: the weights are the same for all
+        K forwards) as ONE group: encoder, the 2L+1 blocks, decoder -- where the forwards with `reuse` read them."""
+        if self._pg is not None:
+            return self._pg
+        import ctypes
+        m, L = self.model, _abi.lib()
+        C, p, D, H = m.cfg.out_dim, m.pos_dim, m.cfg.latent_dim, m.cfg.hidden_layer
+        R, t = b["R"], self._tabs
+        h = ctypes.c_void_p()
+        _abi.check(L.bsms_pack_group_create(ctypes.cast(ctypes.byref(h), _abi.PP)), "bsms_pack_group_create")
+        try:
+            for bk in (b.get("steps") or [b]):
+                _abi.check(L.bsms_pack_group_add_mlp(h, R, C + 1, D, D, H, 1, t["enc"][0][0], bk["s_enc"].data_ptr(), None), "bsms_pack_group_add_mlp(encode)")
+                _abi.check(L.bsms_pack_group_add_bsgmp(h, b["pl"], b["depth"], B, D, p, H, t["proc"][0][0], bk["s_proc"].data_ptr(), None,
+                                                       PRECISIONS[b["prec"]]), "bsms_pack_group_add_bsgmp")
+                _abi.check(L.bsms_pack_group_add_mlp(h, R, D, D, C, H, 0, t["dec"][0][0], bk["s_dec"].data_ptr(), None), "bsms_pack_group_add_mlp(decode)")
+        except Exception:
+            L.bsms_pack_group_destroy(h)
+            raise
+        self._pg, self._pg_builds = h, self._pg_builds + 1
+        return h
+
+    def _decide_packs(self):
+        """Once per step, behind _pointer_tables and _buffers: the group serves this step if it exists (those two drop it when anything
+        it points at changes), or if the step before had the same tables and buffers -- then it is worth building.  Captured steps
+        always use it: their graphs are rebuilt with the tables and buffers anyway."""
+        key = (self._ptr_guard, self._shape_key)
+        stable, self._pg_key = key == self._pg_key, key
+        self._use_group = bool(self.pack_group) and (self._pg is not None or stable or self.use_graph)
+
+    def _launch_packs(self, b, B):
+        _abi.check(_abi.lib().bsms_pack_group_launch(self._pack_group(b, B), _stream()), "bsms_pack_group_launch")
 
     def _f64(self, name, dev, *shape):
         n = 1
@@ -268,23 +332,27 @@ class FusedStep:
         return b["osums_all"] if self.unroll > 1 else b["osums"]
 
     # ------------------------------------------------------------------------------------------------ the two halves
-    def _forward(self, b, node_in, tar, mask, ews, B, N, next_in=None, ic=None):
-        """`next_in` / `ic` (unrolled step only): the epilogue also writes the next step's input by the rollout rule."""
+    def _forward(self, b, node_in, tar, mask, ews, B, N, next_in=None, ic=None, pack=True):
+        """`next_in` / `ic` (unrolled step only): the epilogue also writes the next step's input by the rollout rule.
+        `pack=False` (the unrolled step): one group launch in front of the K forwards covers every buffer set."""
         m, L, s = self.model, _abi.lib(), _stream()
         C, p, D, H = m.cfg.out_dim, m.pos_dim, m.cfg.latent_dim, m.cfg.hidden_layer
         R, t = b["R"], self._tabs
         work = b["work"]                      # owned scratch: the launches are ordered on one stream, also under capture
         ni, no = m._inputNormalizer, m._targetNormalizer
         ck = _abi.check
+        reuse = 1 if self._use_group else 0   # BSMS_MLP_REUSE_PACKS / bit 0 of bsms_bsgmp_fwd_p's `reuse`
+        if pack and reuse:                    # head of the caller's stream: every pack of the step, every bound slot cleared
+            self._launch_packs(b, B)
         ck(L.bsms_sim_prologue(node_in.data_ptr(), R, C, p, ni._E_data.data_ptr(), ni._E_data_squared.data_ptr(),
                                ni.std_eps.data_ptr(), b["norm_in"].data_ptr(), b["pos"].data_ptr(), s), "bsms_sim_prologue")
-        ck(L.bsms_mlp_fwd(b["norm_in"].data_ptr(), R, C + 1, D, D, H, 1, t["enc"][0][0], b["h0"].data_ptr(), b["s_enc"].data_ptr(),
-                          work.data_ptr(), s), "bsms_mlp_fwd(encode)")
+        ck(L.bsms_mlp_fwd_ex(b["norm_in"].data_ptr(), R, C + 1, D, D, H, 1, t["enc"][0][0], b["h0"].data_ptr(), b["s_enc"].data_ptr(),
+                             work.data_ptr(), reuse, s), "bsms_mlp_fwd(encode)")
         ewp, keep = _abi.ptr_array([e.data_ptr() for e in ews])
         ck(L.bsms_bsgmp_fwd_p(b["pl"], ewp, b["depth"], b["h0"].data_ptr(), b["pos"].data_ptr(), B, D, p, N * p, H, t["proc"][0][0],
-                              b["h1"].data_ptr(), b["s_proc"].data_ptr(), work.data_ptr(), 0, PRECISIONS[b["prec"]], s), "bsms_bsgmp_fwd")
-        ck(L.bsms_mlp_fwd(b["h1"].data_ptr(), R, D, D, C, H, 0, t["dec"][0][0], b["norm_pred"].data_ptr(), b["s_dec"].data_ptr(),
-                          work.data_ptr(), s), "bsms_mlp_fwd(decode)")
+                              b["h1"].data_ptr(), b["s_proc"].data_ptr(), work.data_ptr(), reuse, PRECISIONS[b["prec"]], s), "bsms_bsgmp_fwd")
+        ck(L.bsms_mlp_fwd_ex(b["h1"].data_ptr(), R, D, D, C, H, 0, t["dec"][0][0], b["norm_pred"].data_ptr(), b["s_dec"].data_ptr(),
+                             work.data_ptr(), reuse, s), "bsms_mlp_fwd(decode)")
         if self._obj is None:
             ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), tar.data_ptr(), R, C, p,
                                    no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["pred"].data_ptr(),
@@ -371,6 +439,7 @@ class FusedStep:
         plans = [*plans, bottom]
         self._pointer_tables()
         b = self._buffers(B, N, plans, node_in.device)
+        self._decide_packs()
         world = self._world()
         if self.unroll > 1:
             return self._unrolled(b, node_in, tar, mask, later_targets, ews, B, N, world, consistent)
@@ -444,10 +513,13 @@ class FusedStep:
         later = self._later(later, node_in, consistent)
         steps = self._unroll_buffers(b, B, N, node_in.device)
         tars = [tar, *(later[k] for k in range(K - 1))]
+        if self._use_group:
+            self._launch_packs(b, B)                      # the weights are fixed across the K forwards: every set's packs in ONE launch
         # K forwards: step k's epilogue writes in_{k+1} = where(mask == 0, in_0, cat[pred_k, mesh_pos | type])
         for k, bk in enumerate(steps):
             nxt = steps[k + 1]["in"] if k + 1 < K else None
-            self._forward(bk, node_in if k == 0 else bk["in"], tars[k], mask, ews, B, N, next_in=nxt, ic=None if nxt is None else node_in)
+            self._forward(bk, node_in if k == 0 else bk["in"], tars[k], mask, ews, B, N, next_in=nxt, ic=None if nxt is None else node_in,
+                          pack=False)
         if world > 1:
             dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
         # K backwards, k = K-1 .. 0.  The first one run writes grads.flat itself, the others the scratch buffer, folded in after

@@ -204,14 +204,40 @@ int bsms_mlp_bwd(const float* x, const float* grad_y, int64_t R, int64_t in_dim,
                  int64_t out_dim, int hidden, int layer_norm, const float* const* params,
                  const void* saved, void* work, float* grad_x /* nullable */,
                  float* const* grads, bsms_stream_t stream);
-/* bsms_mlp_fwd with `flags`.  BSMS_MLP_REUSE_PACKS (inference only, saved = NULL): the weight packs written into `work` by
+/* bsms_mlp_fwd with `flags`.  BSMS_MLP_REUSE_PACKS, inference (saved = NULL): the weight packs written into `work` by
  * the previous bsms_mlp_fwd / _ex call with the same shape and the same parameter VALUES are still there (a private
  * `work` buffer of an autoregressive caller: utils/rollout_utils.py:49-62 applies the same encoder / decoder every
- * step) -- the prepack launches are skipped. */
+ * step) -- the prepack launches are skipped.  Training (saved != NULL): the packs and the cleared bound slots are in `saved`
+ * already, written by a pack group (bsms_pack_group_launch below) since the parameters last changed. */
 enum { BSMS_MLP_REUSE_PACKS = 1 };
 int bsms_mlp_fwd_ex(const float* x, int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int hidden,
                     int layer_norm, const float* const* params, float* y, void* saved, void* work,
                     int flags, bsms_stream_t stream);
+
+/* ---------------------------------------------------------------- pack groups ---------------
+ * Every forward entry re-lays its weights out for the matrix cores ("prepack") with one small launch per MLP / GMP block: 13 per
+ * training step of the airfoil model, each a latency chain of 23-27 us.  The weights change once per step (at the optimizer), so a
+ * training loop can pack ALL of them with one launch per step instead: build a group once, from the same arguments the forward
+ * calls take, launch it once per step after the optimizer's update, and pass BSMS_MLP_REUSE_PACKS / `reuse` bit 0 to the
+ * forwards.  Every pack, header and cleared bound slot is byte for byte what the forward's own prepack writes.
+ *   create / add_*: host only, no device call.  add_mlp takes the arguments of bsms_mlp_fwd that decide its packs, add_bsgmp
+ *     those of bsms_bsgmp_fwd_p (below); `saved` != NULL: the training layout (packs in `saved`), NULL: the inference layout
+ *     (packs in `work`).  Checked as the forwards check them (BSMS_E_INVALID_ARG: a null group, table, plan or parameter,
+ *     neither `saved` nor `work`; BSMS_E_UNSUPPORTED: width, hidden, pos_dim, MLP shape, precision; BSMS_E_SHAPE: sizes that do
+ *     not fit); a refused call adds nothing.
+ *   launch: the first one uploads the tables (a blocking copy: BSMS_E_INVALID_ARG on a capturing stream) and SEALS the group --
+ *     a later add_* is BSMS_E_INVALID_ARG; when a parameter or buffer pointer, a shape or the precision changes, destroy the
+ *     group and build a new one.  Later launches are one kernel on `stream` and may be captured into a graph (keep the group
+ *     alive as long as the graph).  An empty group launches nothing.
+ *   destroy: waits for the device; NULL is allowed. */
+typedef struct bsms_pack_group bsms_pack_group_t;
+int bsms_pack_group_create(bsms_pack_group_t** out);
+void bsms_pack_group_destroy(bsms_pack_group_t* group);
+int bsms_pack_group_add_mlp(bsms_pack_group_t* group, int64_t R, int64_t in_dim, int64_t D, int64_t out_dim, int hidden,
+                            int layer_norm, const float* const* params, void* saved, void* work);
+int bsms_pack_group_add_bsgmp(bsms_pack_group_t* group, const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p,
+                              int hidden, const float* const* params, void* saved, void* work, int precision);
+int bsms_pack_group_launch(bsms_pack_group_t* group, bsms_stream_t stream);
 
 /* ---------------------------------------------------------------- A4: GMP block -------------
  * GMP.forward (ops/basic.py:48-98) incl. both MLPs, the gathers, the fiber [pos_i-pos_j, |.|]
@@ -278,7 +304,10 @@ int bsms_bsgmp_fwd(const bsms_plan_t* const* plans, const float* const* ew, int 
 /* As bsms_bsgmp_fwd, with `reuse` for INFERENCE calls (saved == NULL) that pass the same `work` buffer as their previous
  * call and let nothing else write to it: bit 0 = the weights are unchanged (skip the weight prepacks), bit 1 = pos and
  * the mesh are unchanged (skip the coarse positions).  The autoregressive rollout (utils/rollout_utils.py:49-62: fixed
- * weights, fixed mesh_pos) sets both from its second step on. */
+ * weights, fixed mesh_pos) sets both from its second step on.
+ * TRAINING calls (saved != NULL) take bit 0 only: the packs of every block and its cleared bound slots are in `saved` already,
+ * written by a pack group (bsms_pack_group_launch) since the weights last changed and ahead of this call in stream order.  No
+ * prepack is launched and the engine's pack lane is neither forked nor joined.  Bit 1 is ignored in training. */
 int bsms_bsgmp_fwd_ex(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
                       int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
                       const float* const* params, float* out, void* saved, void* work, int reuse, bsms_stream_t stream);
