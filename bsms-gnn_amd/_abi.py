@@ -110,6 +110,11 @@ SIGNATURES = {
     "bsms_adamw_work_bytes": (c_size_t, []),
     "bsms_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_float, c_i64, C.c_float, c_void_p, c_void_p, c_void_p]),
+    "bsms_optim_groups_create": (c_int, [c_void_p, c_int, c_i64, PP]),
+    "bsms_optim_groups_destroy": (c_int, [c_void_p]),
+    "bsms_optim_work_bytes": (c_size_t, []),
+    "bsms_optim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
+                                C.c_float, c_i64, C.c_float, c_void_p, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsms_grad_accumulate": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p]),
     "bsms_wgrad_bound_width": (c_size_t, []),
     "bsms_wgrad_work_bytes": (c_size_t, [c_i64, c_int]),
@@ -125,6 +130,11 @@ class WgradJob(C.Structure):
     _fields_ = [("G", c_void_p), ("A", c_void_p), ("dW", c_void_p), ("db", c_void_p), ("R", c_i64),
                 ("ldg", c_int), ("lda", c_int), ("ldw", c_int), ("col0", c_int), ("bf16", c_int),
                 ("g_bound", c_void_p), ("a_bound", c_void_p), ("g_mul", C.c_float), ("a_mul", C.c_float)]
+
+
+class OptimGroup(C.Structure):
+    """bsms_optim_group_t (include/bsms_hip.h)."""
+    _fields_ = [("offset", c_i64), ("count", c_i64), ("lr_scale", C.c_float), ("weight_decay", C.c_float)]
 
 
 _ERRORS = {-1: "BSMS_E_INVALID_ARG", -2: "BSMS_E_SHAPE", -3: "BSMS_E_UNSUPPORTED", -4: "BSMS_E_HIP"}

@@ -33,12 +33,114 @@ class WarmupCosineDecay:
         self.last_epoch += 1
 
 
+def param_groups(model, no_decay_bias=False, lr_scales=None):
+    """Parameter groups for FusedAdamW / Trainer in torch's shape, `[{"params": [...], "lr_scale": s, "weight_decay": wd}, ...]`
+    (a key that is left out takes the optimizer's default).  `no_decay_bias`: every trainable 1-D tensor (biases, LayerNorm
+    weights) gets weight_decay 0.  `lr_scales`: {prefix of named_parameters(): factor on the learning rate}, e.g.
+    {"process": 0.1, "process.bottom_gmp": 0.5}; a prefix ends at a dot or at the end of the name, the longest matching prefix
+    wins, a prefix that matches no trainable parameter raises ValueError.  Parameters no rule touches are not listed: they form
+    the optimizer's default group."""
+    lr_scales = dict(lr_scales or {})
+    for k, f in lr_scales.items():
+        if not (math.isfinite(float(f)) and float(f) >= 0.0):
+            raise ValueError(f"param_groups: lr_scales[{k!r}] = {f!r} is not a finite non-negative factor")
+    hit, by_key = set(), {}
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        best = None
+        for prefix in lr_scales:
+            if (name == prefix or name.startswith(prefix + ".")) and (best is None or len(prefix) > len(best)):
+                best = prefix
+        if best is not None:
+            hit.add(best)
+        scale = float(lr_scales[best]) if best is not None else None
+        no_decay = bool(no_decay_bias) and p.dim() == 1
+        if scale is None and not no_decay:
+            continue
+        by_key.setdefault((scale, no_decay), []).append(p)
+    missing = sorted(set(lr_scales) - hit)
+    if missing:
+        raise ValueError(f"param_groups: lr_scales prefix {missing[0]!r} matches no trainable parameter")
+    out = []
+    for (scale, no_decay), plist in by_key.items():
+        g = {"params": plist}
+        if scale is not None:
+            g["lr_scale"] = scale
+        if no_decay:
+            g["weight_decay"] = 0.0
+        out.append(g)
+    return out
+
+
+def segment_table(grads, groups, weight_decay):
+    """The groups of a FusedAdamW as segments of the flat buffer of `grads` (a GradBuckets): a list of (offset, count, lr_scale,
+    weight_decay), sorted, tiling [0, n) exactly, neighbours with equal hyper-parameters merged.  Parameters no group lists take
+    (1.0, `weight_decay`).  ValueError for a parameter listed twice or one without a slot in `grads` (frozen, or foreign)."""
+    hyper = {}
+    for gi, g in enumerate(groups):
+        unknown = set(g) - {"params", "lr_scale", "weight_decay"}
+        if unknown:
+            raise ValueError(f"FusedAdamW: group {gi}: unknown key {sorted(unknown)[0]!r} (per-group betas / eps are not supported)")
+        scale, wd = float(g.get("lr_scale", 1.0)), float(g.get("weight_decay", weight_decay))
+        if not (math.isfinite(scale) and scale >= 0.0 and math.isfinite(wd) and wd >= 0.0):
+            raise ValueError(f"FusedAdamW: group {gi}: lr_scale = {scale}, weight_decay = {wd} must be finite and >= 0")
+        for p in g["params"]:
+            if p not in grads._slot:
+                raise ValueError(f"FusedAdamW: group {gi} lists a parameter without a gradient slot (frozen, or not of this model)")
+            if p in hyper:
+                raise ValueError(f"FusedAdamW: group {gi} lists a parameter that an earlier group (or this one) lists already")
+            hyper[p] = (scale, wd)
+    segs = []
+    for p in sorted(grads.params, key=lambda q: grads._slot[q][0]):
+        off, n = grads._slot[p]
+        if n == 0:
+            continue
+        scale, wd = hyper.get(p, (1.0, float(weight_decay)))
+        if segs and segs[-1][0] + segs[-1][1] == off and segs[-1][2:] == (scale, wd):
+            segs[-1] = (segs[-1][0], segs[-1][1] + n, scale, wd)
+        else:
+            segs.append((off, n, scale, wd))
+    return segs
+
+
+class _OptimGroups:
+    """Owner of a bsms_optim_groups_t handle (the device copy of a segment table)."""
+
+    def __init__(self, segments, n):
+        import ctypes as C
+        table = (_abi.OptimGroup * len(segments))(*[_abi.OptimGroup(o, c, s, w) for o, c, s, w in segments])
+        h = C.c_void_p()
+        _abi.check(_abi.lib().bsms_optim_groups_create(C.cast(table, C.c_void_p), len(segments), int(n), C.cast(C.byref(h), _abi.PP)),
+                   "bsms_optim_groups_create")
+        self.handle = h
+
+    def __del__(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            try:
+                _abi.lib().bsms_optim_groups_destroy(h)
+            except Exception:  # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
 class FusedAdamW:
     """AdamW over the flat buffers of a GradBuckets (dp.py).  Parameters are re-pointed into one flat fp32
-    array with the gradient buffer's layout, so clip + update are two kernel launches for the whole model."""
+    array with the gradient buffer's layout, so clip + update are two kernel launches for the whole model.
 
-    def __init__(self, grads, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=0.0):
+    Optional (with none of them set the object holds no extra state and `step` calls bsms_adamw_step as ever):
+    `groups` -- torch-style parameter groups with `lr_scale` / `weight_decay` (see `param_groups`); `ema_decay` > 0 -- a flat
+    `ema` buffer with the layout of `flat_p`, updated in the same pass (`ema_warmup`: the decay of call t is
+    min(ema_decay, (1 + t) / (10 + t))); `skip_nonfinite` -- a step whose gradient norm is inf / NaN writes nothing and is
+    counted in a device counter instead (`applied_steps()` / `skipped_steps()`; the bias corrections then follow the applied steps)."""
+
+    def __init__(self, grads, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=0.0, groups=None,
+                 ema_decay=0.0, ema_warmup=True, skip_nonfinite=False):
         self.grads, self.lr, self.betas, self.eps, self.wd, self.max_norm = grads, lr, betas, eps, weight_decay, max_grad_norm
+        ema_decay = float(ema_decay or 0.0)
+        if not 0.0 <= ema_decay <= 1.0:
+            raise ValueError(f"FusedAdamW: ema_decay = {ema_decay} outside [0, 1]")
+        segments = segment_table(grads, groups, weight_decay) if groups is not None else None     # raises before anything is re-pointed
         flat = torch.empty_like(grads.flat)
         for p in grads.params:
             off, n = grads._slot[p]
@@ -50,24 +152,93 @@ class FusedAdamW:
         self.step_count = 0
         self.grad_norm = torch.zeros(1, device=flat.device, dtype=torch.float32)
         self._work = torch.empty(max(int(_abi.lib().bsms_adamw_work_bytes()), 4), dtype=torch.uint8, device=flat.device)
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self.segments, self._groups, self.ema, self.counters = segments, None, None, None
+        if segments:
+            self._groups = _OptimGroups(segments, flat.numel())
+        if ema_decay > 0.0:
+            self.ema = flat.clone()
+        if skip_nonfinite:
+            self.counters = torch.zeros(2, dtype=torch.int64, device=flat.device)
+        if self.extended:
+            self._work = torch.empty(max(int(_abi.lib().bsms_optim_work_bytes()), 4), dtype=torch.uint8, device=flat.device)
+
+    @property
+    def extended(self):
+        """Whether `step` goes through bsms_optim_step (any of groups / EMA / guard is in use)."""
+        return self._groups is not None or self.ema is not None or self.counters is not None
+
+    def ema_decay_at(self, t):
+        """The EMA decay of the step() call after `t` earlier ones (evaluated on the host, handed over as a scalar)."""
+        return min(self.ema_decay, (1.0 + t) / (10.0 + t)) if self.ema_warmup else self.ema_decay
 
     def step(self, lr=None):
         self.step_count += 1
         b1, b2 = self.betas
-        _abi.check(_abi.lib().bsms_adamw_step(
-            self.flat_p.data_ptr(), self.grads.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-            self.flat_p.numel(), float(self.lr if lr is None else lr), b1, b2, self.eps, self.wd, self.step_count,
-            float(self.max_norm), self.grad_norm.data_ptr(), self._work.data_ptr(), torch.cuda.current_stream().cuda_stream),
-            "bsms_adamw_step")
+        if not self.extended:
+            _abi.check(_abi.lib().bsms_adamw_step(
+                self.flat_p.data_ptr(), self.grads.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self.flat_p.numel(), float(self.lr if lr is None else lr), b1, b2, self.eps, self.wd, self.step_count,
+                float(self.max_norm), self.grad_norm.data_ptr(), self._work.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                "bsms_adamw_step")
+        else:
+            guard = self.counters is not None
+            _abi.check(_abi.lib().bsms_optim_step(
+                self.flat_p.data_ptr(), self.grads.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self.flat_p.numel(), None if self._groups is None else self._groups.handle,
+                float(self.lr if lr is None else lr), b1, b2, self.eps, self.wd, 0 if guard else self.step_count, float(self.max_norm),
+                None if self.ema is None else self.ema.data_ptr(), self.ema_decay_at(self.step_count - 1) if self.ema is not None else 0.0,
+                self.counters.data_ptr() if guard else None, self.grad_norm.data_ptr(), self._work.data_ptr(),
+                torch.cuda.current_stream().cuda_stream), "bsms_optim_step")
         bump_param_epoch()           # raw-pointer update: invalidates weight packs cached by ops.InferenceSession
 
+    def applied_steps(self):
+        """Steps that changed the parameters (synchronises: reads the device counter back)."""
+        return int(self.counters[0]) if self.counters is not None else self.step_count
+
+    def skipped_steps(self):
+        """Steps skipped by the non-finite guard (synchronises)."""
+        return int(self.counters[1]) if self.counters is not None else 0
+
+    def ema_model(self, model):
+        """A structural copy of `model` whose trainable parameters are views into `ema`; everything else -- frozen parameters and
+        the normalisers' statistics (Parameter objects that do not require grad) and buffers -- is SHARED with `model`, object for
+        object, so it follows the live model (the normalisers re-assign `.data` while they accumulate).  No copy is made and
+        none is needed later: the views see every `step`."""
+        import copy
+        if self.ema is None:
+            raise ValueError("FusedAdamW.ema_model: no EMA is kept (ema_decay = 0)")
+        memo = {}
+        for p in model.parameters():
+            if p in self.grads._slot:
+                off, n = self.grads._slot[p]
+                memo[id(p)] = torch.nn.Parameter(self.ema[off:off + n].view_as(p), requires_grad=False)
+            else:
+                memo[id(p)] = p
+        for b in model.buffers():
+            memo[id(b)] = b
+        return copy.deepcopy(model, memo)
+
     def state_dict(self):
-        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.step_count}
+        sd = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.step_count}
+        if self.ema is not None:
+            sd["ema"] = self.ema
+        if self.counters is not None:
+            sd["counters"] = self.counters
+        return sd
 
     def load_state_dict(self, sd):
+        """The parameters themselves travel with the model: load them first -- a state without `ema` starts the average from them."""
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.step_count = int(sd["step"])
+        if self.ema is not None:
+            self.ema.copy_(sd["ema"] if "ema" in sd else self.flat_p)
+        if self.counters is not None:
+            if "counters" in sd:
+                self.counters.copy_(sd["counters"])
+            else:
+                self.counters.copy_(torch.tensor([self.step_count, 0], dtype=torch.int64))
 
 
 def usable_cpus():
@@ -149,7 +320,9 @@ class DevicePrefetcher:
 
 class Trainer:
     """src/trainer/trainer.py:9-229.  `model_cfg` needs consistent_mesh, accumulation_steps; `opt_cfg` needs
-    peak_lr, weight_decay, warmup_steps, decay_steps, gnorm_clip (configs/opt/default.yaml).  Optional in `model_cfg`:
+    peak_lr, weight_decay, warmup_steps, decay_steps, gnorm_clip (configs/opt/default.yaml).  Optional in `opt_cfg` (DESIGN.md 4.15;
+    with none set the optimizer is the plain fused AdamW): no_decay_bias, lr_scales (`param_groups`), ema_decay, ema_warmup
+    (`ema_model()`, `get_pred / get_loss / get_error(..., ema=True)`, `{step}_ema_params.pth` in `save`), skip_nonfinite.  Optional in `model_cfg`:
     unroll_steps (default 1: the reference's single-step loss), unroll_weights, unroll_detach -- the loss over that many
     autoregressive steps (step.FusedStep); `iter` then takes `(batch, later_targets)`, what TrajectoryBank(horizon=K) hands out;
     loss_space ("physical" / "normalized"), loss_kind ("rmse" / "mse"), loss_channel_weights -- the training objective
@@ -164,8 +337,13 @@ class Trainer:
         self.objective = Objective.from_cfg(model_cfg)
         self.dp = DataParallel(self.model, unroll=self.unroll, step_weights=getattr(model_cfg, "unroll_weights", None),
                                detach=bool(getattr(model_cfg, "unroll_detach", False)), objective=self.objective)     # world size 1: no collective is issued
+        opt = lambda key, default: getattr(opt_cfg, key, default)
+        no_decay_bias, lr_scales = bool(opt("no_decay_bias", False)), opt("lr_scales", None)
+        groups = param_groups(self.model, no_decay_bias, lr_scales) if (no_decay_bias or lr_scales) else None
         self.optimizer = FusedAdamW(self.dp.grads, lr=opt_cfg.peak_lr, weight_decay=opt_cfg.weight_decay,
-                                    max_grad_norm=opt_cfg.gnorm_clip)
+                                    max_grad_norm=opt_cfg.gnorm_clip, groups=groups, ema_decay=opt("ema_decay", 0.0) or 0.0,
+                                    ema_warmup=bool(opt("ema_warmup", True)), skip_nonfinite=bool(opt("skip_nonfinite", False)))
+        self._ema_model = None
         self.lr_scheduler = WarmupCosineDecay(opt_cfg.peak_lr, opt_cfg.warmup_steps, opt_cfg.decay_steps)
         self.train_step = 0
         _check_host_threads()
@@ -216,26 +394,34 @@ class Trainer:
     def _warming_up(self):
         return self.train_step < self.model_cfg.accumulation_steps
 
-    def _model_forward(self, data):
-        return self.model(data, self.model_cfg.consistent_mesh, self._warming_up())
+    def ema_model(self):
+        """The model with the averaged weights (opt_cfg.ema_decay > 0): FusedAdamW.ema_model of the live one, built once.  Its
+        trainable parameters are views into the optimizer's `ema` buffer, everything else is the live model's: always current."""
+        if self._ema_model is None:
+            self._ema_model = self.optimizer.ema_model(self.model)
+        return self._ema_model
+
+    def _model_forward(self, data, ema=False):
+        return (self.ema_model() if ema else self.model)(data, self.model_cfg.consistent_mesh, self._warming_up())
 
     def get_label_mask(self, data):
         if self.model_cfg.consistent_mesh:
             return data[1], data[2]
         return data[0].y, data[0].mask
 
-    def get_pred(self, data):
-        return self._model_forward(self.move_to_device(data))
+    def get_pred(self, data, ema=False):
+        """`ema=True` (here, in get_loss and in get_error): the averaged weights (`ema_model()`) instead of the live ones."""
+        return self._model_forward(self.move_to_device(data), ema)
 
-    def get_loss(self, data):
+    def get_loss(self, data, ema=False):
         data = self.move_to_device(data)
-        pred = self._model_forward(data)
+        pred = self._model_forward(data, ema)
         tar, mask = self.get_label_mask(data)
         from .objective import masked_loss                    # the default objective: model.masked_rmse, the reference's formula
         std = None if self.objective.space == "physical" else self.model._targetNormalizer.std_with_epsilon()
         return masked_loss(pred, tar, mask, self.objective, std)
 
-    def get_error(self, data, relative=True):
+    def get_error(self, data, relative=True, ema=False):
         """trainer/trainer.py:231-271: (error_mean, error_std) per channel as float32 NumPy arrays [C] -- the masked absolute
         error, divided by each sample's target scale when `relative`.  The reference copies prediction, target and mask to the
         host and reduces there; here one bsms_error_sums launch reduces over the nodes, eval.error_mean_std finishes on the
@@ -248,7 +434,7 @@ class Trainer:
         from .ops import error_sums
         data = self.move_to_device(data)
         with torch.no_grad():
-            pred = self.get_pred(data)
+            pred = self.get_pred(data, ema)
             tar, mask = self.get_label_mask(data)
             rows = pred.shape[-2]
             mean, std = error_mean_std(error_sums(pred.reshape(-1, rows, pred.shape[-1]), tar, mask, rows), rows, relative)
@@ -258,7 +444,10 @@ class Trainer:
     def iter(self, data):
         """One training iteration (trainer.py:134-156): statistics only during warm-up, otherwise
         fwd + loss + bwd (+ gradient all-reduce) + clip + AdamW + LR schedule.  With model_cfg.unroll_steps = K > 1 `data` is
-        `(batch, later_targets)`; the warm-up iterations look at the batch only."""
+        `(batch, later_targets)`; the warm-up iterations look at the batch only.  With opt_cfg.skip_nonfinite a step whose
+        gradient norm is inf / NaN changes nothing on the device (FusedAdamW.skipped_steps() counts it); the non-finite loss is
+        returned as ever and the LR schedule still advances -- what torch does around a skipped GradScaler step -- because
+        the host does not read the decision back."""
         later = None
         if self.unroll > 1:
             if not (isinstance(data, (tuple, list)) and len(data) == 2 and torch.is_tensor(data[1]) and not torch.is_tensor(data[0])):
@@ -281,11 +470,15 @@ class Trainer:
     def save(self, save_dir):
         os.makedirs(save_dir, exist_ok=True)
         torch.save(self.model.state_dict(), f"{save_dir}/{self.train_step}_params.pth")     # reference layout
+        if self.optimizer.ema is not None:                                                  # the averaged weights, same layout
+            torch.save(self.ema_model().state_dict(), f"{save_dir}/{self.train_step}_ema_params.pth")
         torch.save({"opt": self.optimizer.state_dict(), "epoch": self.lr_scheduler.last_epoch, "train_step": self.train_step},
                    f"{save_dir}/{self.train_step}_opt_state.pth")                           # the reference's TODO
 
     def restore(self, save_dir, step, restore_opt_state=True):
         self.model.load_state_dict(torch.load(f"{save_dir}/{step}_params.pth", map_location=self.device))
+        if self.optimizer.ema is not None:          # no optimizer state (or one without `ema`): the average restarts from the parameters
+            self.optimizer.ema.copy_(self.optimizer.flat_p)
         opt_path = f"{save_dir}/{step}_opt_state.pth"
         if restore_opt_state and os.path.exists(opt_path):
             st = torch.load(opt_path, map_location=self.device)

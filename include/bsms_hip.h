@@ -581,6 +581,39 @@ size_t bsms_adamw_work_bytes(void);
 int bsms_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                     float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                     float max_grad_norm, float* grad_norm_out, void* work, bsms_stream_t stream);
+/* The general step: the same pass with parameter groups, an exponential moving average of the weights and a
+ * non-finite guard.  bsms_adamw_step above is unchanged and stays the yardstick: with groups = ema = counters = NULL this entry
+ * writes the same bits, and so does every group with lr_scale = 1 (against the old entry with that group's weight_decay) or
+ * lr_scale = s (against the old entry with lr = the fp32 product lr * s).
+ * GROUPS.  A table of segments of the flat array, each with a factor on the learning rate and its own weight decay.  The handle
+ * owns one small device block, like a plan; bsms_optim_groups_create checks on the host, before any device call, that
+ * 1 <= ngroups <= 4096 and that lr_scale / weight_decay are finite and >= 0 (BSMS_E_INVALID_ARG), that every count >= 1 and
+ * that the groups are sorted by offset and tile [0, n) exactly -- no gap, no overlap, nothing short of or past n (BSMS_E_SHAPE);
+ * *out is NULL after a refusal.  Offsets are arbitrary (no alignment is assumed).  Creation allocates and copies (blocking): it is
+ * not for the data path.  A handle whose n differs from the call's is BSMS_E_SHAPE; with a handle the scalar weight_decay is
+ * not read.  destroy(NULL) is BSMS_OK.
+ * ARITHMETIC per element of group k: lr_k = lr * lr_scale_k (one fp32 product), then bsms_adamw_step's update with lr_k and
+ * wd_k; then, if `ema`, ema = lerp(ema, p_new, 1 - ema_decay) as torch.lerp forms it in fp32: ema + (p_new - ema) * (1 - ema_decay)
+ * when 1 - ema_decay < 0.5, p_new - (p_new - ema) * ema_decay otherwise (ema_decay = 0 copies the parameters and 1 keeps the
+ * average, bit for bit).  ema_decay outside [0, 1] is BSMS_E_INVALID_ARG, also when ema is NULL.
+ * GUARD (counters != NULL: device int64[2] {applied, skipped}).  The norm is always formed (`work` required, max_grad_norm may be
+ * 0).  If it is not finite -- an inf or NaN gradient, or finite gradients whose sum of squares overflows fp32 -- no element of
+ * params / exp_avg / exp_avg_sq / ema is written and counters[1] += 1; otherwise counters[0] += 1.  grad_norm_out receives the
+ * norm either way.  The step number is the device's, t = counters[0] + 1 (bias corrections from t in fp64 on the device, rounded
+ * once to fp32): `step` must be 0 (BSMS_E_INVALID_ARG otherwise).  The counters are updated once per call by a one-thread launch
+ * behind the update.  Without counters: step >= 1 (BSMS_E_SHAPE), as bsms_adamw_step.
+ * No atomics, no allocation, no synchronisation; every element is written by one thread (bit-identical from run to run); the
+ * call captures into a HIP graph; elements past n are never touched; n == 0 launches nothing (and counts nothing).
+ * `work`: bsms_optim_work_bytes() bytes, needed whenever a norm is (clipping, grad_norm_out or the guard). */
+typedef struct bsms_optim_group { int64_t offset, count; float lr_scale, weight_decay; } bsms_optim_group_t;
+typedef struct bsms_optim_groups bsms_optim_groups_t;
+int bsms_optim_groups_create(const bsms_optim_group_t* host_groups, int ngroups, int64_t n, bsms_optim_groups_t** out);
+int bsms_optim_groups_destroy(bsms_optim_groups_t* groups);
+size_t bsms_optim_work_bytes(void);
+int bsms_optim_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                    const bsms_optim_groups_t* groups, float lr, float beta1, float beta2, float eps, float weight_decay,
+                    int64_t step, float max_grad_norm, float* ema, float ema_decay, int64_t* counters,
+                    float* grad_norm_out, void* work, bsms_stream_t stream);
 /* acc[i] = first ? g[i] : acc[i] + g[i] over a flat gradient buffer of n floats (first != 0 overwrites whatever acc held).
  * The weight-gradient kernels overwrite their slots, so every step of an unrolled loss writes a scratch buffer with the
  * layout of the real one and this entry folds it in; fp32 adds in a fixed order, one thread per element.  16-byte accesses
