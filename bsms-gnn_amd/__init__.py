@@ -7,8 +7,8 @@ from .graph import LevelData, LevelPlan, MeshBank, clear_plan_cache, collate_var
 from .model import BSMS_Simulator, Normalizer, masked_rmse  # noqa: F401
 from .objective import Objective, masked_loss  # noqa: F401
 from .ops import BSGMP, GMP, MLP, InferenceSession, Unpool, WeightedEdgeConv, degree, error_sums, scatter_sum  # noqa: F401
-from .eval import error_mean_std  # noqa: F401
-from .databank import TrajectoryBank, epoch_picks  # noqa: F401
+from .eval import equivariance_error, error_mean_std  # noqa: F401
+from .databank import Augment, TrajectoryBank, epoch_picks, transform_rows  # noqa: F401
 from .dp import DataParallel, GradBuckets, global_masked_rmse  # noqa: F401
 from .hierarchy import BistrideMultiLayerGraph, to_flat_edge  # noqa: F401
 from .rollout import RolloutErrors, rank_slice, rollout_bank, rollout_batch, rollout_dataset, rollout_errors, rollout_one_traj, rollout_rmse  # noqa: F401

@@ -100,6 +100,10 @@ SIGNATURES = {
     "bsms_batch_assemble": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, C.c_double, c_void_p, c_i64, C.c_uint64, C.c_uint64,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsms_batch_targets": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p]),
+    "bsms_batch_assemble_xf": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_void_p, C.c_double, c_void_p, c_i64,
+                                       C.c_uint64, C.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsms_rows_transform": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_int, c_void_p, c_i64,
+                                    c_void_p]),
     "bsms_hierarchy_create": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, PP]),
     "bsms_hierarchy_create_f32": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, PP]),
     "bsms_hierarchy_destroy": (c_int, [c_void_p]),

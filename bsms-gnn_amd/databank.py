@@ -11,8 +11,15 @@ in include/bsms_hip.h instead of torch's CPU generator.
 Meshes: with `cfg.consist_mesh` all trajectories share ONE interned hierarchy and `batch` returns the consistent-mesh
 tuple with stride-0 [B,...] index views, so the plan cache hits on every step.  Otherwise every trajectory keeps its
 graph.MeshBank entry (plans and edge weights resident) and `batch` returns the per-level LevelData list of
-`MeshBank.collate`."""
+`MeshBank.collate`.
+
+Frame augmentation (`Augment`, `TrajectoryBank(augment=)`): one rigid transform per sample -- a rotation,
+optionally after a reflection -- applied to the positions and to the vector fields of the state by the same single launch
+(bsms_batch_assemble_xf), before the noise.  `transform_rows` (bsms_rows_transform) applies the same matrices to any other
+row tensor: later targets, predictions, node_in."""
 import ctypes as C
+import dataclasses
+import math
 
 import numpy as np
 import torch
@@ -53,18 +60,124 @@ def pick_lengths(frames, horizon=1):
     return [int(T) - int(horizon) for T in frames]
 
 
+AUGMENT_TAG = 0x58464D54      # third word of the transform generator's seed: keeps its stream apart from every other use of (seed, draw)
+MAX_GROUPS = 4                # vector groups per row (csrc/batch.hip: kMaxVec)
+
+
+@dataclasses.dataclass(frozen=True)
+class Augment:
+    """Which frames a training batch is seen in.  `rotate`: a rotation by an angle uniform in (-max_angle, max_angle) -- in 3-D about
+    a uniformly distributed axis; `reflect`: with probability 1/2 the first coordinate is negated before the rotation (det = -1).
+    `vector_fields`: the output fields whose components turn with the frame; every other channel is a scalar."""
+    rotate: bool = True
+    max_angle: float = math.pi
+    reflect: bool = False
+    vector_fields: tuple = ("velocity",)
+
+    def __post_init__(self):
+        angle = float(self.max_angle)
+        if not 0.0 < angle <= math.pi:
+            raise ValueError(f"Augment: max_angle must be in (0, pi], got {self.max_angle!r}")
+        if isinstance(self.vector_fields, str) or not all(isinstance(n, str) for n in self.vector_fields):
+            raise ValueError(f"Augment: vector_fields must be a sequence of field names, got {self.vector_fields!r}")
+        object.__setattr__(self, "rotate", bool(self.rotate))
+        object.__setattr__(self, "reflect", bool(self.reflect))
+        object.__setattr__(self, "max_angle", angle)
+        object.__setattr__(self, "vector_fields", tuple(self.vector_fields))
+
+    @classmethod
+    def from_cfg(cls, cfg):
+        """The datasets config's optional augment_rotate / augment_max_angle / augment_reflect / vector_fields; None when neither
+        a rotation nor a reflection is asked for."""
+        rotate, reflect = bool(getattr(cfg, "augment_rotate", False)), bool(getattr(cfg, "augment_reflect", False))
+        if not (rotate or reflect):
+            return None
+        return cls(rotate=rotate, max_angle=getattr(cfg, "augment_max_angle", math.pi), reflect=reflect,
+                   vector_fields=tuple(getattr(cfg, "vector_fields", ("velocity",))))
+
+    def sample(self, p, n, seed, draw):
+        """[n, p, p] fp32: the transforms of the `n` samples of batch `draw`, evaluated in fp64 and rounded once.  Sample k takes
+        the k-th four consecutive uniforms of `np.random.default_rng([seed, draw, AUGMENT_TAG])` -- axis height, axis azimuth, angle,
+        reflection -- whatever is switched on, so a sample's frame depends on (seed, draw, k) alone."""
+        p, n = int(p), int(n)
+        if p not in (2, 3):
+            raise ValueError(f"Augment.sample: p must be 2 or 3, got {p}")
+        u = np.random.default_rng([int(seed) & _MASK64, int(draw) & _MASK64, AUGMENT_TAG]).random((n, 4))
+        theta = (2.0 * u[:, 2] - 1.0) * self.max_angle if self.rotate else np.zeros(n)
+        c, s = np.cos(theta), np.sin(theta)
+        q = np.zeros((n, p, p))
+        if p == 2:
+            q[:, 0, 0], q[:, 0, 1], q[:, 1, 0], q[:, 1, 1] = c, -s, s, c
+        else:
+            z, phi = 2.0 * u[:, 0] - 1.0, 2.0 * np.pi * u[:, 1]
+            rad = np.sqrt(np.maximum(1.0 - z * z, 0.0))
+            k = np.stack([rad * np.cos(phi), rad * np.sin(phi), z], -1)                # unit axis, uniform on the sphere
+            cross = np.zeros((n, 3, 3))
+            cross[:, 0, 1], cross[:, 0, 2], cross[:, 1, 0] = -k[:, 2], k[:, 1], k[:, 2]
+            cross[:, 1, 2], cross[:, 2, 0], cross[:, 2, 1] = -k[:, 0], -k[:, 1], k[:, 0]
+            q = c[:, None, None] * np.eye(3) + s[:, None, None] * cross + (1.0 - c)[:, None, None] * (k[:, :, None] * k[:, None, :])
+        if self.reflect:
+            q[:, :, 0] = np.where((u[:, 3] < 0.5)[:, None], -q[:, :, 0], q[:, :, 0])   # Q = R diag(-1, 1, ..): x -> -x, then R
+        return np.ascontiguousarray(q, dtype=np.float32)
+
+
+def _host_transforms(transforms, n, p=None):
+    """`transforms` (tensor or array) as a contiguous host fp32 [n, p, p]."""
+    if torch.is_tensor(transforms):
+        transforms = transforms.detach().cpu().numpy()
+    xf = np.ascontiguousarray(transforms, dtype=np.float32)
+    if xf.ndim != 3 or xf.shape[0] != n or xf.shape[1] != xf.shape[2] or (p is not None and xf.shape[1] != p) or xf.shape[1] not in (2, 3):
+        raise ValueError(f"transforms must be [{n}, p, p] with p = {p if p is not None else '2 or 3'}, got {tuple(xf.shape)}")
+    return xf
+
+
+def transform_rows(x, rows_per_sample, transforms, groups, inverse=False, out=None):
+    """Q v (Q^T v with `inverse`) on every vector group of the rows of `x`, one matrix per sample (bsms_rows_transform; arithmetic and
+    rounding order in include/bsms_hip.h).  `x`: device fp32, contiguous, [R,C], [B,N,C] or [F,R,C]; `rows_per_sample`: an int (every
+    sample has that many rows) or one row count per sample; `transforms` [n,p,p] (host or device); `groups`: the first channel of
+    every group.  A 3-D `x` is B samples of N rows when B * N is the table's row count and N alone is not; otherwise it is F frames
+    of R rows cut by the same table.  Rows past the table stay as they are.  `out=x` works in place; None allocates."""
+    n = int(transforms.shape[0])
+    xf = _host_transforms(transforms, n)
+    rows = [int(rows_per_sample)] * n if isinstance(rows_per_sample, (int, np.integer)) else [int(r) for r in rows_per_sample]
+    if len(rows) != n:
+        raise ValueError(f"transform_rows: {len(rows)} row counts for {n} transforms")
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() in (2, 3)):
+        raise ValueError("transform_rows: x must be a contiguous fp32 device tensor [R,C], [B,N,C] or [F,R,C]")
+    total, width = sum(rows), int(x.shape[-1])
+    if x.dim() == 2 or (x.shape[0] * x.shape[1] == total and x.shape[1] != total):
+        frames, per_frame = 1, x.numel() // width
+    else:
+        frames, per_frame = int(x.shape[0]), int(x.shape[1])
+    if total > per_frame:
+        raise ValueError(f"transform_rows: the samples hold {total} rows, x of shape {tuple(x.shape)} has {per_frame}")
+    if out is None:
+        out = torch.empty_like(x) if total == per_frame else x.clone()
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape):
+        raise ValueError("transform_rows: out must be a contiguous fp32 device tensor of x's shape")
+    first = (C.c_int32 * max(len(groups), 1))(*[int(g) for g in groups])
+    table = (C.c_int64 * n)(*rows)
+    with torch.cuda.device(x.device):
+        _abi.check(_abi.lib().bsms_rows_transform(x.data_ptr(), out.data_ptr(), frames, per_frame, width, C.addressof(table), n, xf.shape[1],
+                                                  xf.ctypes.data, 1 if inverse else 0, C.addressof(first), len(groups),
+                                                  torch.cuda.current_stream(x.device).cuda_stream), "bsms_rows_transform")
+    return out
+
+
 class _Traj:
     __slots__ = ("state", "pos", "type", "pos_static", "type_static", "T", "N", "entry")
 
 
 class TrajectoryBank:
     """`cfg`: what datapipe.TrajectoryDataset takes (field_names, output_field_names, consist_mesh, unet_depth, mesh_type,
-    noise_level, noise_gamma).  `process`: the model's BSGMP, needed for variable meshes only (it builds the per-mesh plans).
+    noise_level, noise_gamma, and optionally augment_rotate / augment_max_angle / augment_reflect / vector_fields).  `process`: the model's BSGMP, needed for variable meshes only (it builds the per-mesh plans).
     `horizon` = K > 1 serves an unrolled loss over K steps: a pick (trajectory, t) then needs the frames t+1 .. t+K, so the epoch
-    order stops K frames before the end, and `batch` also returns the later targets (frames t+2 .. t+K, without noise)."""
+    order stops K frames before the end, and `batch` also returns the later targets (frames t+2 .. t+K, without noise).
+    `augment` (None: `Augment.from_cfg(cfg)`, which is None for a config without the keys): training batches are seen in a
+    freshly drawn frame per sample; evaluation batches, `trajectory` and the rollouts stay in the data's frame."""
 
     def __init__(self, cfg, dataset="airfoil", device=None, seed=0, process=None, max_bytes=None, order="trajectory", cache_dir=None,
-                 horizon=1):
+                 horizon=1, augment=None):
         if dataset not in VALID_TYPES:
             raise ValueError(f"dataset must be one of {sorted(VALID_TYPES)}, got {dataset!r}")
         if order not in ("trajectory", "global"):
@@ -72,6 +185,14 @@ class TrajectoryBank:
         if int(horizon) < 1:
             raise ValueError(f"horizon must be >= 1, got {horizon}")
         self.cfg, self.dataset, self.order, self.cache_dir, self.horizon = cfg, dataset, order, cache_dir, int(horizon)
+        self.augment = Augment.from_cfg(cfg) if augment is None else augment
+        if not (self.augment is None or isinstance(self.augment, Augment)):
+            raise ValueError(f"TrajectoryBank: augment must be an Augment or None, got {type(augment).__name__}")
+        # vector groups: the bank's own Augment names them; without one an explicit `transforms=` goes by the config (or "velocity")
+        self._vector_fields = self.augment.vector_fields if self.augment is not None else tuple(getattr(cfg, "vector_fields", ("velocity",)))
+        self.fields, self._groups, self._group_error = None, None, None      # set by the first `add`
+        if self.augment is not None:
+            self._check_vector_names()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise _abi.BsmsError("TrajectoryBank needs a GPU device: trajectories are resident in HBM")
@@ -110,6 +231,44 @@ class TrajectoryBank:
         self._claim(t.numel() * t.element_size())
         return _upload(t, self.device)
 
+    def _check_vector_names(self):
+        names = list(self._vector_fields)
+        for name in names:
+            if name not in self.cfg.output_field_names:
+                raise ValueError(f"vector field {name!r} is not one of cfg.output_field_names {list(self.cfg.output_field_names)}")
+        if len(set(names)) != len(names) or len(names) > MAX_GROUPS:
+            raise ValueError(f"vector_fields must be at most {MAX_GROUPS} different names, got {names}")
+
+    def _record_fields(self, fields, p):
+        """Channel offset and width of every output field; the named vector fields become the groups of the transform."""
+        layout, off = {}, 0
+        for k in self.cfg.output_field_names:
+            layout[k] = (off, int(fields[k].shape[-1]))
+            off += layout[k][1]
+        if self.fields is None:
+            self.fields = layout
+            try:
+                self._check_vector_names()
+                for name in self._vector_fields:
+                    if layout[name][1] != p:
+                        raise ValueError(f"vector field {name!r} has {layout[name][1]} components, the positions have {p}")
+                first = [layout[name][0] for name in self._vector_fields]
+                self._groups = (tuple(first), (C.c_int32 * max(len(first), 1))(*first))
+            except ValueError as e:
+                if self.augment is not None:
+                    self.fields = None
+                    raise
+                self._group_error = str(e)          # no augmentation asked for: only an explicit `transforms=` would need the groups
+        elif layout != self.fields and self.augment is not None:
+            raise ValueError(f"TrajectoryBank.add: output fields laid out as {layout}, the bank holds {self.fields}")
+
+    @property
+    def vector_groups(self):
+        """First channel of every vector group of the state (what `transform_rows` takes as `groups`)."""
+        if self._group_error is not None:
+            raise ValueError(self._group_error)
+        return () if self._groups is None else self._groups[0]
+
     def add(self, source):
         """Upload ONE trajectory (a path or a dict, read through datapipe.load_fields).  Returns its index."""
         cfg = self.cfg
@@ -131,6 +290,7 @@ class TrajectoryBank:
             raise ValueError(f"TrajectoryBank.add: {state.shape[-1]} state channels, cfg.noise_level has {len(cfg.noise_level)}")
         if typ.shape[-1] != 1:
             raise ValueError(f"TrajectoryBank.add: node_type must be [T,N,1], got {tuple(typ.shape)}")
+        self._record_fields(fields, int(pos.shape[-1]))
         tr.pos_static, tr.type_static = bool((pos == pos[:1]).all()), bool((typ == typ[:1]).all())
         tr.entry = None
         if cfg.consist_mesh:
@@ -162,7 +322,8 @@ class TrajectoryBank:
         return [self.add(s) for s in sources[lo:hi]]
 
     # ------------------------------------------------------------------------------------------------ batches
-    def _assemble(self, picks, noisy, draw, return_noise, horizon=1):
+    def _assemble(self, picks, noisy, draw, return_noise, horizon=1, xf=None):
+        """`xf`: host fp32 [len(picks), p, p] or None.  None makes exactly the calls of a bank without augmentation."""
         cfg = self.cfg
         n_c, table = len(self._std), (_Sample * len(picks))()
         p, rows = None, 0
@@ -187,10 +348,27 @@ class TrajectoryBank:
         node_in, node_tar, node_mask = new(n_c + p + 1), new(n_c), new(1)
         noise = new(n_c) if return_noise else None
         later = torch.empty(horizon - 1, rows, n_c, device=self.device, dtype=torch.float32) if horizon > 1 else None
+        if xf is not None:
+            groups, first = self.vector_groups, self._groups[1]
+            if xf.shape != (len(picks), p, p):
+                raise ValueError(f"TrajectoryBank: transforms must be [{len(picks)}, {p}, {p}], got {tuple(xf.shape)}")
         with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
             if later is not None:
                 _abi.check(_abi.lib().bsms_batch_targets(C.addressof(table), len(picks), n_c, horizon - 1, later.data_ptr(),
                                                          torch.cuda.current_stream(self.device).cuda_stream), "bsms_batch_targets")
+                if xf is not None:                  # the later targets in the frame of their sample: in place, same matrices
+                    seg = (C.c_int64 * len(picks))(*[table[k].n for k in range(len(picks))])
+                    _abi.check(_abi.lib().bsms_rows_transform(later.data_ptr(), later.data_ptr(), horizon - 1, rows, n_c, C.addressof(seg),
+                                                              len(picks), p, xf.ctypes.data, 0, C.addressof(first), len(groups), stream),
+                               "bsms_rows_transform")
+            if xf is not None:
+                _abi.check(_abi.lib().bsms_batch_assemble_xf(
+                    C.addressof(table), len(picks), n_c, p, xf.ctypes.data, C.addressof(first), len(groups),
+                    C.addressof(self._std) if noisy else None, float(cfg.noise_gamma), C.addressof(self._valid), len(self._valid), self.seed,
+                    int(draw) & _MASK64, node_in.data_ptr(), node_tar.data_ptr(), node_mask.data_ptr(),
+                    None if noise is None else noise.data_ptr(), stream), "bsms_batch_assemble_xf")
+                return node_in, node_tar, node_mask, noise, later
             _abi.check(_abi.lib().bsms_batch_assemble(
                 C.addressof(table), len(picks), n_c, p, C.addressof(self._std) if noisy else None, float(cfg.noise_gamma),
                 C.addressof(self._valid), len(self._valid), self.seed, int(draw) & _MASK64, node_in.data_ptr(), node_tar.data_ptr(),
@@ -205,14 +383,18 @@ class TrajectoryBank:
             v = self._views[B] = ([g.unsqueeze(0).expand(B, *g.shape) for g in m_gs], [i.unsqueeze(0).expand(B, *i.shape) for i in m_ids])
         return v
 
-    def batch(self, picks, train=True, draw=None, return_noise=False, horizon=None):
+    def batch(self, picks, train=True, draw=None, return_noise=False, horizon=None, transforms=None, return_transforms=False):
         """The device batch of `picks`, a list of (trajectory, frame).  `train`: inject the training noise; `draw` selects the
         noise of this batch (None: the bank's running batch counter, which then advances).  Consistent mesh:
         [node_in [B,N,C+p+1], node_tar [B,N,C], node_mask [B,N,1], m_gs, m_ids]; variable meshes: the per-level LevelData list.
         `return_noise` appends the noise tensor that was added ([B,N,C] / [rows,C]; zeros when `train` is false).
         `horizon` (None: the bank's) = K > 1 returns (batch, later) -- or (batch, later, noise) -- with the targets of the steps after
         the first, later [K-1,B,N,C] / [K-1,rows,C] = frames t+2 .. t+K as they are resident: the noise (and its `gamma` correction
-        of node_tar) belongs to the first step alone, whose tensors are bit-equal to those of horizon = 1 for the same draw."""
+        of node_tar) belongs to the first step alone, whose tensors are bit-equal to those of horizon = 1 for the same draw.
+        Frames: a bank with an `augment` sees a `train` batch through `augment.sample(p, B, seed, draw)`, one matrix per pick,
+        applied before the noise to positions and vector fields, and to the later targets; `train=False` stays in the data's frame.
+        `transforms` [B,p,p] (tensor or array) is applied instead, whatever `train` says and with or without an `augment`.
+        `return_transforms` appends the host fp32 array that was applied (None when the batch is in the data's frame)."""
         horizon = self.horizon if horizon is None else int(horizon)
         if horizon < 1:
             raise ValueError(f"horizon must be >= 1, got {horizon}")
@@ -221,7 +403,12 @@ class TrajectoryBank:
             raise ValueError("TrajectoryBank.batch: no picks")
         if draw is None:
             draw, self._draw = self._draw, self._draw + 1
-        node_in, node_tar, node_mask, noise, later = self._assemble(picks, bool(train), draw, return_noise, horizon)
+        xf = None
+        if transforms is not None:
+            xf = _host_transforms(transforms, len(picks))
+        elif self.augment is not None and train:
+            xf = self.augment.sample(self._trajs[picks[0][0]].pos.shape[-1], len(picks), self.seed, draw)
+        node_in, node_tar, node_mask, noise, later = self._assemble(picks, bool(train), draw, return_noise, horizon, xf)
         if self.cfg.consist_mesh:
             B, N = len(picks), self._hier[2]
             m_gs, m_ids = self._hier_views(B)
@@ -230,9 +417,8 @@ class TrajectoryBank:
             later = None if later is None else later.view(horizon - 1, B, N, -1)
         else:
             out = self._meshes.assemble([self._trajs[si].entry for si, _ in picks], node_in, node_tar, node_mask)
-        if later is not None:
-            return (out, later, noise) if return_noise else (out, later)
-        return (out, noise) if return_noise else out
+        extra = ([later] if later is not None else []) + ([noise] if return_noise else []) + ([xf] if return_transforms else [])
+        return (out, *extra) if extra else out
 
     def next_picks(self, B):
         """The next `B` picks of the epoch order (fewer at the end of an epoch, like a loader without drop_last)."""

@@ -29,3 +29,42 @@ def error_mean_std(sums, rows_per_segment, relative=True):
     mean = (AE / scale).sum(0) / count
     e2 = (SE / scale ** 2).sum(0) / count
     return mean, torch.sqrt(torch.clamp(e2 - mean ** 2, min=0.0))
+
+
+def equivariance_error(model, batch, transforms, groups, rows_per_sample=None):
+    """How far `model` is from commuting with a change of frame, per channel, as a relative RMS difference (fp64 [C]):
+
+        pred   = model(batch)
+        pred_q = model(batch seen through `transforms`)          state groups and the position columns of node_in, Q v
+        back   = Q^T pred_q on the same groups
+        err_c  = sqrt( sum m (back_c - pred_c)^2 / sum m pred_c^2 )      over all unmasked rows of the batch
+
+    Exactly 0 for identity matrices; 0 up to rounding for an equivariant model.  `model` is a Trainer (anything with
+    `get_pred(batch)`); `batch` a consistent-mesh device batch [node_in [B,N,C+p+1], node_tar, node_mask, ..] or the per-level
+    list of variable meshes, for which `rows_per_sample` lists the nodes of every sample; `transforms` [B,p,p]; `groups` the first
+    channel of every vector group of the state (`TrajectoryBank.vector_groups`).  The reduction is `ops.error_sums`; nothing but
+    the C results leaves the device."""
+    from .databank import transform_rows
+    from .graph import LevelData
+    from .ops import error_sums
+    levels = isinstance(batch[0], LevelData)
+    node_in, node_tar, mask = (batch[0].x, batch[0].y, batch[0].mask) if levels else batch[:3]
+    n_c, p = int(node_tar.shape[-1]), int(transforms.shape[-1])
+    if rows_per_sample is None:
+        if levels:
+            raise ValueError("equivariance_error: a variable-mesh batch needs rows_per_sample")
+        rows_per_sample = int(node_in.shape[-2])
+    groups = [int(g) for g in groups]
+    with torch.no_grad():
+        turned = transform_rows(node_in.contiguous(), rows_per_sample, transforms, groups + [n_c])     # the positions follow the state
+        if levels:
+            seen = [LevelData(batch[0].edge_index, batch[0].num_nodes, batch[0].face, turned, node_tar, mask), *batch[1:]]
+        else:
+            seen = [turned, *batch[1:]]
+        pred = model.get_pred(batch).contiguous()
+        back = model.get_pred(seen).contiguous()
+        pred, back = pred.reshape(-1, n_c), back.reshape(-1, n_c)
+        transform_rows(back, rows_per_sample, transforms, groups, inverse=True, out=back)
+        sums = error_sums(back, pred, mask.reshape(-1, 1).contiguous(), pred.shape[0]).sum(0)
+        se, tt = sums[1:1 + n_c], sums[1 + 2 * n_c:]
+        return torch.where(se == 0, torch.zeros_like(se), torch.sqrt(se / tt))      # identical predictions: 0 even where pred itself is 0

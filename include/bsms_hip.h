@@ -549,6 +549,48 @@ int bsms_batch_assemble(const bsms_batch_sample* samples, int64_t n_samples, int
 int bsms_batch_targets(const bsms_batch_sample* samples, int64_t n_samples, int64_t C, int64_t n_later, float* later,
                        bsms_stream_t stream);
 
+/* ---------------------------------------------------------------- frame augmentation: rotated and reflected batches ---
+ * bsms_batch_assemble with ONE RIGID TRANSFORM PER SAMPLE: `xf` is a HOST [n_samples, p, p] fp32 table (row-major), `vec_first`
+ * a HOST [n_vec] int32 table with the first channel of every VECTOR GROUP, the p consecutive state channels [f, f+p).  For every
+ * row of sample s, with Q = xf[s], a vector v = (v[0] .. v[p-1]) becomes
+ *   y[a] = fl32( .. fl32( fl32(Q[a][0] * v[0]) + fl32(Q[a][1] * v[1]) ) .. )      b ascending, every product rounded, no FMA
+ * -- applied to the position columns of node_in and, for every group, to those channels of state_in and of state_tar.  Scalar
+ * channels, the node type and the mask are what bsms_batch_assemble writes.  The NOISE COMES AFTER THE TRANSFORM and is that
+ * entry's in every respect (same Philox counter and key per batch-global row and channel, same noise_out, zero where the mask
+ * is zero):  node_in = fl32(y_in + noise),  node_tar = fl32(y_tar + fl32(g * noise)).  noise_std NULL: the transformed columns
+ * are exactly y and the others are bit copies.  The matrices are NOT checked for orthogonality: the kernel applies what it is
+ * given (identity matrices reproduce bsms_batch_assemble up to the sign of a zero).
+ * The matrices travel in the kernel-argument table (an entry is 88 B), 40 samples per launch; results do not depend on the
+ * chunking, the row offset is carried across launches.  Nothing is uploaded and nothing synchronises.
+ * Checked in this order, all before any device call:
+ *   C in 1..8, p in 2..3, n_valid in 1..4, n_vec in 0..4          else BSMS_E_UNSUPPORTED
+ *   n_samples >= 0                                                 else BSMS_E_INVALID_ARG
+ *   vec_first non-null when n_vec > 0; every group inside [0, C); no two groups overlapping      else BSMS_E_INVALID_ARG
+ *   n_samples == 0 returns BSMS_OK without a launch (nothing else is looked at)
+ *   samples, xf, valid_types, node_in, node_tar, node_mask non-null       else BSMS_E_INVALID_ARG
+ *   per sample: n in 0 .. 2^25 - 256 (BSMS_E_UNSUPPORTED), no null field where n > 0 (BSMS_E_INVALID_ARG). */
+int bsms_batch_assemble_xf(const bsms_batch_sample* samples, int64_t n_samples, int64_t C, int64_t p,
+                           const float* xf /* HOST [n_samples,p,p] */, const int32_t* vec_first /* HOST [n_vec] */, int64_t n_vec,
+                           const float* noise_std /* HOST [C], nullable */, double noise_gamma,
+                           const float* valid_types /* HOST */, int64_t n_valid, uint64_t seed, uint64_t draw, float* node_in,
+                           float* node_tar, float* node_mask, float* noise_out /* nullable */, bsms_stream_t stream);
+/* The same transform on the rows of x [F, R, C] (DEVICE fp32): the later targets of an unrolled loss, predictions mapped back to
+ * the data's frame, node_in itself (its position columns are one more group).  The first rows of EVERY frame are cut into
+ * n_samples consecutive segments of rows[s] rows (HOST int64 table; a segment of 0 rows is legal anywhere) with one matrix each;
+ * every vector group of every such row is replaced by Q v -- or by Q^T v when `transpose` is non-zero -- in the arithmetic and
+ * order above; the other channels are copied.  Rows past the table (sum rows < R) are not touched.  out == x works in place: a
+ * thread reads its row's groups completely before it writes; any other overlap of x and out is undefined.
+ * One launch per 40 segments, the frame is the grid's second axis.  Checked in this order, all before any device call:
+ *   C in 1..16 (node_in rows are C + p + 1 wide), p in 2..3, n_vec in 0..4, F <= 65535        else BSMS_E_UNSUPPORTED
+ *   n_samples, F, R >= 0                                           else BSMS_E_INVALID_ARG
+ *   vec_first / the groups as above, inside [0, C)                  else BSMS_E_INVALID_ARG
+ *   n_samples == 0 or F == 0 returns BSMS_OK and touches nothing
+ *   x, out, rows, xf non-null                                      else BSMS_E_INVALID_ARG
+ *   per segment: rows[s] in 0 .. 2^25 - 256 (BSMS_E_UNSUPPORTED), running sum <= R (BSMS_E_INVALID_ARG). */
+int bsms_rows_transform(const float* x, float* out, int64_t F, int64_t R, int64_t C, const int64_t* rows /* HOST [n_samples] */,
+                        int64_t n_samples, int64_t p, const float* xf /* HOST [n_samples,p,p] */, int transpose,
+                        const int32_t* vec_first /* HOST [n_vec] */, int64_t n_vec, bsms_stream_t stream);
+
 /* ---------------------------------------------------------------- hierarchy builder (host) ---
  * BistrideMultiLayerGraph (graph_wrappers/bsms_graph_wrapper.py:8-154 + graph_wrapper.py:67-134): the
  * bi-stride multi-level hierarchy of a mesh, built natively on the HOST (no GPU needed, no SciPy/MKL).
