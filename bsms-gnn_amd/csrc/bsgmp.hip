@@ -11,7 +11,7 @@
 // caller's stream -- no new arithmetic -- so that a training step costs the host two calls instead of ~60 autograd
 // nodes (the Python mirror of the reference's module tree needed 5.4 ms per step to enqueue what the GPU runs in
 // 7.6 ms at airfoil size and was the limit outright at cylinder size).
-#include "chain.h"
+#include "gmp_block.h"
 
 using namespace bsms;
 
@@ -23,20 +23,17 @@ struct Shape {
   int L;
   int64_t B, D, p, N[kMaxLevels + 1], E[kMaxLevels + 1];
   int H;
-  int prec = BSMS_F32;
+  int prec;
+  const bsms_plan_t* const* plans;
+  // the shape of a block acting on level `lv` (training layout: what the size queries ask for)
+  GmpShape level(int lv) const {
+    GmpShape g;
+    g.B = B; g.N = N[lv]; g.E = E[lv]; g.D = D; g.p = p; g.H = H; g.precision = prec;
+    return g;
+  }
 };
 
-struct Carve {
-  char* base;
-  size_t off = 0;
-  explicit Carve(void* b) : base(reinterpret_cast<char*>(b)) {}
-  char* bytes(size_t n) {
-    char* r = base ? base + off : nullptr;
-    off += align_up(n);
-    return r;
-  }
-  float* floats(size_t n) { return reinterpret_cast<float*>(bytes(n * sizeof(float))); }
-};
+inline int level_of_block(int k, int L) { return k <= L ? k : 2 * L - k; }   // storage order: down 0..L-1, bottom L, up i acts on L-1-i
 
 // what the backward needs: every block's own saved blob, the inputs of the blocks (x of a GMP is needed by its
 // backward) and the coarse positions
@@ -48,19 +45,14 @@ struct Saved {
   size_t bytes;
 };
 Saved carve_saved(void* base, const Shape& s, bool training) {
-  Carve c(base);
+  Carver c(base);
   Saved v{};
-  for (int i = 0; i < s.L; ++i) v.gmp[i] = training ? c.bytes(gmp_saved_bytes_p(s.B, s.N[i], s.E[i], s.D, s.H, s.prec)) : nullptr;
-  v.gmp[s.L] = training ? c.bytes(gmp_saved_bytes_p(s.B, s.N[s.L], s.E[s.L], s.D, s.H, s.prec)) : nullptr;
-  for (int i = 0; i < s.L; ++i) {
-    const int d = s.L - 1 - i;
-    v.gmp[s.L + 1 + i] = training ? c.bytes(gmp_saved_bytes_p(s.B, s.N[d], s.E[d], s.D, s.H, s.prec)) : nullptr;
-  }
+  for (int k = 0; k <= 2 * s.L; ++k) v.gmp[k] = training ? c.take_bytes(gmp_saved_bytes(s.level(level_of_block(k, s.L)))) : nullptr;
   for (int i = 1; i <= s.L; ++i) {
-    v.hin[i] = c.floats(size_t(s.B) * s.N[i] * s.D);
-    v.pos[i] = c.floats(size_t(s.B) * s.N[i] * s.p);
+    v.hin[i] = c.take(size_t(s.B) * s.N[i] * s.D);
+    v.pos[i] = c.take(size_t(s.B) * s.N[i] * s.p);
   }
-  for (int d = 0; d < s.L; ++d) v.upin[d] = c.floats(size_t(s.B) * s.N[d] * s.D);
+  for (int d = 0; d < s.L; ++d) v.upin[d] = c.take(size_t(s.B) * s.N[d] * s.D);
   v.bytes = c.off;
   return v;
 }
@@ -82,19 +74,19 @@ struct Work {
   size_t bytes;
 };
 Work carve_work(void* base, const Shape& s) {
-  Carve c(base);
+  Carver c(base);
   Work w{};
   size_t g = 0;
   for (int i = 0; i <= s.L; ++i) g = std::max(g, bsms_gmp_work_bytes(s.B, s.N[i], s.E[i], s.D, s.H));
   // ---- what a FORWARD touches (training or inference) comes first: bsms_bsgmp_infer_work_bytes stops behind it, so a forward-only
   // caller does not carry the backward's scratch sets (1.4 GB had become 4.7 GB at the airfoil batch-8 shape)
-  w.gmp = c.bytes(g);
-  for (int i = 0; i < s.L; ++i) w.skip[i] = c.floats(size_t(s.B) * s.N[i] * s.D);
-  for (int k = 0; k < 2; ++k) w.a[k] = c.floats(size_t(s.B) * s.N[0] * s.D);
-  for (int k = 0; k <= 2 * s.L; ++k) w.packs[k] = c.bytes(gmp_pack_bytes(s.D, s.H));
+  w.gmp = c.take_bytes(g);
+  for (int i = 0; i < s.L; ++i) w.skip[i] = c.take(size_t(s.B) * s.N[i] * s.D);
+  for (int k = 0; k < 2; ++k) w.a[k] = c.take(size_t(s.B) * s.N[0] * s.D);
+  for (int k = 0; k <= 2 * s.L; ++k) w.packs[k] = c.take_bytes(gmp_pack_bytes(s.D, s.H));
   w.fwd_bytes = c.off;
   // ---- backward only
-  w.gmp_b = c.bytes(s.L > 0 ? g : 0);
+  w.gmp_b = c.take_bytes(s.L > 0 ? g : 0);
   // Per-block sets for the backward (round 5): 2L + 1 scratch sets sized for their own level -- 4.7 GB instead of 1.4 GB at the
   // airfoil batch-8 shape, out of 288 GB; larger shapes than the cap keep the two alternating sets -- remove the 2L - 1 barrier packets with which block k waited for the side lanes of block
   // k - 2 before reusing its set (each ~5 us of idle caller's stream; profiles/r05_perblock_scratch_ab.txt).  The first two blocks
@@ -107,16 +99,15 @@ Work carve_work(void* base, const Shape& s) {
   const bool per_block = s.L > 0 && extra <= kPerBlockScratchCap;
   for (int k = 0; k <= 2 * s.L; ++k) {
     const int lv = level_of_block_bwd(k, s.L);
-    w.gmp_blk[k] = !per_block ? nullptr : (k == 0 ? w.gmp : (k == 1 ? w.gmp_b : c.bytes(bsms_gmp_work_bytes(s.B, s.N[lv], s.E[lv], s.D, s.H))));
+    w.gmp_blk[k] = !per_block ? nullptr : (k == 0 ? w.gmp : (k == 1 ? w.gmp_b : c.take_bytes(bsms_gmp_work_bytes(s.B, s.N[lv], s.E[lv], s.D, s.H))));
   }
   w.bytes = c.off;
   return w;
 }
-inline int level_of_block(int k, int L) { return k <= L ? k : 2 * L - k; }   // down 0..L-1, bottom L, up i acts on L-1-i
 
-int make_shape(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int H, Shape* s, const char* who) {
+int make_shape(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int H, int precision, Shape* s, const char* who) {
   BSMS_REQUIRE(plans != nullptr && L >= 0 && L <= kMaxLevels, BSMS_E_INVALID_ARG, "%s: unet_depth %d (0..%d)", who, L, kMaxLevels);
-  s->L = L; s->B = B; s->D = D; s->p = p; s->H = H;
+  s->L = L; s->B = B; s->D = D; s->p = p; s->H = H; s->prec = precision; s->plans = plans;
   for (int i = 0; i <= L; ++i) {
     BSMS_REQUIRE(plans[i] != nullptr, BSMS_E_INVALID_ARG, "%s: plan of level %d is null", who, i);
     s->N[i] = plans[i]->N;
@@ -125,11 +116,22 @@ int make_shape(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int
       BSMS_REQUIRE(plans[i - 1]->Nk == s->N[i], BSMS_E_SHAPE, "%s: level %d keeps %lld nodes but level %d has %lld", who, i - 1,
                    (long long)plans[i - 1]->Nk, i, (long long)s->N[i]);
   }
+  BSMS_REQUIRE(precision == BSMS_F32 || precision == BSMS_BF16 || precision == BSMS_BF16_NODES, BSMS_E_UNSUPPORTED, "%s: precision %d", who, precision);
   return BSMS_OK;
 }
 
-// parameters of block k: 4 (H + 1) pointers (mlp_node then mlp_edge), blocks ordered down 0..L-1, bottom, up 0..L-1
-inline const float* const* block(const float* const* params, int k, int H) { return params + size_t(k) * 4 * (H + 1); }
+// The call on block k (storage order) of a U-Net call: its level, its parameters, its saved blob (training) or its pack area
+// (inference: `v.gmp[k]` is null), and `scratch`, the scratch set it runs in.  The caller adds the block's input and positions.
+GmpCall block_call(const Shape& s, const float* const* params, const Saved& v, const Work& w, int k, void* scratch) {
+  const int lv = level_of_block(k, s.L);
+  GmpCall c;
+  static_cast<GmpShape&>(c) = s.level(lv);
+  c.params = params + size_t(k) * 4 * (s.H + 1);   // 4 (H + 1) pointers per block (mlp_node then mlp_edge)
+  c.bind(s.plans[lv], v.gmp[k], scratch, v.gmp[k] ? nullptr : w.packs[k]);
+  return c;
+}
+
+// gradient entries of block k: 4 (H + 1) pointers (mlp_node then mlp_edge), blocks ordered down 0..L-1, bottom, up 0..L-1
 inline float* const* block(float* const* grads, int k, int H) { return grads ? grads + size_t(k) * 4 * (H + 1) : nullptr; }   // null: every MLP frozen
 
 }  // namespace
@@ -140,20 +142,19 @@ extern "C" size_t bsms_bsgmp_saved_bytes(const bsms_plan_t* const* plans, int L,
 extern "C" size_t bsms_bsgmp_saved_bytes_p(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden,
                                            int precision) {
   Shape s;
-  if (make_shape(plans, L, B, D, p, hidden, &s, "bsgmp_saved_bytes")) return 0;
-  s.prec = precision;
+  if (make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_saved_bytes")) return 0;
   return carve_saved(nullptr, s, true).bytes;
 }
 extern "C" size_t bsms_bsgmp_work_bytes(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden) {
   Shape s;
-  if (make_shape(plans, L, B, D, p, hidden, &s, "bsgmp_work_bytes")) return 0;
+  if (make_shape(plans, L, B, D, p, hidden, BSMS_F32, &s, "bsgmp_work_bytes")) return 0;
   // (an inference call keeps its level inputs behind the forward part; covered, as the backward's sets are larger)
   const Work w = carve_work(nullptr, s);
   return std::max(w.bytes, w.fwd_bytes + carve_saved(nullptr, s, false).bytes);
 }
 extern "C" size_t bsms_bsgmp_infer_work_bytes(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden) {
   Shape s;
-  if (make_shape(plans, L, B, D, p, hidden, &s, "bsgmp_infer_work_bytes")) return 0;
+  if (make_shape(plans, L, B, D, p, hidden, BSMS_F32, &s, "bsgmp_infer_work_bytes")) return 0;
   return carve_work(nullptr, s).fwd_bytes + carve_saved(nullptr, s, false).bytes;
 }
 
@@ -174,10 +175,8 @@ extern "C" int bsms_bsgmp_fwd_p(const bsms_plan_t* const* plans, const float* co
                                 const float* const* params, float* out, void* saved, void* work, int reuse, int precision,
                                 bsms_stream_t stream) {
   Shape s;
-  int rc = make_shape(plans, L, B, D, p, hidden, &s, "bsgmp_fwd");
+  int rc = make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_fwd");
   if (rc) return rc;
-  BSMS_REQUIRE(precision == BSMS_F32 || precision == BSMS_BF16 || precision == BSMS_BF16_NODES, BSMS_E_UNSUPPORTED, "bsgmp_fwd: precision %d", precision);
-  s.prec = precision;
   BSMS_REQUIRE(h && pos && params && out && work && (ew || L == 0), BSMS_E_INVALID_ARG, "bsgmp_fwd: null argument");
   hipStream_t st = as_stream(stream);
   const bool training = saved != nullptr;
@@ -199,7 +198,12 @@ extern "C" int bsms_bsgmp_fwd_p(const bsms_plan_t* const* plans, const float* co
   // changed and in front of this call in stream order); no prepack is launched and lane 0 is neither forked nor joined.
   const bool packs_ok = reuse & 1, pos_ok = !training && (reuse & 2);
   SideLane *lane = nullptr, *lane0 = nullptr;
-  auto packs_of = [&](int k) { return training ? nullptr : w.packs[k]; };
+  // block k (storage order) on level `lv`, reading `x`, in the forward's one scratch set
+  auto fwd_block = [&](int k, int lv, const float* x, float* y, bool do_prepack, const float* resid2) -> int {
+    GmpCall c = block_call(s, params, v, w, k, w.gmp);
+    c.x = x; c.pos = pos_l[lv]; c.pos_bstride = pstride_l[lv];
+    return gmp_fwd_core(c, y, resid2, do_prepack, st);
+  };
   for (int i = 0; i < L; ++i) {
     pos_l[i + 1] = v.pos[i + 1];
     pstride_l[i + 1] = pos_batch_stride ? s.N[i + 1] * p : 0;
@@ -220,8 +224,7 @@ extern "C" int bsms_bsgmp_fwd_p(const bsms_plan_t* const* plans, const float* co
       // (slot 1: waited for in front of the first up block).  One join behind block 0 made the caller's stream wait for all 2L
       // prepacks -- 130-160 us per step at D = 256, where a block's prepack takes 55 us (profiles/r05_surface_join_ab.txt)
       for (int k = 1; k <= 2 * L; ++k) {
-        const int lv = level_of_block(k, L);
-        if ((r = gmp_prepack(B, s.N[lv], s.E[lv], D, p, hidden, block(params, k, hidden), v.gmp[k], w.gmp, packs_of(k), lane0->stream, precision))) return r;
+        if ((r = gmp_prepack(block_call(s, params, v, w, k, w.gmp), lane0->stream))) return r;
         if ((k == L || k == 2 * L) && (r = side_mark(lane0, k == L ? 0 : 1))) return r;
       }
     }
@@ -229,26 +232,21 @@ extern "C" int bsms_bsgmp_fwd_p(const bsms_plan_t* const* plans, const float* co
   };
   const float* hi = h;
   for (int i = 0; i < L; ++i) {
-    if ((rc = gmp_fwd_core(plans[i], hi, pos_l[i], B, D, p, pstride_l[i], hidden, block(params, i, hidden), w.skip[i], v.gmp[i], w.gmp,
-                           packs_of(i), i == 0 && !packs_ok, nullptr, st, precision))) return rc;
+    if ((rc = fwd_block(i, i, hi, w.skip[i], i == 0 && !packs_ok, nullptr))) return rc;
     if (i == 0 && ((rc = enqueue_lanes()) || (lane && (rc = side_join(lane, st))) || (lane0 && (rc = side_wait_mark(lane0, 0, st))))) return rc;
     // restrict the features to the kept nodes (ops/BSMS.py:74, 79-83)
     if ((rc = bsms_edge_conv(plans[i], w.skip[i], B, D, ew[i], 1, 1, v.hin[i + 1], stream))) return rc;
     hi = v.hin[i + 1];
   }
-  const float* pi = pos_l[L];
-  const int64_t pstride = pstride_l[L];
   float* cur = (L == 0) ? out : w.a[0];
-  if ((rc = gmp_fwd_core(plans[L], hi, pi, B, D, p, pstride, hidden, block(params, L, hidden), cur, v.gmp[L], w.gmp, packs_of(L),
-                         L == 0 && !packs_ok, nullptr, st, precision))) return rc;
+  if ((rc = fwd_block(L, L, hi, cur, L == 0 && !packs_ok, nullptr))) return rc;
   if (lane0 && (rc = side_wait_mark(lane0, 1, st))) return rc;   // the up blocks' packs
   for (int i = 0; i < L; ++i) {
     const int d = L - 1 - i;
     if ((rc = bsms_edge_conv(plans[d], cur, B, D, ew[d], 0, 1, v.upin[d], stream))) return rc;   // prolong (BSMS.py:98-100)
     // up block + skip connection (BSMS.py:101-102): the node chain's epilogue adds s_d after its own residual
     float* nxt = (d == 0) ? out : w.a[(i + 1) & 1];
-    if ((rc = gmp_fwd_core(plans[d], v.upin[d], pos_l[d], B, D, p, pstride_l[d], hidden, block(params, L + 1 + i, hidden), nxt,
-                           v.gmp[L + 1 + i], w.gmp, packs_of(L + 1 + i), false, w.skip[d], st, precision))) return rc;
+    if ((rc = fwd_block(L + 1 + i, d, v.upin[d], nxt, false, w.skip[d]))) return rc;
     cur = nxt;
   }
   return BSMS_OK;
@@ -263,19 +261,14 @@ extern "C" int bsms_pack_group_add_bsgmp(bsms_pack_group_t* group, const bsms_pl
   int rc = pack_group_open(group, "pack_group_add_bsgmp", &g);
   if (rc) return rc;
   Shape s;
-  if ((rc = make_shape(plans, L, B, D, p, hidden, &s, "pack_group_add_bsgmp"))) return rc;
-  BSMS_REQUIRE(precision == BSMS_F32 || precision == BSMS_BF16 || precision == BSMS_BF16_NODES, BSMS_E_UNSUPPORTED, "pack_group_add_bsgmp: precision %d", precision);
-  s.prec = precision;
+  if ((rc = make_shape(plans, L, B, D, p, hidden, precision, &s, "pack_group_add_bsgmp"))) return rc;
   BSMS_REQUIRE(params != nullptr && (saved != nullptr || work != nullptr), BSMS_E_INVALID_ARG, "pack_group_add_bsgmp: null argument");
   const bool training = saved != nullptr;
   for (int pass = 0; pass < 2; ++pass) {   // every block is checked before the first one is added (the carvers only add up sizes)
     Work w = carve_work(work, s);
     Saved v = carve_saved(saved, s, training);
-    for (int k = 0; k <= 2 * L; ++k) {
-      const int lv = level_of_block(k, L);
-      if ((rc = gmp_pack_group_add(pass ? g : nullptr, B, s.N[lv], s.E[lv], D, p, hidden, block(params, k, hidden), v.gmp[k], w.gmp,
-                                   training ? nullptr : w.packs[k], precision))) return rc;
-    }
+    for (int k = 0; k <= 2 * L; ++k)
+      if ((rc = gmp_pack_group_add(pass ? g : nullptr, block_call(s, params, v, w, k, w.gmp)))) return rc;
   }
   return BSMS_OK;
 }
@@ -326,12 +319,12 @@ struct PosWork {
   size_t bytes;
 };
 PosWork carve_pos_work(void* base, const Shape& s) {
-  Carve c(base);
+  Carver c(base);
   PosWork w{};
   size_t sc = 0;
   for (int i = 0; i <= s.L; ++i) sc = std::max(sc, pos_edge_scratch_bytes(s.B, s.E[i], s.p));
-  w.scratch = reinterpret_cast<float*>(c.bytes(std::max<size_t>(sc, 256)));
-  for (int i = 1; i <= s.L; ++i) w.g[i] = c.floats(size_t(s.B) * s.N[i] * s.p);   // B rows: also covers a shared pos (1 row)
+  w.scratch = reinterpret_cast<float*>(c.take_bytes(std::max<size_t>(sc, 256)));
+  for (int i = 1; i <= s.L; ++i) w.g[i] = c.take(size_t(s.B) * s.N[i] * s.p);   // B rows: also covers a shared pos (1 row)
   w.bytes = c.off;
   return w;
 }
@@ -344,7 +337,7 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
 
 extern "C" size_t bsms_bsgmp_pos_work_bytes(const bsms_plan_t* const* plans, int L, int64_t B, int64_t p) {
   Shape s;
-  if (B < 0 || p < 1 || p > 7 || make_shape(plans, L, B, 128, p, 1, &s, "bsgmp_pos_work_bytes")) return 0;
+  if (B < 0 || p < 1 || p > 7 || make_shape(plans, L, B, 128, p, 1, BSMS_F32, &s, "bsgmp_pos_work_bytes")) return 0;
   return carve_pos_work(nullptr, s).bytes;
 }
 
@@ -388,10 +381,8 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
                    int precision, int flags, void* const* block_done_events, float* grad_pos, void* pos_work, hipStream_t st) {
   bsms_stream_t stream = st;
   Shape s;
-  int rc = make_shape(plans, L, B, D, p, hidden, &s, "bsgmp_bwd");
+  int rc = make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_bwd");
   if (rc) return rc;
-  BSMS_REQUIRE(precision == BSMS_F32 || precision == BSMS_BF16 || precision == BSMS_BF16_NODES, BSMS_E_UNSUPPORTED, "bsgmp_bwd: precision %d", precision);
-  s.prec = precision;
   BSMS_REQUIRE(h && pos && grad_out && params && saved && work && grad_h && (ew || L == 0), BSMS_E_INVALID_ARG,
                "bsgmp_bwd: null argument");
   // frozen MLPs: every block's entries are checked here, before the first launch of the call; lanes[k] = block k
@@ -438,9 +429,11 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
     const int order = nblk;   // position of this block in the backward's execution order
     ++nblk;
     if (lanes[k]) marked[slot] = true;   // a block without lanes marks nothing
-    if ((r = gmp_bwd_core(plans[level], x, pos_l[level], g_in, B, D, p, pstride_l[level], hidden, block(params, k, hidden), v.gmp[k],
-                          own ? own : (slot ? w.gmp_b : w.gmp), gx, block(grads, k, hidden), slot, st, precision, gp[level],
-                          pw.scratch, pos_acc))) return r;
+    GmpCall c = block_call(s, params, v, w, k, own ? own : (slot ? w.gmp_b : w.gmp));
+    c.x = x; c.pos = pos_l[level]; c.pos_bstride = pstride_l[level];
+    GmpBwdOpts o;
+    o.defer_slot = slot; o.grad_pos = gp[level]; o.pos_work = pw.scratch; o.pos_accumulate = pos_acc;
+    if ((r = gmp_bwd_core(c, g_in, gx, block(grads, k, hidden), o, st))) return r;
     // Gradient-bucket hand-off (bsms_bsgmp_bwd_ev): lane 1's mark of this block covers lane 0's (gmp_marks_chained) and both
     // lanes are in-order streams, so an event recorded on lane 1 HERE completes when every weight gradient of this block,
     // of the blocks before it and of anything queued on the lanes earlier (a deferred bsms_mlp_bwd_ex) has been written.

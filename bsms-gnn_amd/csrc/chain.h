@@ -190,11 +190,8 @@ struct PackGroup {
 };
 void pack_group_append(PackGroup& g, const PackTable& t);
 int launch_prepack_group(PackGroup& g, hipStream_t s);
-// gmp.hip: the group behind an ABI handle, refused (BSMS_E_INVALID_ARG) when null or sealed; and one GMP block's packs added to a group
-// (arguments as gmp_prepack; `g` == null: the checks only, so that a caller can check every block before it adds the first)
+// the group behind an ABI handle, refused (BSMS_E_INVALID_ARG) when null or sealed
 int pack_group_open(bsms_pack_group_t* group, const char* who, PackGroup** g);
-int gmp_pack_group_add(PackGroup* g, int64_t B, int64_t N, int64_t E, int64_t D, int64_t p, int hidden, const float* const* params,
-                       void* saved, void* work, void* packs_base, int precision);
 
 int launch_chain_fwd(int D, int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s);
 int launch_chain_bwd(int D, int gin_mode, int first_mode, const ChainBwdArgs& a, hipStream_t s);
@@ -224,7 +221,7 @@ constexpr int kMaxWgradJobs = 20;
 size_t wgrad_work_bytes(int D, int njobs);
 // `skip_mask` (bit j = job j): jobs of a frozen MLP -- not run, but counted when the launch shape is chosen, so that the jobs that remain are
 // partitioned (and rounded) exactly as in the launch with nothing frozen; a launch whose jobs are all skipped is not issued
-int launch_wgrad(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t s, unsigned skip_mask = 0);
+int launch_wgrad(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t s, unsigned skip_mask);
 static_assert(kMaxWgradJobs <= 32, "launch_wgrad: one bit per job");
 
 // small-side weight gradients: out[s*os + f*of] = sum_r G[r][f] * S[r][s],  s < S (<= 8)
@@ -303,7 +300,7 @@ int rowsum_by_source(const bsms_plan* p, const float* x, int64_t B, int64_t D, f
 int rowsum_source_and_target(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* outS, float* outD, hipStream_t s);
 int rowsum_source_target_fiber(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* outS, float* outD,
                                const float* fiber, int ld, int ncols, float* part, int64_t part_blocks, int* nwg, hipStream_t s,
-                               bool x_bf16 = false);
+                               bool x_bf16);
 int rowsum_plan_order_bf16(const bsms_plan* p, const float* x_bf16, int64_t B, int64_t D, float* out, hipStream_t s);
 // wgrad.hip: partial blocks of the narrow weight gradients ([blocks][10][D] floats) and their fixed-order reduction
 int64_t small_wgrad_part_blocks(size_t work_bytes, int D);

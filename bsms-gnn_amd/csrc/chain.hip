@@ -231,3 +231,34 @@ int launch_chain_bwd(int D, int gin, int first, const ChainBwdArgs& a, hipStream
 }
 
 }  // namespace bsms
+
+// The pack group behind its ABI handle (bsms_pack_group_*; the members are added by bsms_pack_group_add_mlp, mlp.hip, and
+// bsms_pack_group_add_bsgmp, bsgmp.hip)
+struct bsms_pack_group {
+  bsms::PackGroup g;
+};
+
+extern "C" int bsms_pack_group_create(bsms_pack_group_t** out) {
+  BSMS_REQUIRE(out != nullptr, BSMS_E_INVALID_ARG, "pack_group_create: null argument");
+  *out = new bsms_pack_group();   // host state only: the device image is made by the first launch
+  return BSMS_OK;
+}
+
+extern "C" void bsms_pack_group_destroy(bsms_pack_group_t* group) {
+  if (!group) return;
+  if (group->g.dev) (void)hipFree(group->g.dev);   // waits for a launch still reading the tables
+  delete group;
+}
+
+int bsms::pack_group_open(bsms_pack_group_t* group, const char* who, PackGroup** g) {
+  BSMS_REQUIRE(group != nullptr, BSMS_E_INVALID_ARG, "%s: the group is null", who);
+  BSMS_REQUIRE(group->g.dev == nullptr, BSMS_E_INVALID_ARG, "%s: the group has been launched and is sealed (other pointers, shapes or "
+               "precision: build a new group)", who);
+  *g = &group->g;
+  return BSMS_OK;
+}
+
+extern "C" int bsms_pack_group_launch(bsms_pack_group_t* group, bsms_stream_t stream) {
+  BSMS_REQUIRE(group != nullptr, BSMS_E_INVALID_ARG, "pack_group_launch: the group is null");
+  return bsms::launch_prepack_group(group->g, bsms::as_stream(stream));
+}

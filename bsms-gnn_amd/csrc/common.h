@@ -115,27 +115,6 @@ inline int device_cu_count() {
 // rowsum.hip: bsms_edge_conv + fused addend
 int edge_conv_add(const bsms_plan* p, const float* x, int64_t B, int64_t D, const float* ew, int aggregating, int pooled,
                   float* out, const float* addend, hipStream_t stream);
-// gmp.hip: the GMP block with the knobs the U-Net entry uses.  `packs_base` (nullable): where the weight packs of an
-// INFERENCE call live (training keeps them in `saved`); `do_prepack` = false: the packs were filled by gmp_prepack
-// earlier in the same step; `resid2` (nullable): the skip connection added to the block's output (ops/BSMS.py:102).
-size_t gmp_pack_bytes(int64_t D, int hidden);
-int gmp_prepack(int64_t B, int64_t N, int64_t E, int64_t D, int64_t p, int hidden, const float* const* params,
-                void* saved, void* work, void* packs_base, hipStream_t stream, int precision = BSMS_F32);
-size_t gmp_saved_bytes_p(int64_t B, int64_t N, int64_t E, int64_t D, int hidden, int precision);
-int gmp_fwd_core(const bsms_plan* plan, const float* x, const float* pos, int64_t B, int64_t D, int64_t p,
-                 int64_t pos_bstride, int hidden, const float* const* params, float* out, void* saved, void* work,
-                 void* packs_base, bool do_prepack, const float* resid2, hipStream_t stream, int precision = BSMS_F32);
-// `defer_slot` < 0: the side lanes are joined before returning (ABI semantics).  0/1: they are only MARKED in that slot;
-// the caller joins later with side_wait_mark on both lanes and must not touch `work` or read `grads` before that.
-// gmp.hip: the `grads` table of one block: 2 (H + 1) node-MLP entries, then 2 (H + 1) edge-MLP entries; each group
-// all there or all null (the MLP is frozen), `grads` == NULL = both frozen.  BSMS_E_INVALID_ARG for a partly null group,
-// BSMS_E_UNSUPPORTED for null entries in a bf16 precision.  A host check: nothing is launched.
-int gmp_check_grads(float* const* grads, int hidden, int precision, const char* who, bool* node_live, bool* edge_live);
-bool gmp_marks_chained();   // gmp.hip: waiting for lane 1's mark of a slot is enough
-int gmp_bwd_core(const bsms_plan* plan, const float* x, const float* pos, const float* grad_out, int64_t B, int64_t D,
-                 int64_t p, int64_t pos_bstride, int hidden, const float* const* params, const void* saved, void* work,
-                 float* grad_x, float* const* grads, int defer_slot, hipStream_t stream, int precision = BSMS_F32,
-                 float* grad_pos = nullptr, void* pos_work = nullptr, bool pos_accumulate = false);
 // posgrad.hip: the position gradient of one GMP block from its first edge gradient gE[0] (plan order; bf16 rows when
 // `g_bf16`) and the saved fiber rows; `scratch` holds pos_edge_scratch_bytes(B, E, p).  grad_pos [B,N,p] (pos_bstride != 0)
 // or [N,p] (0, summed over the batch) is overwritten, or added to when `accumulate`.
