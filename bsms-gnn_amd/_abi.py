@@ -120,6 +120,9 @@ SIGNATURES = {
     "bsms_optim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_float, c_i64, C.c_float, c_void_p, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsms_grad_accumulate": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p]),
+    "bsms_accum_coef": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_i64, c_i64,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsms_grad_fold": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     "bsms_wgrad_bound_width": (c_size_t, []),
     "bsms_wgrad_work_bytes": (c_size_t, [c_i64, c_int]),
     "bsms_wgrad": (c_int, [c_void_p, c_int, c_i64, C.c_uint, c_void_p, c_size_t, c_void_p]),

@@ -124,6 +124,50 @@ extern "C" int bsms_grad_accumulate(float* acc, const float* g, int64_t n, int f
   return BSMS_OK;
 }
 
+// ---- gradient accumulation over micro-batches (step.py): acc = a * acc + b * g with (a, b) read from the device
+// (bsms_accum_coef wrote them on the same stream; the host never sees them).  k_grad_accumulate's grid, 16-byte path and tail; every
+// element goes through the same three separately rounded fp32 operations on either path, so the result does not depend on it.
+namespace {
+// (HIP's __fmul_rn / __fadd_rn are plain * and +, which the default contraction fuses once they are inlined: the pragma, as in
+// optim_element, is what keeps the three roundings.)
+__device__ __forceinline__ float fold_element(float a, float b, float acc, float g) {
+#pragma clang fp contract(off)
+  const float x = a * acc;
+  const float y = b * g;
+  return x + y;
+}
+
+__global__ __launch_bounds__(256) void k_grad_fold(float* __restrict__ acc, const float* __restrict__ g, int64_t n4, int64_t n,
+                                                   const float* __restrict__ coef) {
+  const float a = coef[0], b = coef[1];
+  const int64_t stride = int64_t(gridDim.x) * 256;
+  const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  float4* a4 = reinterpret_cast<float4*>(acc);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  for (int64_t i = t; i < n4; i += stride) {
+    const float4 v = g4[i];
+    float4 o = a4[i];
+    o.x = fold_element(a, b, o.x, v.x); o.y = fold_element(a, b, o.y, v.y);
+    o.z = fold_element(a, b, o.z, v.z); o.w = fold_element(a, b, o.w, v.w);
+    a4[i] = o;
+  }
+  for (int64_t i = 4 * n4 + t; i < n; i += stride) acc[i] = fold_element(a, b, acc[i], g[i]);   // tail (and unaligned buffers: n4 = 0)
+}
+}  // namespace
+
+extern "C" int bsms_grad_fold(float* acc, const float* g, int64_t n, const float* coef, bsms_stream_t stream) {
+  BSMS_REQUIRE(n >= 0, BSMS_E_SHAPE, "grad_fold: n=%lld", (long long)n);
+  if (n == 0) return BSMS_OK;
+  BSMS_REQUIRE(acc && g && coef, BSMS_E_INVALID_ARG, "grad_fold: null argument");
+  BSMS_REQUIRE(acc != g, BSMS_E_INVALID_ARG, "grad_fold: acc and g are the same buffer");
+  const bool aligned = ((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+  const int64_t n4 = aligned ? n / 4 : 0;
+  const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(std::max<int64_t>(n4, n - 4 * n4), 256), 2048);
+  hipLaunchKernelGGL(k_grad_fold, dim3(grid), dim3(256), 0, as_stream(stream), acc, g, n4, n, coef);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}
+
 // ---- the general step (bsms_optim_step): parameter groups, an exponential moving average of the weights and a
 // non-finite guard in the one pass over params / grads / exp_avg / exp_avg_sq.  k_adamw above stays the degenerate case's yardstick:
 // for lr_scale = 1 (or lr pre-multiplied) this kernel reproduces its bits, and the tests hold it to that.

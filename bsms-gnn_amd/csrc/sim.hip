@@ -357,3 +357,103 @@ extern "C" int bsms_sim_objective_bwd(const float* pred, const float* target, co
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
+
+namespace {
+
+// The coefficients of one fold of gradient accumulation (include/bsms_hip.h: bsms_accum_coef).  One block; thread k
+// owns unroll step k: its sums, its row of `running`, its entry of loss_out.  The pair (a, b) is step 0's (the mask, and so the
+// factor, is shared by the K steps wherever a scalar factor exists).  Everything is fp64 until the single rounding of a, b and the
+// losses to fp32; a_c and std are formed as k_sim_objective_bwd forms them.  No guard for m == 0 or a zero loss, as there.
+struct AccumCoefArgs {
+  const void* sums;
+  int64_t stride;
+  const double *mean, *meansq, *eps, *weights;
+  double* running;
+  float *coef, *loss_out;
+  int64_t t;
+  int row, C, normalized, rmse, mean_reduction, K;
+};
+
+__global__ __launch_bounds__(64) void k_accum_coef(AccumCoefArgs p) {
+  for (int k = threadIdx.x; k < p.K; k += 64) {
+    double m, n;
+    if (p.row) {
+      const double* s = reinterpret_cast<const double*>(p.sums) + int64_t(k) * p.stride;
+      const double e = p.normalized ? *p.eps : 0.0;
+      m = s[0];
+      n = 0.0;
+      for (int c = 0; c < p.C; ++c) {
+        const double wc = p.weights ? p.weights[c] : 1.0;
+        double a = wc;
+        if (p.normalized) {
+          const double sd = std_eps(p.mean[c], p.meansq[c], e);
+          a = wc / (sd * sd);
+        }
+        n += a * s[1 + c];
+      }
+    } else {
+      const float* s = reinterpret_cast<const float*>(p.sums) + int64_t(k) * p.stride;
+      n = double(s[0]);
+      m = double(s[1]);
+    }
+    const double Cd = double(p.C);
+    const double q = n / (m * Cd);
+    const double l = p.rmse ? sqrt(q) : q;
+    double* run = p.running + 3 * k;
+    double a = 0.0, b = 1.0, Mc = m, Nc = n, Lc = l;
+    if (p.t > 0) {
+      const double Mp = run[0], Np = run[1], Lp = run[2];
+      Mc = Mp + m;
+      Nc = Np + n;
+      if (p.mean_reduction) {
+        const double td = double(p.t), t1 = double(p.t + 1);
+        Lc = (Lp * td + l) / t1;
+        a = td / t1;
+        b = 1.0 / t1;
+      } else {
+        const double Qc = Nc / (Mc * Cd);
+        Lc = p.rmse ? sqrt(Qc) : Qc;
+        if (p.rmse) {
+          const double den = Lc * Mc;
+          a = (Lp * Mp) / den;
+          b = (l * m) / den;
+        } else {
+          a = Mp / Mc;
+          b = m / Mc;
+        }
+      }
+    }
+    run[0] = Mc; run[1] = Nc; run[2] = Lc;
+    p.loss_out[k] = float(Lc);
+    if (k == 0) { p.coef[0] = float(a); p.coef[1] = float(b); }
+  }
+}
+
+}  // namespace
+
+extern "C" int bsms_accum_coef(const void* sums, int layout, int64_t sums_stride, int64_t C, const double* mean, const double* meansq,
+                               const double* std_eps_dev, const double* channel_weights, int space, int kind, int reduction,
+                               int64_t t, int64_t K, double* running, float* coef, float* loss_out, bsms_stream_t stream) {
+  BSMS_REQUIRE(K >= 1 && K <= 4096 && C >= 1 && C <= kMaxC && t >= 0, BSMS_E_UNSUPPORTED, "accum_coef: K=%lld C=%lld t=%lld",
+               (long long)K, (long long)C, (long long)t);
+  BSMS_REQUIRE((layout == BSMS_ACCUM_SUMS_PAIR || layout == BSMS_ACCUM_SUMS_ROW) &&
+                   (space == BSMS_LOSS_PHYSICAL || space == BSMS_LOSS_NORMALIZED) && (kind == BSMS_LOSS_MSE || kind == BSMS_LOSS_RMSE) &&
+                   (reduction == BSMS_ACCUM_BATCH || reduction == BSMS_ACCUM_MEAN),
+               BSMS_E_UNSUPPORTED, "accum_coef: layout=%d space=%d kind=%d reduction=%d (each 0 or 1)", layout, space, kind, reduction);
+  const bool row = layout == BSMS_ACCUM_SUMS_ROW;
+  BSMS_REQUIRE(sums_stride >= (row ? 1 + C : 2), BSMS_E_SHAPE, "accum_coef: sums_stride=%lld is shorter than one entry (%lld)",
+               (long long)sums_stride, (long long)(row ? 1 + C : 2));
+  BSMS_REQUIRE(sums && running && coef && loss_out, BSMS_E_INVALID_ARG, "accum_coef: null argument");
+  const bool normalized = row && space == BSMS_LOSS_NORMALIZED;
+  BSMS_REQUIRE(!normalized || (mean && meansq && std_eps_dev), BSMS_E_INVALID_ARG,
+               "accum_coef: the normalized space needs the target normaliser's statistics");
+  AccumCoefArgs p{};
+  p.sums = sums; p.stride = sums_stride; p.mean = mean; p.meansq = meansq; p.eps = std_eps_dev;
+  p.weights = row ? channel_weights : nullptr;
+  p.running = running; p.coef = coef; p.loss_out = loss_out; p.t = t;
+  p.row = int(row); p.C = (int)C; p.normalized = int(normalized); p.rmse = int(kind == BSMS_LOSS_RMSE);
+  p.mean_reduction = int(reduction == BSMS_ACCUM_MEAN); p.K = (int)K;
+  hipLaunchKernelGGL(k_accum_coef, dim3(1), dim3(64), 0, as_stream(stream), p);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}

@@ -31,6 +31,10 @@ scratch flat buffer that bsms_grad_accumulate folds into `GradBuckets.flat`.
 (the same schedule plus the position kernels), the encoder's backward returns its input gradient at every step, and one
 bsms_sim_input_grad launch per step folds them, with the step's g_pred, into a static [B, N, C+p+1] buffer (`input_grad()`).
 
+`accumulate=M > 1`: a call is one micro-batch of a cycle of M.  The first is the plain step; every later one writes
+its gradient into the scratch flat buffer, bsms_accum_coef forms two coefficients on the device from the running loss sums, and
+bsms_grad_fold leaves a * grads.flat + b * scratch: the gradient of the loss over every sample seen so far in the cycle.
+
 Frozen parameters: an MLP -- encoder, decoder, a block's node or edge MLP -- all of whose parameters have
 `requires_grad == False` gets NULL entries in the gradient tables; the backward then launches nothing for its weight gradients.
 With nothing trainable (or `param_grad=False`) and `input_grad=True` the backward is data-only."""
@@ -42,6 +46,9 @@ import torch.distributed as dist
 
 from . import _abi
 from .ops import PRECISIONS, _param_ptrs, _stream
+
+
+REDUCTIONS = {"batch": 0, "mean": 1}             # BSMS_ACCUM_BATCH / BSMS_ACCUM_MEAN
 
 
 def _ptr(t):
@@ -88,8 +95,11 @@ class _Arena:
 
 class FusedStep:
     def __init__(self, model, grads, group=None, use_graph=False, unroll=1, step_weights=None, detach=False, objective=None,
-                 input_grad=False, param_grad=True):
-        """`objective` (objective.Objective): None or the default objective keeps the reference's masked RMSE on the kernels it
+                 input_grad=False, param_grad=True, accumulate=1, reduction="batch"):
+        """`accumulate=M > 1`: every call is one MICRO-batch; after the t-th call of a cycle `grads.flat` holds the
+        gradient of the loss over all samples of the cycle so far (`reduction="batch"`), or the mean of the micro-batch gradients
+        (`reduction="mean"`, what `(loss / M).backward()` gives); `ready` after the M-th, and the next call starts a new cycle.
+        `objective` (objective.Objective): None or the default objective keeps the reference's masked RMSE on the kernels it
         always ran on; any other runs bsms_error_sums after every forward and bsms_sim_objective_bwd in front of every backward.
         `input_grad`: every backward also forms the gradient of the (K-step) loss w.r.t. `node_in` -- state, mesh
         positions and node type -- into a static [B, N, C+p+1] buffer, handed out by `input_grad()`.  Off: nothing changes.
@@ -127,6 +137,23 @@ class FusedStep:
         from .objective import Objective
         self.objective = (Objective() if objective is None else objective).bind(model.cfg.out_dim)
         self._obj = None if self.objective.is_default else self.objective      # None: the default route, untouched
+        if isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1:
+            raise ValueError(f"FusedStep: accumulate must be an integer >= 1, got {accumulate!r}")
+        if reduction not in REDUCTIONS:
+            raise ValueError(f"FusedStep: unknown reduction {reduction!r} (one of {sorted(REDUCTIONS)})")
+        self.accumulate, self.reduction = int(accumulate), reduction
+        if self.accumulate > 1:
+            if use_graph:
+                raise ValueError("FusedStep: accumulate > 1 is not captured into HIP graphs; use use_graph=False")
+            if input_grad:
+                raise ValueError("FusedStep: input_grad=True with accumulate > 1: the static input-gradient buffer carries one call's "
+                                 "loss coefficient; use accumulate=1")
+            if unroll > 1 and reduction == "batch" and self.objective.kind == "rmse":
+                raise ValueError("FusedStep: accumulate > 1 with unroll > 1 and an rmse loss has no exact batch gradient (the steps' "
+                                 'coefficients scale differently): use reduction="mean" or loss_kind="mse"')
+        self._micro = 0                             # micro-batches of the current cycle that have run
+        self._acc = None                            # accumulate > 1: dict(running fp64 [K,3], coef fp32 [2], loss fp32 [K]) on the device
+        self._gsum = None                           # accumulate > 1 and unroll > 1: where a micro-batch t >= 1 sums its K steps
         self._obj_w = None                          # the channel weights on the device (fp64 [C]), or None for unit weights
         self._gscratch, self._wts = None, None     # unroll > 1: scratch flat gradient buffer (GradBuckets layout), weights on the device
         self._shape_key, self._graphs, self._ptr_guard = None, None, None
@@ -221,13 +248,19 @@ class FusedStep:
             groups = (("enc", enc), ("proc", proc), ("dec", dec))
             self._any_live = any(states)
             self._tabs = {k: (_param_ptrs(ps), table(self.grads.flat if self._any_live else None, ps)) for k, ps in groups}
-            self._tabs_scratch = None
-            if self.unroll > 1 and self._any_live:  # the same slots in the scratch flat buffer: where all steps but the first-run write
-                if self._gscratch is None or self._gscratch.device != self.grads.flat.device or self._gscratch.numel() != self.grads.flat.numel():
+            self._tabs_scratch = self._tabs_sum = None
+            fits = lambda t: t is not None and t.device == self.grads.flat.device and t.numel() == self.grads.flat.numel()
+            scratch = self.unroll > 1 or self.accumulate > 1
+            if scratch and self._any_live:          # the same slots in the scratch flat buffer: where all steps but the first-run write
+                if not fits(self._gscratch):
                     self._gscratch = torch.zeros_like(self.grads.flat)       # zeros: a slot no kernel writes adds nothing
                 self._tabs_scratch = {k: (self._tabs[k][0], table(self._gscratch, ps)) for k, ps in groups}
-            elif self.unroll > 1:                   # nothing trainable: every table is NULLs, no scratch buffer
-                self._tabs_scratch = self._tabs
+                if self.unroll > 1 and self.accumulate > 1:      # a micro-batch t >= 1 sums its K steps here, never in grads.flat
+                    if not fits(self._gsum):
+                        self._gsum = torch.zeros_like(self.grads.flat)
+                    self._tabs_sum = {k: (self._tabs[k][0], table(self._gsum, ps)) for k, ps in groups}
+            elif scratch:                           # nothing trainable: every table is NULLs, no scratch buffer
+                self._tabs_scratch = self._tabs_sum = self._tabs
             self._ptr_guard = guard
             self._graphs = None
             self._drop_pack_group()
@@ -365,14 +398,15 @@ class FusedStep:
         ck(L.bsms_error_sums(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), 1, R, C, R, R, R, b["osums"].data_ptr(),
                              b["work_obj"].data_ptr(), s), "bsms_error_sums")
 
-    def _backward(self, b, tar, mask, ews, B, N, events=None, chain=None):
+    def _backward(self, b, tar, mask, ews, B, N, events=None, chain=None, tabs=None):
         """`events`: (pointer array, keep-alive) of 2L+1 hipEvent_t for bsms_bsgmp_bwd_ev, or None.
+        `tabs` (without `chain`; gradient accumulation): the weight gradients of the plain step go to the slots of these tables.
         `chain` (unrolled step only): dict(w, g_pred_next, g_nin_next, g_pred, grad_x, tabs) -- the loss gradient comes from
         bsms_sim_unroll_bwd with the carried pair, the encoder's backward returns its input gradient into `grad_x`, and the
         weight gradients go to the slots of `tabs`."""
         m, L, s = self.model, _abi.lib(), _stream()
         C, p, D, H = m.cfg.out_dim, m.pos_dim, m.cfg.latent_dim, m.cfg.hidden_layer
-        R, t = b["R"], (self._tabs if chain is None else chain["tabs"])
+        R, t = b["R"], ((tabs or self._tabs) if chain is None else chain["tabs"])
         work = b["work"]
         no = m._targetNormalizer
         ck = _abi.check
@@ -441,6 +475,8 @@ class FusedStep:
         b = self._buffers(B, N, plans, node_in.device)
         self._decide_packs()
         world = self._world()
+        if self.accumulate > 1:
+            return self._micro_batch(b, node_in, tar, mask, later_targets, ews, B, N, world, consistent)
         if self.unroll > 1:
             return self._unrolled(b, node_in, tar, mask, later_targets, ews, B, N, world, consistent)
         if self.use_graph:
@@ -508,8 +544,11 @@ class FusedStep:
             raise RuntimeError(f"later_targets is on {later.device}, node_in on {node_in.device}")
         return later if (later.is_contiguous() and later.dtype == torch.float32) else later.contiguous().float()
 
-    def _unrolled(self, b, node_in, tar, mask, later, ews, B, N, world, consistent):
+    def _unrolled(self, b, node_in, tar, mask, later, ews, B, N, world, consistent, into=None):
+        """`into` (gradient accumulation): (tables, flat buffer) that receive the K-step sum instead of grads.flat, and no gradient
+        all-reduce here; the steps that are folded in then go through `_tabs_scratch` / `_gscratch` as ever."""
         K, L, s = self.unroll, _abi.lib(), _stream()
+        tabs_sum, flat_sum = (self._tabs, None if self.grads is None else self.grads.flat) if into is None else into   # (param_grad=False: no grads)
         later = self._later(later, node_in, consistent)
         steps = self._unroll_buffers(b, B, N, node_in.device)
         tars = [tar, *(later[k] for k in range(K - 1))]
@@ -529,16 +568,88 @@ class FusedStep:
             bk, last = steps[k], k == K - 1
             carry = not last and not self.detach
             keep = self._input_grad or (k > 0 and not self.detach)      # input_grad: g_pred and the encoder's grad_x of EVERY step
-            chain = dict(w=self.step_weights[k], tabs=self._tabs if last else self._tabs_scratch,
+            chain = dict(w=self.step_weights[k], tabs=tabs_sum if last else self._tabs_scratch,
                          g_pred_next=b["g_pred"][(k + 1) & 1] if carry else None, g_nin_next=b["g_nin"] if carry else None,
                          g_pred=b["g_pred"][k & 1] if keep else None, grad_x=b["g_nin"] if keep else None,
                          first_step=int(k == 0), overwrite=int(last))
             self._backward(bk, tars[k], mask, ews, B, N, chain=chain)          # ends with bsms_side_lanes_join
             if not last and self._any_live:
-                _abi.check(L.bsms_grad_accumulate(self.grads.flat.data_ptr(), self._gscratch.data_ptr(), n, 0, s), "bsms_grad_accumulate")
-        if world > 1 and self._any_live:
+                _abi.check(L.bsms_grad_accumulate(flat_sum.data_ptr(), self._gscratch.data_ptr(), n, 0, s), "bsms_grad_accumulate")
+        if world > 1 and self._any_live and into is None:
             dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         return torch.dot(b["loss_all"], self._wts)
+
+    # ------------------------------------------------------------------------------------------------ gradient accumulation
+    def _micro_batch(self, b, node_in, tar, mask, later, ews, B, N, world, consistent):
+        """One micro-batch of a cycle of `accumulate` (DESIGN.md 4.17).  Micro-batch 0 is the plain (or unrolled) step into grads.flat;
+        micro-batch t >= 1 writes its whole gradient into the scratch flat buffer, and behind the join bsms_accum_coef forms (a, b)
+        on the device from the (all-reduced) loss sums and bsms_grad_fold leaves a * grads.flat + b * scratch in grads.flat.  The host
+        reads nothing back.  Data parallel: every rank folds with the same global coefficients; ONE all-reduce of the flat buffer
+        after the last fold of the cycle."""
+        from .objective import KINDS, SPACES
+        L, s, K = _abi.lib(), _stream(), self.unroll
+        dev = node_in.device
+        if self._micro >= self.accumulate:            # the (M+1)-th call starts a new cycle by itself
+            self._micro = 0
+        t = self._micro
+        if self._acc is None or self._acc["coef"].device != dev:
+            self._acc = dict(running=torch.zeros(K, 3, device=dev, dtype=torch.float64), coef=torch.zeros(2, device=dev),
+                             loss=torch.zeros(K, device=dev))
+        if K > 1:                                     # t >= 1: the K-step sum in _gsum, the folded-in steps through _gscratch
+            into = (self._tabs, self.grads.flat) if t == 0 else (self._tabs_sum, self._gsum)
+            loss = self._unrolled(b, node_in, tar, mask, later, ews, B, N, world, consistent, into=into)
+            g = self._gsum
+        else:
+            self._forward(b, node_in, tar, mask, ews, B, N)
+            if world > 1:
+                dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
+            self._backward(b, tar, mask, ews, B, N, tabs=None if t == 0 else self._tabs_scratch)       # ends with bsms_side_lanes_join
+            loss, g = b["loss"][0].clone(), self._gscratch
+        sums, no, o = self._loss_sums(b), self.model._targetNormalizer, self.objective
+        row = self._obj is not None
+        C = self.model.cfg.out_dim
+        _abi.check(L.bsms_accum_coef(sums.data_ptr(), int(row), (1 + 3 * C) if row else 2, C, no._E_data.data_ptr(),
+                                     no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), _ptr(self._obj_w) if row else None,
+                                     SPACES[o.space], KINDS[o.kind], REDUCTIONS[self.reduction], t, K, self._acc["running"].data_ptr(),
+                                     self._acc["coef"].data_ptr(), self._acc["loss"].data_ptr(), s), "bsms_accum_coef")
+        if t > 0 and self._any_live:
+            _abi.check(L.bsms_grad_fold(self.grads.flat.data_ptr(), g.data_ptr(), self.grads.flat.numel(), self._acc["coef"].data_ptr(), s),
+                       "bsms_grad_fold")
+        self._micro = t + 1
+        if self.ready and world > 1 and self._any_live:
+            dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
+        return loss
+
+    @property
+    def micro_index(self):
+        """Micro-batches of the current cycle that have run: 0 after construction or `reset_accumulation()`, `accumulate` when `ready`."""
+        return self._micro
+
+    @property
+    def ready(self):
+        """True after the last micro-batch of a cycle (always, with accumulate = 1): `grads.flat` holds the cycle's gradient."""
+        return self.accumulate == 1 or self._micro == self.accumulate
+
+    def reset_accumulation(self):
+        """Drop the partial cycle: the next call is micro-batch 0 (which overwrites `grads.flat` and the running sums)."""
+        self._micro = 0
+
+    def _accumulating(self, what):
+        if self.accumulate == 1:
+            raise ValueError(f"FusedStep.{what}: the step was built with accumulate = 1")
+        if self._acc is None:
+            raise RuntimeError(f"FusedStep.{what}: the step has not run yet")
+
+    def accumulated_loss(self):
+        """Device scalar sum_k w_k Lc_k: the loss over every sample of the cycle so far (`reduction="batch"`) or the running mean of the
+        micro-batch losses (`"mean"`), weighted over the unroll steps like the value a call returns (a copy)."""
+        self._accumulating("accumulated_loss")
+        return torch.dot(self._acc["loss"], self._wts) if self.unroll > 1 else self._acc["loss"][0].clone()
+
+    def accumulation_coefficients(self):
+        """Device [2]: a copy of (a, b) of the last bsms_accum_coef -- (0, 1) after micro-batch 0.  For tests."""
+        self._accumulating("accumulation_coefficients")
+        return self._acc["coef"].clone()
 
     def predictions(self):
         """The K predictions of the last step, [B,N,C] each (static buffers: clone to keep)."""

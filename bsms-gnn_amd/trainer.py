@@ -326,7 +326,12 @@ class Trainer:
     unroll_steps (default 1: the reference's single-step loss), unroll_weights, unroll_detach -- the loss over that many
     autoregressive steps (step.FusedStep); `iter` then takes `(batch, later_targets)`, what TrajectoryBank(horizon=K) hands out;
     loss_space ("physical" / "normalized"), loss_kind ("rmse" / "mse"), loss_channel_weights -- the training objective
-    (objective.Objective; absent: the reference's masked RMSE in physical units), which `iter` trains on and `get_loss` reports."""
+    (objective.Objective; absent: the reference's masked RMSE in physical units), which `iter` trains on and `get_loss` reports.
+    Optional in `opt_cfg`: gradient_accumulation_steps = M (absent or 1: every `iter` is an optimizer step) and
+    accumulation_reduction ("batch", the default: the exact loss over the M micro-batches; "mean": the mean of their gradients).  After
+    warm-up the optimizer step, the LR-schedule step and the parameter epoch then happen on every M-th `iter` only; `train_step`
+    counts calls; `last_accumulated_loss` is the device scalar of the last completed cycle.  `save` inside a cycle does not keep
+    the partial sum: `restore` starts the cycle again."""
 
     def __init__(self, model, model_cfg, opt_cfg):
         self.model_cfg, self.opt_cfg = model_cfg, opt_cfg
@@ -335,9 +340,12 @@ class Trainer:
         self.unroll = int(getattr(model_cfg, "unroll_steps", 1) or 1)
         from .objective import Objective
         self.objective = Objective.from_cfg(model_cfg)
-        self.dp = DataParallel(self.model, unroll=self.unroll, step_weights=getattr(model_cfg, "unroll_weights", None),
-                               detach=bool(getattr(model_cfg, "unroll_detach", False)), objective=self.objective)     # world size 1: no collective is issued
         opt = lambda key, default: getattr(opt_cfg, key, default)
+        self.accumulate = int(opt("gradient_accumulation_steps", 1) or 1)       # the reference's key (configs/opt/default.yaml), unread there
+        self.last_accumulated_loss = None          # device scalar: the loss over every sample of the last completed cycle
+        self.dp = DataParallel(self.model, unroll=self.unroll, step_weights=getattr(model_cfg, "unroll_weights", None),
+                               detach=bool(getattr(model_cfg, "unroll_detach", False)), objective=self.objective,      # world size 1: no collective is issued
+                               accumulate=self.accumulate, reduction=opt("accumulation_reduction", None) or "batch")
         no_decay_bias, lr_scales = bool(opt("no_decay_bias", False)), opt("lr_scales", None)
         groups = param_groups(self.model, no_decay_bias, lr_scales) if (no_decay_bias or lr_scales) else None
         self.optimizer = FusedAdamW(self.dp.grads, lr=opt_cfg.peak_lr, weight_decay=opt_cfg.weight_decay,
@@ -462,8 +470,11 @@ class Trainer:
                 self.dp.sync_normalizers(self._norm_base)
                 self._synced, self._norm_base = True, None
             loss = self.dp.step_loss_backward(data, self.model_cfg.consistent_mesh, later)
-            self.optimizer.step(self.lr_scheduler.lr())
-            self.lr_scheduler.step()
+            if self.accumulate == 1 or self.dp.fused.ready:       # a micro-batch inside a cycle changes no parameter
+                if self.accumulate > 1:
+                    self.last_accumulated_loss = self.dp.fused.accumulated_loss()
+                self.optimizer.step(self.lr_scheduler.lr())
+                self.lr_scheduler.step()
         self.train_step += 1
         return loss
 
@@ -479,6 +490,8 @@ class Trainer:
         self.model.load_state_dict(torch.load(f"{save_dir}/{step}_params.pth", map_location=self.device))
         if self.optimizer.ema is not None:          # no optimizer state (or one without `ema`): the average restarts from the parameters
             self.optimizer.ema.copy_(self.optimizer.flat_p)
+        if self.dp.fused is not None:               # a checkpoint taken inside a cycle loses the partial sum: the cycle starts again
+            self.dp.fused.reset_accumulation()
         opt_path = f"{save_dir}/{step}_opt_state.pth"
         if restore_opt_state and os.path.exists(opt_path):
             st = torch.load(opt_path, map_location=self.device)

@@ -662,6 +662,38 @@ int bsms_optim_step(float* params, const float* grads, float* exp_avg, float* ex
  * when both pointers are 16-byte aligned.  n == 0 returns BSMS_OK; n < 0 BSMS_E_SHAPE; null or identical pointers
  * BSMS_E_INVALID_ARG. */
 int bsms_grad_accumulate(float* acc, const float* g, int64_t n, int first, bsms_stream_t stream);
+/* Gradient accumulation over micro-batches: the coefficients of one fold, formed on the device from the sums the
+ * step already has.  Micro-batch t (0-based) of a cycle, unroll step k < K; `sums` holds K entries `sums_stride` ELEMENTS apart:
+ *   BSMS_ACCUM_SUMS_PAIR  float (S, M) of bsms_sim_epilogue:                 m = M, n = S
+ *   BSMS_ACCUM_SUMS_ROW   double [M | SE[0..C) ...] of bsms_error_sums:      m = M, n = sum_c a_c SE[c] in channel order, a_c as
+ *                         bsms_sim_objective_bwd forms it from `space`, `channel_weights` (nullable: ones) and the TARGET
+ *                         normaliser's mean / meansq / std_eps (read with BSMS_LOSS_NORMALIZED only; the pair ignores all four)
+ * (under data parallelism: after their all-reduce).  All fp64, no contraction:
+ *   Q(m, n) = n / (m C),   loss(m, n) = Q (BSMS_LOSS_MSE) or sqrt(Q) (BSMS_LOSS_RMSE),   l = loss(m, n)
+ *   running[k] = (Mc, Nc, Lc):  t == 0:  (m, n, l), whatever it held before (NaNs included)
+ *                               t  > 0:  Mc = Mc' + m,  Nc = Nc' + n  (primes: the values read),  and
+ *     BSMS_ACCUM_BATCH   Lc = loss(Mc, Nc);   mse:  a = Mc' / Mc,                 b = m / Mc
+ *                                             rmse: a = (Lc' Mc') / (Lc Mc),      b = (l m) / (Lc Mc)
+ *     BSMS_ACCUM_MEAN    Lc = (Lc' t + l) / (t + 1);   a = t / (t + 1),   b = 1 / (t + 1)
+ *   loss_out[k] = fl32(Lc);   coef = (fl32(a), fl32(b)) of step k = 0, each rounded once;   t == 0 writes (0, 1).
+ * After the call the gradient of Lc is  fl32(a) * (gradient of Lc') + fl32(b) * (gradient of l): what bsms_grad_fold forms.  m == 0,
+ * and a zero loss under rmse, are not guarded: the non-finite coefficient shows.
+ * One launch of one block; no atomics, no allocation, no synchronisation, nothing read back: the call can be captured into a HIP
+ * graph.  Checked in this order, all before any device call: K in 1..4096, C in 1..8, t >= 0 (BSMS_E_UNSUPPORTED); layout, space,
+ * kind and reduction in {0, 1} (BSMS_E_UNSUPPORTED); sums_stride >= 2 (pair) or 1 + C (row) (BSMS_E_SHAPE); null sums / running /
+ * coef / loss_out, or a row with BSMS_LOSS_NORMALIZED and null statistics (BSMS_E_INVALID_ARG). */
+enum { BSMS_ACCUM_SUMS_PAIR = 0, BSMS_ACCUM_SUMS_ROW = 1 };   /* layout */
+enum { BSMS_ACCUM_BATCH = 0, BSMS_ACCUM_MEAN = 1 };           /* reduction */
+int bsms_accum_coef(const void* sums, int layout, int64_t sums_stride, int64_t C, const double* mean /* nullable */,
+                    const double* meansq /* nullable */, const double* std_eps /* nullable */,
+                    const double* channel_weights /* nullable */, int space, int kind, int reduction, int64_t t, int64_t K,
+                    double* running /* [K][3] */, float* coef /* [2] */, float* loss_out /* [K] */, bsms_stream_t stream);
+/* acc[i] = fl32(fl32(a * acc[i]) + fl32(b * g[i])) over n floats, (a, b) = coef[0..1] read on the DEVICE (bsms_accum_coef's output):
+ * three separately rounded fp32 operations per element, never fused, the same on the 16-byte path (both pointers 16-byte aligned)
+ * and on the element path (anything else, and the tail), one thread per element: bit-identical from run to run.  The grid of
+ * bsms_grad_accumulate.  Elements past n are never touched.  n == 0 returns BSMS_OK; n < 0 BSMS_E_SHAPE; null or identical
+ * pointers (coef included) BSMS_E_INVALID_ARG; all before any device call.  No allocation, no synchronisation; can be captured. */
+int bsms_grad_fold(float* acc, const float* g, int64_t n, const float* coef, bsms_stream_t stream);
 
 /* ---------------------------------------------------------------- weight-gradient primitives ---
  * The batched weight gradient of D x D Linears, the launcher every MLP / GMP backward uses, as an entry of its own:
