@@ -65,6 +65,8 @@ SIGNATURES = {
     "bsms_bsgmp_fwd_ex": (c_int, [PP, PP, c_int, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, PP, c_void_p, c_void_p,
                                   c_void_p, c_int, c_void_p]),
     "bsms_bsgmp_saved_bytes_p": (c_size_t, [PP, c_int, c_i64, c_i64, c_i64, c_int, c_int]),
+    "bsms_bsgmp_saved_bytes_ex": (c_size_t, [PP, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int]),
+    "bsms_bsgmp_work_bytes_ex": (c_size_t, [PP, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int]),
     "bsms_bsgmp_fwd_p": (c_int, [PP, PP, c_int, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, PP, c_void_p, c_void_p,
                                  c_void_p, c_int, c_int, c_void_p]),
     "bsms_bsgmp_bwd_p": (c_int, [PP, PP, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, PP, c_void_p,

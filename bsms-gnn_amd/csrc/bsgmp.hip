@@ -36,7 +36,8 @@ struct Shape {
 inline int level_of_block(int k, int L) { return k <= L ? k : 2 * L - k; }   // storage order: down 0..L-1, bottom L, up i acts on L-1-i
 
 // what the backward needs: every block's own saved blob, the inputs of the blocks (x of a GMP is needed by its
-// backward) and the coarse positions
+// backward) and the coarse positions.  Without the blobs (`training` false) it is the layout of an inference call's level inputs in
+// `work` AND the lean `saved` of BSMS_FWD_LEAN / BSMS_BWD_RECOMPUTE, whose backward rebuilds each blob in `work` (Work::blob)
 struct Saved {
   void* gmp[2 * kMaxLevels + 1];   // down 0..L-1, bottom, up 0..L-1
   float* hin[kMaxLevels + 1];      // input of GMP_down[i] for i >= 1 and of the bottom block (hin[0] = caller's h)
@@ -71,9 +72,14 @@ struct Work {
   float* a[2];                    // two ping-pong level-0 sized buffers
   void* packs[2 * kMaxLevels + 1];  // inference: weight packs of every block (training keeps them in the saved blobs)
   size_t fwd_bytes;               // the part a forward call touches (an inference call keeps its level inputs right behind it)
+  // BSMS_BWD_RECOMPUTE: the blobs the backward rebuilds a block's activations in, block n of the backward in blob
+  // n & 1 (one blob at depth 0), each sized for the largest level; and where the re-run forwards leave their output
+  void* blob[2];
+  float* discard;
+  size_t blob_bytes;
   size_t bytes;
 };
-Work carve_work(void* base, const Shape& s) {
+Work carve_work(void* base, const Shape& s, bool recompute = false) {
   Carver c(base);
   Work w{};
   size_t g = 0;
@@ -101,9 +107,19 @@ Work carve_work(void* base, const Shape& s) {
     const int lv = level_of_block_bwd(k, s.L);
     w.gmp_blk[k] = !per_block ? nullptr : (k == 0 ? w.gmp : (k == 1 ? w.gmp_b : c.take_bytes(bsms_gmp_work_bytes(s.B, s.N[lv], s.E[lv], s.D, s.H))));
   }
+  // behind everything the unflagged layout holds: a forward never touches them, and they stay clear of the packs
+  if (recompute) {
+    for (int i = 0; i <= s.L; ++i) w.blob_bytes = std::max(w.blob_bytes, gmp_saved_bytes(s.level(i)));
+    w.blob[0] = c.take_bytes(w.blob_bytes);
+    w.blob[1] = s.L > 0 ? c.take_bytes(w.blob_bytes) : w.blob[0];
+    w.discard = c.take(size_t(s.B) * s.N[0] * s.D);
+  }
   w.bytes = c.off;
   return w;
 }
+
+constexpr int kBwdFlags = BSMS_BWD_DEFER_JOIN | BSMS_BWD_RECOMPUTE;
+constexpr int kFwdReuse = 1 | 2 | BSMS_FWD_LEAN;
 
 int make_shape(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int H, int precision, Shape* s, const char* who) {
   BSMS_REQUIRE(plans != nullptr && L >= 0 && L <= kMaxLevels, BSMS_E_INVALID_ARG, "%s: unet_depth %d (0..%d)", who, L, kMaxLevels);
@@ -146,10 +162,22 @@ extern "C" size_t bsms_bsgmp_saved_bytes_p(const bsms_plan_t* const* plans, int 
   return carve_saved(nullptr, s, true).bytes;
 }
 extern "C" size_t bsms_bsgmp_work_bytes(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden) {
+  return bsms_bsgmp_work_bytes_ex(plans, L, B, D, p, hidden, BSMS_F32, 0);
+}
+// `flags`: those of bsms_bsgmp_bwd_ex.  BSMS_BWD_RECOMPUTE: the lean `saved` (the level inputs and the coarse positions, the layout
+// of an inference call's level inputs) and a `work` that also holds the blobs; 0: the two queries above.
+extern "C" size_t bsms_bsgmp_saved_bytes_ex(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden,
+                                            int precision, int flags) {
   Shape s;
-  if (make_shape(plans, L, B, D, p, hidden, BSMS_F32, &s, "bsgmp_work_bytes")) return 0;
+  if ((flags & ~kBwdFlags) || make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_saved_bytes_ex")) return 0;
+  return carve_saved(nullptr, s, !(flags & BSMS_BWD_RECOMPUTE)).bytes;
+}
+extern "C" size_t bsms_bsgmp_work_bytes_ex(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden,
+                                           int precision, int flags) {
+  Shape s;
+  if ((flags & ~kBwdFlags) || make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_work_bytes_ex")) return 0;
   // (an inference call keeps its level inputs behind the forward part; covered, as the backward's sets are larger)
-  const Work w = carve_work(nullptr, s);
+  const Work w = carve_work(nullptr, s, flags & BSMS_BWD_RECOMPUTE);
   return std::max(w.bytes, w.fwd_bytes + carve_saved(nullptr, s, false).bytes);
 }
 extern "C" size_t bsms_bsgmp_infer_work_bytes(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden) {
@@ -174,6 +202,13 @@ extern "C" int bsms_bsgmp_fwd_p(const bsms_plan_t* const* plans, const float* co
                                 int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
                                 const float* const* params, float* out, void* saved, void* work, int reuse, int precision,
                                 bsms_stream_t stream) {
+  BSMS_REQUIRE(!(reuse & ~kFwdReuse), BSMS_E_INVALID_ARG, "bsgmp_fwd: unknown bits in reuse = %d", reuse);
+  // BSMS_FWD_LEAN: `saved` has the lean layout -- the level inputs and the coarse positions only.  The blocks run as
+  // they do in inference (messages and aggregate in the scratch set, packs in the pack area of `work`); only the level inputs go to
+  // `saved` instead of behind the forward part of `work`.  What a block computes does not depend on where it keeps it: `out` is the
+  // full forward's bit for bit.
+  const bool lean = reuse & BSMS_FWD_LEAN;
+  BSMS_REQUIRE(!lean || saved, BSMS_E_INVALID_ARG, "bsgmp_fwd: BSMS_FWD_LEAN needs `saved` (bsms_bsgmp_saved_bytes_ex)");
   Shape s;
   int rc = make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_fwd");
   if (rc) return rc;
@@ -181,7 +216,8 @@ extern "C" int bsms_bsgmp_fwd_p(const bsms_plan_t* const* plans, const float* co
   hipStream_t st = as_stream(stream);
   const bool training = saved != nullptr;
   Work w = carve_work(work, s);
-  Saved v = training ? carve_saved(saved, s, true) : carve_saved(reinterpret_cast<char*>(work) + w.fwd_bytes, s, false);
+  Saved v = lean ? carve_saved(saved, s, false)
+                 : (training ? carve_saved(saved, s, true) : carve_saved(reinterpret_cast<char*>(work) + w.fwd_bytes, s, false));
   const int64_t posB = pos_batch_stride ? B : 1;   // a 2-D pos is shared by the batch (ops/basic.py:87-88)
 
   // Two side lanes run ahead of the blocks; both are joined before level 1 starts:
@@ -380,6 +416,9 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
                    const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
                    int precision, int flags, void* const* block_done_events, float* grad_pos, void* pos_work, hipStream_t st) {
   bsms_stream_t stream = st;
+  BSMS_REQUIRE(!(flags & ~kBwdFlags), BSMS_E_INVALID_ARG, "bsgmp_bwd: unknown bits in flags = %d", flags);
+  const bool recompute = flags & BSMS_BWD_RECOMPUTE;
+  BSMS_REQUIRE(!recompute || saved, BSMS_E_INVALID_ARG, "bsgmp_bwd: BSMS_BWD_RECOMPUTE needs the lean `saved` of the forward");
   Shape s;
   int rc = make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_bwd");
   if (rc) return rc;
@@ -393,8 +432,8 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
     if ((rc = gmp_check_grads(block(grads, k, hidden), hidden, precision, "bsgmp_bwd", &nlive, &elive))) return rc;
     lanes[k] = nlive || elive;
   }
-  Work w = carve_work(work, s);
-  Saved v = carve_saved(const_cast<void*>(saved), s, true);
+  Work w = carve_work(work, s, recompute);
+  Saved v = carve_saved(const_cast<void*>(saved), s, !recompute);   // recompute: the lean layout; run_block points v.gmp[k] at a blob
   // position gradients (bsms_bsgmp_bwd_pos): gp[l] of level l collects its up block, the adjoint of restrict_l applied to
   // gp[l + 1] and its down block, in that order -- complete when down block l is done, which is when level l - 1 needs it
   PosWork pw = carve_pos_work(grad_pos ? pos_work : nullptr, s);
@@ -425,12 +464,18 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
     const int slot = nblk & 1;
     int r;
     void* const own = w.gmp_blk[nblk];   // this block's own scratch set, or null: alternate between the two shared ones
-    if (!own && marked[slot] && ((!gmp_marks_chained() && (r = side_wait_mark(lane0, slot, st))) || (r = side_wait_mark(lane1, slot, st)))) return r;
+    // (BSMS_BWD_RECOMPUTE: blob `slot` is shared whatever the scratch sets are -- the lanes of the block before last still read it)
+    if ((!own || recompute) && marked[slot] && ((!gmp_marks_chained() && (r = side_wait_mark(lane0, slot, st))) || (r = side_wait_mark(lane1, slot, st)))) return r;
     const int order = nblk;   // position of this block in the backward's execution order
     ++nblk;
     if (lanes[k]) marked[slot] = true;   // a block without lanes marks nothing
+    if (recompute) v.gmp[k] = w.blob[slot];
     GmpCall c = block_call(s, params, v, w, k, own ? own : (slot ? w.gmp_b : w.gmp));
     c.x = x; c.pos = pos_l[level]; c.pos_bstride = pstride_l[level];
+    // BSMS_BWD_RECOMPUTE: the block's training forward again, from its stored input into the blob, on the caller's stream and in the
+    // scratch set of its backward.  Its prepack also clears the bound slots.  The skip addition is epilogue-only and reaches nothing
+    // that is saved, so the output (never read) goes without it.
+    if (recompute && (r = gmp_fwd_core(c, w.discard, nullptr, true, st))) return r;
     GmpBwdOpts o;
     o.defer_slot = slot; o.grad_pos = gp[level]; o.pos_work = pw.scratch; o.pos_accumulate = pos_acc;
     if ((r = gmp_bwd_core(c, g_in, gx, block(grads, k, hidden), o, st))) return r;

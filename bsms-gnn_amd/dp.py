@@ -146,8 +146,10 @@ class DataParallel:
     """Wraps a replica: broadcast of parameters at construction, bucketed gradient all-reduce."""
 
     def __init__(self, model, bucket_bytes=2 << 20, group=None, unroll=1, step_weights=None, detach=False, objective=None,
-                 input_grad=False, accumulate=1, reduction="batch"):
-        """`accumulate` > 1, `reduction` (step.FusedStep): every `step_loss_backward` is one micro-batch; the loss sums
+                 input_grad=False, accumulate=1, reduction="batch", recompute=False):
+        """`recompute` (step.FusedStep): activation recomputation in the U-Net's backward -- the same gradients, bit for
+        bit, from a fraction of the memory per (unrolled) step.  Only the fused step implements it.
+        `accumulate` > 1, `reduction` (step.FusedStep): every `step_loss_backward` is one micro-batch; the loss sums
         are all-reduced per micro-batch, the flat gradient buffer once, after the last fold of the cycle (`fused.ready`).  Only the
         fused step implements it.
         `unroll` > 1: the loss runs over that many autoregressive steps (step.FusedStep; `step_weights` default 1/unroll,
@@ -182,9 +184,13 @@ class DataParallel:
         if os.environ.get("BSMS_FUSED_STEP", "1") == "1" and FusedStep.supports(model) and next(model.parameters()).is_cuda:
             self.fused = FusedStep(model, self.grads, group, use_graph=os.environ.get("BSMS_STEP_GRAPH", "0") == "1",   # with unroll > 1: ValueError
                                    unroll=self.unroll, step_weights=step_weights, detach=detach, objective=self.objective,
-                                   input_grad=input_grad, accumulate=accumulate, reduction=reduction)
+                                   input_grad=input_grad, accumulate=accumulate, reduction=reduction, recompute=recompute)
         elif not isinstance(input_grad, bool):
             raise TypeError(f"DataParallel: input_grad is a bool, got {type(input_grad).__name__}")
+        elif not isinstance(recompute, bool):
+            raise TypeError(f"DataParallel: recompute is a bool, got {type(recompute).__name__}")
+        if recompute and self.fused is None:
+            raise ValueError("DataParallel: recompute needs the fused step (a standard BSMS_Simulator on the GPU, BSMS_FUSED_STEP != 0)")
         if self.fused is None and (isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1):
             raise ValueError(f"DataParallel: accumulate must be an integer >= 1, got {accumulate!r}")
         if self.fused is None and int(accumulate) > 1:

@@ -568,7 +568,7 @@ class _BSGMPFunction(torch.autograd.Function):
     ~60 Python autograd nodes."""
 
     @staticmethod
-    def forward(ctx, h, pos, plans, ews, hidden, prec, *params):
+    def forward(ctx, h, pos, plans, ews, hidden, prec, recompute, *params):
         B, _, D = h.shape
         p = pos.shape[-1]
         pos_bstride = pos.shape[-2] * p if pos.dim() == 3 else 0
@@ -577,13 +577,16 @@ class _BSGMPFunction(torch.autograd.Function):
         pl, keep_pl = _abi.ptr_array([q.handle.value if hasattr(q.handle, "value") else q.handle for q in plans])
         ewp, keep_ew = _abi.ptr_array([e.data_ptr() for e in ews])
         out = torch.empty_like(h)
-        saved = torch.empty(L.bsms_bsgmp_saved_bytes_p(pl, depth, B, D, p, hidden, prec), dtype=torch.uint8, device=h.device)
-        work = _workspace(h.device, L.bsms_bsgmp_work_bytes(pl, depth, B, D, p, hidden))
+        # recompute: the lean `saved` (block inputs and coarse positions), BSMS_FWD_LEAN / BSMS_BWD_RECOMPUTE
+        flags = BWD_RECOMPUTE if recompute else 0
+        saved = torch.empty(L.bsms_bsgmp_saved_bytes_ex(pl, depth, B, D, p, hidden, prec, flags), dtype=torch.uint8, device=h.device)
+        work = _workspace(h.device, L.bsms_bsgmp_work_bytes_ex(pl, depth, B, D, p, hidden, prec, flags))
         pp, keep = _param_ptrs(params)
         _abi.check(L.bsms_bsgmp_fwd_p(pl, ewp, depth, h.data_ptr(), pos.data_ptr(), B, D, p, pos_bstride, hidden, pp,
-                                      out.data_ptr(), saved.data_ptr(), work.data_ptr(), 0, prec, _stream()), "bsms_bsgmp_fwd")
+                                      out.data_ptr(), saved.data_ptr(), work.data_ptr(), FWD_LEAN if recompute else 0, prec, _stream()),
+                   "bsms_bsgmp_fwd")
         ctx.save_for_backward(h, pos, saved, *ews)
-        ctx.params, ctx.plans, ctx.hidden, ctx.prec = params, plans, hidden, prec
+        ctx.params, ctx.plans, ctx.hidden, ctx.prec, ctx.recompute = params, plans, hidden, prec, recompute
         return out
 
     @staticmethod
@@ -600,15 +603,25 @@ class _BSGMPFunction(torch.autograd.Function):
         gout = gout.contiguous()
         gh = torch.empty_like(h)
         if ctx.prec == 0:     # fp32: a frozen MLP (node / edge MLP of a block) gets no weight gradient at all
-            entries, grads = _grad_targets_by_mlp(params, ctx.needs_input_grad[6:], 2 * (hidden + 1))
+            entries, grads = _grad_targets_by_mlp(params, ctx.needs_input_grad[7:], 2 * (hidden + 1))
         else:                 # the bf16 precisions form every weight gradient (frozen parameters: throwaway storage)
             grads = _grad_targets(params)
             entries = [t.data_ptr() for t in grads]
-        work = _workspace(h.device, L.bsms_bsgmp_work_bytes(pl, depth, B, D, p, hidden))
+        flags = BWD_RECOMPUTE if ctx.recompute else 0
+        work = _workspace(h.device, L.bsms_bsgmp_work_bytes_ex(pl, depth, B, D, p, hidden, ctx.prec, flags))
         pp, keep = _param_ptrs(params)
         gp, keep2 = _abi.ptr_array(entries)
         gpos = None
-        if ctx.needs_input_grad[1]:   # positions as an autograd input: through every block and the pooling of the positions
+        if ctx.recompute:             # bsms_bsgmp_bwd_pos / _p take no flags: the one entry that takes everything (joined on return)
+            pwork = None
+            if ctx.needs_input_grad[1]:
+                gpos = torch.empty_like(pos)
+                pwork = torch.empty(L.bsms_bsgmp_pos_work_bytes(pl, depth, B, p), dtype=torch.uint8, device=h.device)
+            _abi.check(L.bsms_bsgmp_bwd_pos_ev(pl, ewp, depth, h.data_ptr(), pos.data_ptr(), gout.data_ptr(), B, D, p, pos_bstride,
+                                               hidden, pp, saved.data_ptr(), work.data_ptr(), gh.data_ptr(), gp, ctx.prec, flags, None,
+                                               None if gpos is None else gpos.data_ptr(), None if pwork is None else pwork.data_ptr(),
+                                               _stream()), "bsms_bsgmp_bwd_pos_ev")
+        elif ctx.needs_input_grad[1]:   # positions as an autograd input: through every block and the pooling of the positions
             gpos = torch.empty_like(pos)
             pwork = torch.empty(L.bsms_bsgmp_pos_work_bytes(pl, depth, B, p), dtype=torch.uint8, device=h.device)
             _abi.check(L.bsms_bsgmp_bwd_pos(pl, ewp, depth, h.data_ptr(), pos.data_ptr(), gout.data_ptr(), B, D, p, pos_bstride,
@@ -618,7 +631,7 @@ class _BSGMPFunction(torch.autograd.Function):
             _abi.check(L.bsms_bsgmp_bwd_p(pl, ewp, depth, h.data_ptr(), pos.data_ptr(), gout.data_ptr(), B, D, p, pos_bstride,
                                           hidden, pp, saved.data_ptr(), work.data_ptr(), gh.data_ptr(), gp, ctx.prec, _stream()),
                        "bsms_bsgmp_bwd")
-        return (gh, gpos, None, None, None, None, *grads)
+        return (gh, gpos, None, None, None, None, None, *grads)
 
 
 _PARAM_EPOCH = [0]
@@ -659,6 +672,7 @@ class InferenceSession:
         return reuse
 
 
+FWD_LEAN, BWD_RECOMPUTE = 4, 2     # include/bsms_hip.h: BSMS_FWD_LEAN (a bit of `reuse`), BSMS_BWD_RECOMPUTE (a bit of `flags`)
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16_nodes": 2}   # include/bsms_hip.h: bsms_precision (bf16: edge MLP; bf16_nodes: edge + node MLP)
 
 
@@ -729,11 +743,27 @@ class BSGMP(nn.Module):
         # in the edge MLP, fp32 accumulation and fp32 everywhere at node level.  "bf16_nodes": the node MLP of every block in
         # that arithmetic as well (include/bsms_hip.h: bsms_precision)
         self.precision = os.environ.get("BSMS_PRECISION", "f32")
+        self._recompute = False      # `recompute`, below
         self.edge_conv = WeightedEdgeConv()
         for _ in range(unet_depth):
             self.down_gmps.append(GMP(latent_dim, hidden_layer, pos_dim))
             self.up_gmps.append(GMP(latent_dim, hidden_layer, pos_dim))
             self.unpools.append(Unpool())
+
+    @property
+    def recompute(self):
+        """True (one-call path only): a training forward keeps the INPUT of every block instead of its activations,
+        and the backward rebuilds a block's activations just before it needs them -- the same bits, one more forward, a fraction
+        of the memory held between the two."""
+        return self._recompute
+
+    @recompute.setter
+    def recompute(self, value):
+        if not isinstance(value, bool):
+            raise TypeError(f"BSGMP.recompute is a bool, got {type(value).__name__}")
+        if value and self.per_block:
+            raise ValueError("BSGMP.recompute exists on the one-call U-Net path only (BSGMP.per_block must be False)")
+        self._recompute = value
 
     def _edge_weights(self, plans, m_ids, device):
         """cal_ew chain of the down pass (BSMS.py:64,73,89).  It depends on the MESH only (w starts as ones, runs
@@ -773,6 +803,8 @@ class BSGMP(nn.Module):
         """`session` (ops.InferenceSession, forward-only calls): reuse weight packs / coarse positions between calls."""
         if h.dim() not in (2, 3) or pos.dim() not in (2, 3):
             raise NotImplementedError("Only implemented for dim 2 and 3")
+        if self._recompute and self.per_block:
+            raise ValueError("BSGMP.recompute exists on the one-call U-Net path only (BSGMP.per_block must be False)")
         h = _dev_f32(h, "BSGMP")
         pos = _dev_f32(pos, "BSGMP")
         L = self.unet_depth
@@ -792,7 +824,7 @@ class BSGMP(nn.Module):
             hidden = self.bottom_gmp.hidden_layer
             prec = PRECISIONS[self.precision]
             if _needs_grad(h, pos, *params):
-                y = _BSGMPFunction.apply(h, pos, all_plans, ews, hidden, prec, *params)
+                y = _BSGMPFunction.apply(h, pos, all_plans, ews, hidden, prec, self._recompute, *params)
             else:
                 y = _bsgmp_infer(h, pos, all_plans, ews, hidden, params, session, prec)
             return y.squeeze(0) if squeeze else y

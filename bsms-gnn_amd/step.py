@@ -37,7 +37,12 @@ bsms_grad_fold leaves a * grads.flat + b * scratch: the gradient of the loss ove
 
 Frozen parameters: an MLP -- encoder, decoder, a block's node or edge MLP -- all of whose parameters have
 `requires_grad == False` gets NULL entries in the gradient tables; the backward then launches nothing for its weight gradients.
-With nothing trainable (or `param_grad=False`) and `input_grad=True` the backward is data-only."""
+With nothing trainable (or `param_grad=False`) and `input_grad=True` the backward is data-only.
+
+`recompute=True`: the U-Net's forward keeps only the inputs of its blocks (the lean `s_proc`, BSMS_FWD_LEAN) and its
+backward rebuilds every block's activations just before it needs them (BSMS_BWD_RECOMPUTE), into two blobs in `work`, which all K steps
+share.  Every loss, prediction and gradient keeps its bits; a backward costs one more U-Net forward; what a step holds per unrolled
+step drops by the blocks' saved activations -- nearly all of it."""
 import os
 import sys
 
@@ -45,7 +50,7 @@ import torch
 import torch.distributed as dist
 
 from . import _abi
-from .ops import PRECISIONS, _param_ptrs, _stream
+from .ops import BWD_RECOMPUTE, FWD_LEAN, PRECISIONS, _param_ptrs, _stream
 
 
 REDUCTIONS = {"batch": 0, "mean": 1}             # BSMS_ACCUM_BATCH / BSMS_ACCUM_MEAN
@@ -95,8 +100,10 @@ class _Arena:
 
 class FusedStep:
     def __init__(self, model, grads, group=None, use_graph=False, unroll=1, step_weights=None, detach=False, objective=None,
-                 input_grad=False, param_grad=True, accumulate=1, reduction="batch"):
-        """`accumulate=M > 1`: every call is one MICRO-batch; after the t-th call of a cycle `grads.flat` holds the
+                 input_grad=False, param_grad=True, accumulate=1, reduction="batch", recompute=False):
+        """`recompute`: activation recomputation in the U-Net's backward: the same bits from a fraction of the memory
+        per (unrolled) step, for one more U-Net forward per backward.  Off: nothing changes.
+        `accumulate=M > 1`: every call is one MICRO-batch; after the t-th call of a cycle `grads.flat` holds the
         gradient of the loss over all samples of the cycle so far (`reduction="batch"`), or the mean of the micro-batch gradients
         (`reduction="mean"`, what `(loss / M).backward()` gives); `ready` after the M-th, and the next call starts a new cycle.
         `objective` (objective.Objective): None or the default objective keeps the reference's masked RMSE on the kernels it
@@ -125,6 +132,10 @@ class FusedStep:
         if not isinstance(input_grad, bool):
             raise TypeError(f"FusedStep: input_grad is a bool, got {type(input_grad).__name__}")
         self._input_grad, self._ig_ran = input_grad, False
+        if not isinstance(recompute, bool):
+            raise TypeError(f"FusedStep: recompute is a bool, got {type(recompute).__name__}")
+        self.recompute = recompute
+        self._proc_flags = BWD_RECOMPUTE if recompute else 0       # `flags` of the U-Net's size queries
         self._param_grad = bool(param_grad)
         if not self._param_grad and not input_grad:
             raise ValueError("FusedStep: param_grad=False without input_grad=True would compute nothing")
@@ -283,10 +294,11 @@ class FusedStep:
                  norm_pred=f("norm_pred", R, C), pred=f("pred", B, N, C),
                  sums=f("sums", 2), loss=f("loss", 1), g_np=f("g_np", R, C), gh1=f("gh1", R, D), gh0=f("gh0", R, D),
                  s_enc=u8("s_enc", L.bsms_mlp_saved_bytes(R, C + 1, D, D, H)), s_dec=u8("s_dec", L.bsms_mlp_saved_bytes(R, D, D, C, H)),
-                 s_proc=u8("s_proc", L.bsms_bsgmp_saved_bytes_p(pl, depth, B, D, p, H, PRECISIONS[m.process.precision])),
+                 s_proc=u8("s_proc", L.bsms_bsgmp_saved_bytes_ex(pl, depth, B, D, p, H, PRECISIONS[m.process.precision], self._proc_flags)),
                  prec=m.process.precision,
                  work=u8("work", max(L.bsms_mlp_work_bytes(R, C + 1, D, D, H), L.bsms_mlp_work_bytes(R, D, D, C, H),
-                                     L.bsms_bsgmp_work_bytes(pl, depth, B, D, p, H), L.bsms_sim_work_bytes(R))),
+                                     L.bsms_bsgmp_work_bytes_ex(pl, depth, B, D, p, H, PRECISIONS[m.process.precision], self._proc_flags),
+                                     L.bsms_sim_work_bytes(R))),
                  work_enc=u8("work_enc", L.bsms_mlp_work_bytes(R, C + 1, D, D, H)),   # the encoder's backward overlaps the U-Net's last weight gradients
                  work_dec=u8("work_dec", L.bsms_mlp_work_bytes(R, D, D, C, H)),       # the decoder's weight gradients run under the U-Net's first block
                  in_static=None)
@@ -319,7 +331,10 @@ class FusedStep:
 
     def _pack_group(self, b, B):
         """The packs of every buffer set of the step (one set, or the K sets of the unrolled step: the weights are the same for all
-        K forwards) as ONE group: encoder, the 2L+1 blocks, decoder -- where the forwards with `reuse` read them."""
+        K forwards) as ONE group: encoder, the 2L+1 blocks, decoder -- where the forwards with `reuse` read them.
+        `recompute`: the encoder and the decoder only -- the lean forward keeps the blocks' packs in `work`, which the encoder's forward
+        scribbles on behind the group's launch, so the U-Net packs per call (2L + 1 launches on its pack lane, as without a group); the
+        backward's re-run forwards pack for themselves anyway."""
         if self._pg is not None:
             return self._pg
         import ctypes
@@ -331,8 +346,9 @@ class FusedStep:
         try:
             for bk in (b.get("steps") or [b]):
                 _abi.check(L.bsms_pack_group_add_mlp(h, R, C + 1, D, D, H, 1, t["enc"][0][0], bk["s_enc"].data_ptr(), None), "bsms_pack_group_add_mlp(encode)")
-                _abi.check(L.bsms_pack_group_add_bsgmp(h, b["pl"], b["depth"], B, D, p, H, t["proc"][0][0], bk["s_proc"].data_ptr(), None,
-                                                       PRECISIONS[b["prec"]]), "bsms_pack_group_add_bsgmp")
+                if not self.recompute:
+                    _abi.check(L.bsms_pack_group_add_bsgmp(h, b["pl"], b["depth"], B, D, p, H, t["proc"][0][0], bk["s_proc"].data_ptr(), None,
+                                                           PRECISIONS[b["prec"]]), "bsms_pack_group_add_bsgmp")
                 _abi.check(L.bsms_pack_group_add_mlp(h, R, D, D, C, H, 0, t["dec"][0][0], bk["s_dec"].data_ptr(), None), "bsms_pack_group_add_mlp(decode)")
         except Exception:
             L.bsms_pack_group_destroy(h)
@@ -383,7 +399,8 @@ class FusedStep:
                              work.data_ptr(), reuse, s), "bsms_mlp_fwd(encode)")
         ewp, keep = _abi.ptr_array([e.data_ptr() for e in ews])
         ck(L.bsms_bsgmp_fwd_p(b["pl"], ewp, b["depth"], b["h0"].data_ptr(), b["pos"].data_ptr(), B, D, p, N * p, H, t["proc"][0][0],
-                              b["h1"].data_ptr(), b["s_proc"].data_ptr(), work.data_ptr(), reuse, PRECISIONS[b["prec"]], s), "bsms_bsgmp_fwd")
+                              b["h1"].data_ptr(), b["s_proc"].data_ptr(), work.data_ptr(), FWD_LEAN if self.recompute else reuse,
+                              PRECISIONS[b["prec"]], s), "bsms_bsgmp_fwd")     # (the lean forward packs per call: _pack_group)
         ck(L.bsms_mlp_fwd_ex(b["h1"].data_ptr(), R, D, D, C, H, 0, t["dec"][0][0], b["norm_pred"].data_ptr(), b["s_dec"].data_ptr(),
                              work.data_ptr(), reuse, s), "bsms_mlp_fwd(decode)")
         if self._obj is None:
@@ -437,16 +454,17 @@ class FusedStep:
         ck(L.bsms_mlp_bwd_ex(b["h1"].data_ptr(), b["g_np"].data_ptr(), R, D, D, C, H, 0, t["dec"][0][0], b["s_dec"].data_ptr(),
                              b["work_dec"].data_ptr(), b["gh1"].data_ptr(), t["dec"][1][0], 1, s), "bsms_mlp_bwd(decode)")   # 1 = BSMS_BWD_DEFER_JOIN
         ewp, keep = _abi.ptr_array([e.data_ptr() for e in ews])
+        flags = 1 | self._proc_flags                  # BSMS_BWD_DEFER_JOIN (| BSMS_BWD_RECOMPUTE)
         # BSMS_BWD_DEFER_JOIN: the weight gradients of the last (level-0) block are still running on the engine's side
         # streams (~0.2 ms on half the chip) while the encoder's backward -- own scratch, own gradient slots -- runs here
         if ig is None:
             ck(L.bsms_bsgmp_bwd_ev(b["pl"], ewp, b["depth"], b["h0"].data_ptr(), b["pos"].data_ptr(), b["gh1"].data_ptr(), B, D, p, N * p, H,
                                    t["proc"][0][0], b["s_proc"].data_ptr(), work.data_ptr(), b["gh0"].data_ptr(), t["proc"][1][0],
-                                   PRECISIONS[b["prec"]], 1, None if events is None else events[0], s), "bsms_bsgmp_bwd")
+                                   PRECISIONS[b["prec"]], flags, None if events is None else events[0], s), "bsms_bsgmp_bwd")
         else:                                         # the same schedule, plus the position kernels on this stream (g_pos is complete on return)
             ck(L.bsms_bsgmp_bwd_pos_ev(b["pl"], ewp, b["depth"], b["h0"].data_ptr(), b["pos"].data_ptr(), b["gh1"].data_ptr(), B, D, p, N * p, H,
                                        t["proc"][0][0], b["s_proc"].data_ptr(), work.data_ptr(), b["gh0"].data_ptr(), t["proc"][1][0],
-                                       PRECISIONS[b["prec"]], 1, None if events is None else events[0], ig["g_pos"].data_ptr(),
+                                       PRECISIONS[b["prec"]], flags, None if events is None else events[0], ig["g_pos"].data_ptr(),
                                        ig["pos_work"].data_ptr(), s), "bsms_bsgmp_bwd_pos")
         ck(L.bsms_mlp_bwd(b["norm_in"].data_ptr(), b["gh0"].data_ptr(), R, C + 1, D, D, H, 1, t["enc"][0][0], b["s_enc"].data_ptr(),
                           b["work_enc"].data_ptr(), None if chain is None else _ptr(chain["grad_x"]), t["enc"][1][0], s),
@@ -495,6 +513,18 @@ class FusedStep:
 
     # ------------------------------------------------------------------------------------------------ the unrolled step
     _PER_STEP = ("s_enc", "s_proc", "s_dec", "norm_in", "h0", "h1", "pred", "sums")     # saved per step; everything else is shared
+
+    def held_bytes(self):
+        """dict(per_step=, shared=): the bytes of the step's device buffers (capacities of its arena; no allocator statistics).
+        `per_step`: what one unrolled step owns -- the `_PER_STEP` names, and with unroll > 1 the step's input (`in@k`; the first
+        step's is the caller's), i.e. what unroll + 1 would add.  `shared`: everything else, whatever the unroll.  All buffers
+        together: shared + (step 0: the `_PER_STEP` names) + (unroll - 1) x per_step."""
+        if self._shape_key is None:
+            raise RuntimeError("FusedStep.held_bytes: the step has not run yet")
+        cap = {n: t.numel() * t.element_size() for n, t in self._arena._t.items() if t is not None}
+        owned = lambda k: sum(cap.get(n if k == 0 else f"{n}@{k}", 0) for n in (*self._PER_STEP, *(("in",) if k else ())))
+        steps = [owned(k) for k in range(self.unroll)]
+        return dict(per_step=steps[1] if self.unroll > 1 else steps[0], shared=sum(cap.values()) - sum(steps))
 
     def _unroll_buffers(self, b, B, N, dev):
         """Step k's own buffers (`name@k` in the arena) on top of the shared ones of `_buffers`, which serve as step 0's."""
@@ -839,12 +869,14 @@ class FusedStep:
         return b["loss"][0].clone()
 
 
-def _input_gradient_key(K, step_weights, detach, objective, param_grad):
-    """Cache key of `input_gradient`'s steps: one FusedStep per (K, step_weights, detach, objective, param_grad)."""
-    return (int(K), None if step_weights is None else tuple(float(w) for w in step_weights), bool(detach), objective, bool(param_grad))
+def _input_gradient_key(K, step_weights, detach, objective, param_grad, recompute=False):
+    """Cache key of `input_gradient`'s steps: one FusedStep per (K, step_weights, detach, objective, param_grad, recompute)."""
+    return (int(K), None if step_weights is None else tuple(float(w) for w in step_weights), bool(detach), objective, bool(recompute),
+            bool(param_grad))
 
 
-def input_gradient(model, data, consistent=True, later_targets=None, step_weights=None, detach=False, objective=None, param_grad=True):
+def input_gradient(model, data, consistent=True, later_targets=None, step_weights=None, detach=False, objective=None, param_grad=True,
+                   recompute=False):
     """Sensitivity of a (rollout) objective of a trained `BSMS_Simulator`: returns `(loss, grad_node_in)`, the weighted K-step loss
     and its gradient w.r.t. `node_in` -- initial state, mesh positions, node type; [B, N, C+p+1], or [1, rows, C+p+1] for variable
     meshes.  K = 1 without `later_targets`, else `later_targets.shape[0] + 1`; `step_weights`, `detach` and
@@ -858,18 +890,23 @@ def input_gradient(model, data, consistent=True, later_targets=None, step_weight
 
     `param_grad=False`: the backward is data-only whatever `requires_grad` says -- no weight gradient is formed,
     no `GradBuckets` is created and no `p.grad` is touched or created; loss and gradient are bit-identical to `param_grad=True`'s.
-    fp32 precision only."""
+    fp32 precision only.
+
+    `recompute=True`: FusedStep's -- the adjoint through a long rollout holds the blocks' inputs per step instead of
+    their activations; loss and gradient keep their bits."""
     from .dp import GradBuckets
     from .objective import Objective
     K = 1 if later_targets is None else int(later_targets.shape[0]) + 1
     objective = Objective() if objective is None else objective
-    key = _input_gradient_key(K, step_weights, detach, objective, param_grad)
+    if not isinstance(recompute, bool):
+        raise TypeError(f"input_gradient: recompute is a bool, got {type(recompute).__name__}")
+    key = _input_gradient_key(K, step_weights, detach, objective, param_grad, recompute)
     cache = model.__dict__.setdefault("_bsms_input_grad_steps", {})
     step = cache.get(key)
     if step is None:
         if param_grad and "grads" not in cache:
             cache["grads"] = GradBuckets(list(model.parameters()))
         step = cache[key] = FusedStep(model, cache["grads"] if param_grad else None, unroll=K, step_weights=step_weights, detach=detach,
-                                      objective=objective, input_grad=True, param_grad=bool(param_grad))
+                                      objective=objective, input_grad=True, param_grad=bool(param_grad), recompute=recompute)
     loss = step(data, consistent, later_targets)
     return loss, step.input_grad().clone()

@@ -318,6 +318,16 @@ class DevicePrefetcher:
             th.join(timeout=5.0)
 
 
+def recompute_from_cfg(model_cfg):
+    """`model_cfg.recompute_activations` (optional): absent or None is False, the route without the key."""
+    v = getattr(model_cfg, "recompute_activations", None)
+    if v is None:
+        return False
+    if not isinstance(v, bool):
+        raise TypeError(f"model_cfg.recompute_activations is a bool, got {v!r}")
+    return v
+
+
 class Trainer:
     """src/trainer/trainer.py:9-229.  `model_cfg` needs consistent_mesh, accumulation_steps; `opt_cfg` needs
     peak_lr, weight_decay, warmup_steps, decay_steps, gnorm_clip (configs/opt/default.yaml).  Optional in `opt_cfg` (DESIGN.md 4.15;
@@ -326,7 +336,9 @@ class Trainer:
     unroll_steps (default 1: the reference's single-step loss), unroll_weights, unroll_detach -- the loss over that many
     autoregressive steps (step.FusedStep); `iter` then takes `(batch, later_targets)`, what TrajectoryBank(horizon=K) hands out;
     loss_space ("physical" / "normalized"), loss_kind ("rmse" / "mse"), loss_channel_weights -- the training objective
-    (objective.Objective; absent: the reference's masked RMSE in physical units), which `iter` trains on and `get_loss` reports.
+    (objective.Objective; absent: the reference's masked RMSE in physical units), which `iter` trains on and `get_loss` reports;
+    recompute_activations (absent or false: off) -- the fused step holds the U-Net blocks' inputs instead of their
+    activations and recomputes in the backward: the same parameters after every step, bit for bit, less memory per unrolled step.
     Optional in `opt_cfg`: gradient_accumulation_steps = M (absent or 1: every `iter` is an optimizer step) and
     accumulation_reduction ("batch", the default: the exact loss over the M micro-batches; "mean": the mean of their gradients).  After
     warm-up the optimizer step, the LR-schedule step and the parameter epoch then happen on every M-th `iter` only; `train_step`
@@ -345,7 +357,8 @@ class Trainer:
         self.last_accumulated_loss = None          # device scalar: the loss over every sample of the last completed cycle
         self.dp = DataParallel(self.model, unroll=self.unroll, step_weights=getattr(model_cfg, "unroll_weights", None),
                                detach=bool(getattr(model_cfg, "unroll_detach", False)), objective=self.objective,      # world size 1: no collective is issued
-                               accumulate=self.accumulate, reduction=opt("accumulation_reduction", None) or "batch")
+                               accumulate=self.accumulate, reduction=opt("accumulation_reduction", None) or "batch",
+                               recompute=recompute_from_cfg(model_cfg))
         no_decay_bias, lr_scales = bool(opt("no_decay_bias", False)), opt("lr_scales", None)
         groups = param_groups(self.model, no_decay_bias, lr_scales) if (no_decay_bias or lr_scales) else None
         self.optimizer = FusedAdamW(self.dp.grads, lr=opt_cfg.peak_lr, weight_decay=opt_cfg.weight_decay,

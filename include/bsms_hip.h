@@ -329,6 +329,29 @@ int bsms_bsgmp_bwd(const bsms_plan_t* const* plans, const float* const* ew, int 
  * work that touches neither `work` nor `grads` (the fused training step runs the encoder's backward there, with its own
  * scratch) and MUST call bsms_side_lanes_join(stream) before anything reads `grads`, reuses `work`, or the step ends. */
 enum { BSMS_BWD_DEFER_JOIN = 1 };
+/* ACTIVATION RECOMPUTATION: a forward / backward pair that keeps only the INPUT of every block between the two
+ * calls, for long unrolled losses whose K steps each hold a `saved`.
+ *   BSMS_FWD_LEAN, a bit of bsms_bsgmp_fwd_p's `reuse`: `saved` (non-null, else BSMS_E_INVALID_ARG) has the LEAN layout -- the
+ *     inputs of the blocks on levels 1..L, the positions of levels 1..L and the inputs of the L up blocks, fp32 in every precision;
+ *     bsms_bsgmp_saved_bytes_ex(.., BSMS_BWD_RECOMPUTE) bytes.  The blocks run as in inference, with their packs in the pack area of
+ *     `work`; bits 0 / 1 of `reuse` keep their inference meaning for those packs (bit 1 is ignored).  `out` is bit-identical to the
+ *     full forward's.
+ *   BSMS_BWD_RECOMPUTE, a bit of `flags` of bsms_bsgmp_bwd_ex / _ev / _pos_ev: `saved` is the lean one of such a forward, `work`
+ *     has bsms_bsgmp_work_bytes_ex(.., BSMS_BWD_RECOMPUTE) bytes.  In front of every block's backward its training forward runs again
+ *     on `stream` (prepack included) from the stored input into one of two blobs at the end of `work`; block n of the backward uses
+ *     blob n & 1 and first waits for the weight-gradient lanes of block n - 2, which read that blob.  Every gradient is bit-identical
+ *     to the unflagged pair's; the price is one more U-Net forward.  `saved` is only read: any number of backwards may follow one
+ *     forward.  `work` may be shared by any number of (forward, backward) pairs on one stream.  Under BSMS_BWD_DEFER_JOIN the blobs
+ *     belong to the lanes until bsms_side_lanes_join, like the rest of `work`.
+ * The `_ex` size queries take the backward's `flags`: 0 gives bsms_bsgmp_saved_bytes_p / bsms_bsgmp_work_bytes, bit for bit; unknown
+ * bits or a bad shape give 0.  Unknown bits in `reuse` or `flags` of a call, and BSMS_BWD_RECOMPUTE without `saved`, are
+ * BSMS_E_INVALID_ARG, checked before anything else.  The one-block bsms_gmp_* entries have no such mode. */
+enum { BSMS_FWD_LEAN = 4 };
+enum { BSMS_BWD_RECOMPUTE = 2 };
+size_t bsms_bsgmp_saved_bytes_ex(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden, int precision,
+                                 int flags);
+size_t bsms_bsgmp_work_bytes_ex(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden, int precision,
+                                int flags);
 int bsms_bsgmp_bwd_ex(const bsms_plan_t* const* plans, const float* const* ew, int L, const float* h, const float* pos,
                       const float* grad_out, int64_t B, int64_t D, int64_t p, int64_t pos_batch_stride, int hidden,
                       const float* const* params, const void* saved, void* work, float* grad_h, float* const* grads,
