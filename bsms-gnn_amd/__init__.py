@@ -10,7 +10,7 @@ from .ops import BSGMP, GMP, MLP, InferenceSession, Unpool, WeightedEdgeConv, de
 from .eval import equivariance_error, error_mean_std  # noqa: F401
 from .databank import Augment, TrajectoryBank, epoch_picks, transform_rows  # noqa: F401
 from .dp import DataParallel, GradBuckets, global_masked_rmse  # noqa: F401
-from .hierarchy import BistrideMultiLayerGraph, to_flat_edge  # noqa: F401
+from .hierarchy import BistrideMultiLayerGraph, lumped_node_measure, to_flat_edge  # noqa: F401
 from .rollout import RolloutErrors, rank_slice, rollout_bank, rollout_batch, rollout_dataset, rollout_errors, rollout_one_traj, rollout_rmse  # noqa: F401
 from .step import FusedStep, input_gradient  # noqa: F401
 from .trainer import DevicePrefetcher, FusedAdamW, Trainer, WarmupCosineDecay, param_groups, segment_table  # noqa: F401

@@ -290,13 +290,16 @@ namespace {
 // (bsms_error_sums); every thread forms the C per-channel coefficients G * a_c from it in fp64 and rounds each to fp32 once.
 // The carry and the way out through the de-normalisation are those of k_sim_unroll_bwd, op for op.  No guard for M == 0 or
 // loss == 0, as in k_sim_loss_bwd: the non-finite coefficient reaches the output.
-__global__ __launch_bounds__(256) void k_sim_objective_bwd(const float* pred, const float* target, const float* mask, int64_t R,
-                                                           int C, const double* mean, const double* meansq, const double* eps,
-                                                           const double* in_mean, const double* in_meansq, const double* in_eps,
-                                                           const double* sums, const double* weights, int normalized, int rmse,
-                                                           float w, const float* g_pred_next, const float* g_norm_in_next,
-                                                           float* loss_out, float* chan_out, float* g_pred,
-                                                           float* grad_norm_pred) {
+// kWeighted (bsms_sim_objective_bwd_w): row r's loss gradient carries mu = m * row_weights[r % period], ONE fp32 product formed first,
+// so (d * mu) * coef is the unweighted (d * m) * coef whenever the weight is 1.  The mask of the carry and of the way out stays m.
+template <bool kWeighted>
+__device__ __forceinline__ void sim_objective_bwd_row(const float* pred, const float* target, const float* mask,
+                                                      const float* row_weights, int64_t weight_period, int64_t R, int C,
+                                                      const double* mean, const double* meansq, const double* eps,
+                                                      const double* in_mean, const double* in_meansq, const double* in_eps,
+                                                      const double* sums, const double* weights, int normalized, int rmse, float w,
+                                                      const float* g_pred_next, const float* g_norm_in_next, float* loss_out,
+                                                      float* chan_out, float* g_pred, float* grad_norm_pred) {
   const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
   const double e = *eps;
   const double MC = sums[0] * double(C);
@@ -315,11 +318,12 @@ __global__ __launch_bounds__(256) void k_sim_objective_bwd(const float* pred, co
   if (r >= R) return;
   const double G = rmse ? 1.0 / (loss * MC) : 2.0 / MC;
   const float m = mask[r];
+  const float mu = kWeighted ? m * row_weights[r % weight_period] : m;
   const bool carried = g_pred_next != nullptr && m != 0.f;
   const double ie = g_pred_next ? *in_eps : 0.0;
   for (int c = 0; c < C; ++c) {
     const float coef = float(G * a[c]);
-    float gp = (pred[r * C + c] - target[r * C + c]) * m * coef;
+    float gp = (pred[r * C + c] - target[r * C + c]) * mu * coef;
     gp = w * gp;
     if (carried) {
       const float through_norm = float(double(g_norm_in_next[r * (C + 1) + c]) / std_eps(in_mean[c], in_meansq[c], ie));
@@ -330,6 +334,29 @@ __global__ __launch_bounds__(256) void k_sim_objective_bwd(const float* pred, co
     const float gd = gp * m;
     grad_norm_pred[r * C + c] = float(double(gd) * sd[c]);
   }
+}
+
+__global__ __launch_bounds__(256) void k_sim_objective_bwd(const float* pred, const float* target, const float* mask, int64_t R,
+                                                           int C, const double* mean, const double* meansq, const double* eps,
+                                                           const double* in_mean, const double* in_meansq, const double* in_eps,
+                                                           const double* sums, const double* weights, int normalized, int rmse,
+                                                           float w, const float* g_pred_next, const float* g_norm_in_next,
+                                                           float* loss_out, float* chan_out, float* g_pred,
+                                                           float* grad_norm_pred) {
+  sim_objective_bwd_row<false>(pred, target, mask, nullptr, 1, R, C, mean, meansq, eps, in_mean, in_meansq, in_eps, sums, weights,
+                               normalized, rmse, w, g_pred_next, g_norm_in_next, loss_out, chan_out, g_pred, grad_norm_pred);
+}
+
+__global__ __launch_bounds__(256) void k_sim_objective_bwd_w(const float* pred, const float* target, const float* mask,
+                                                             const float* row_weights, int64_t weight_period, int64_t R, int C,
+                                                             const double* mean, const double* meansq, const double* eps,
+                                                             const double* in_mean, const double* in_meansq, const double* in_eps,
+                                                             const double* sums, const double* weights, int normalized, int rmse,
+                                                             float w, const float* g_pred_next, const float* g_norm_in_next,
+                                                             float* loss_out, float* chan_out, float* g_pred,
+                                                             float* grad_norm_pred) {
+  sim_objective_bwd_row<true>(pred, target, mask, row_weights, weight_period, R, C, mean, meansq, eps, in_mean, in_meansq, in_eps, sums,
+                              weights, normalized, rmse, w, g_pred_next, g_norm_in_next, loss_out, chan_out, g_pred, grad_norm_pred);
 }
 
 }  // namespace
@@ -354,6 +381,34 @@ extern "C" int bsms_sim_objective_bwd(const float* pred, const float* target, co
                      (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, channel_weights,
                      int(space == BSMS_LOSS_NORMALIZED), int(kind == BSMS_LOSS_RMSE), w, g_pred_next, g_norm_in_next, loss_out,
                      chan_out, g_pred, grad_norm_pred);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}
+
+// bsms_sim_objective_bwd with a weight per row (include/bsms_hip.h): the checks of that entry in its order, each followed at once by
+// the weighted argument that belongs to it.
+extern "C" int bsms_sim_objective_bwd_w(const float* pred, const float* target, const float* mask, const float* row_weights,
+                                        int64_t weight_period, int64_t R, int64_t C, const double* mean, const double* meansq,
+                                        const double* std_eps_dev, const double* in_mean, const double* in_meansq,
+                                        const double* in_std_eps_dev, const double* sums, const double* channel_weights, int space,
+                                        int kind, float w, const float* g_pred_next, const float* g_norm_in_next, float* loss_out,
+                                        float* chan_out, float* g_pred, float* grad_norm_pred, bsms_stream_t stream) {
+  BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "sim_objective_bwd_w: R=%lld C=%lld", (long long)R, (long long)C);
+  BSMS_REQUIRE((space == BSMS_LOSS_PHYSICAL || space == BSMS_LOSS_NORMALIZED) && (kind == BSMS_LOSS_MSE || kind == BSMS_LOSS_RMSE),
+               BSMS_E_UNSUPPORTED, "sim_objective_bwd_w: space=%d kind=%d (each 0 or 1)", space, kind);
+  BSMS_REQUIRE(pred && target && mask && row_weights && mean && meansq && std_eps_dev && sums && grad_norm_pred, BSMS_E_INVALID_ARG,
+               "sim_objective_bwd_w: null argument");
+  BSMS_REQUIRE(weight_period >= 1 && weight_period <= R && R % weight_period == 0, BSMS_E_INVALID_ARG,
+               "sim_objective_bwd_w: weight_period=%lld does not divide R=%lld", (long long)weight_period, (long long)R);
+  BSMS_REQUIRE((g_pred_next == nullptr) == (g_norm_in_next == nullptr), BSMS_E_INVALID_ARG,
+               "sim_objective_bwd_w: the carried pair (g_pred_next, g_norm_in_next) is given together or not at all");
+  BSMS_REQUIRE(!g_pred_next || (in_mean && in_meansq && in_std_eps_dev), BSMS_E_INVALID_ARG,
+               "sim_objective_bwd_w: a carried gradient needs the input normaliser's statistics");
+  BSMS_REQUIRE(!g_pred || (g_pred != g_pred_next), BSMS_E_INVALID_ARG, "sim_objective_bwd_w: g_pred aliases g_pred_next");
+  hipLaunchKernelGGL(k_sim_objective_bwd_w, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask,
+                     row_weights, weight_period, R, (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums,
+                     channel_weights, int(space == BSMS_LOSS_NORMALIZED), int(kind == BSMS_LOSS_RMSE), w, g_pred_next, g_norm_in_next,
+                     loss_out, chan_out, g_pred, grad_norm_pred);
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }

@@ -165,7 +165,7 @@ def transform_rows(x, rows_per_sample, transforms, groups, inverse=False, out=No
 
 
 class _Traj:
-    __slots__ = ("state", "pos", "type", "pos_static", "type_static", "T", "N", "entry")
+    __slots__ = ("state", "pos", "type", "pos_static", "type_static", "T", "N", "entry", "weights")
 
 
 class TrajectoryBank:
@@ -174,10 +174,16 @@ class TrajectoryBank:
     `horizon` = K > 1 serves an unrolled loss over K steps: a pick (trajectory, t) then needs the frames t+1 .. t+K, so the epoch
     order stops K frames before the end, and `batch` also returns the later targets (frames t+2 .. t+K, without noise).
     `augment` (None: `Augment.from_cfg(cfg)`, which is None for a config without the keys): training batches are seen in a
-    freshly drawn frame per sample; evaluation batches, `trajectory` and the rollouts stay in the data's frame."""
+    freshly drawn frame per sample; evaluation batches, `trajectory` and the rollouts stay in the data's frame.
+    `node_weights="measure"`: `add` also keeps every trajectory's `hierarchy.lumped_node_measure` resident (float32 [N],
+    from its `cells` and its first frame's positions, which must be static) for a node-weighted objective; `node_weights(picks)` and
+    `batch(..., return_weights=True)` hand them out.  None: nothing is computed, kept or returned."""
 
     def __init__(self, cfg, dataset="airfoil", device=None, seed=0, process=None, max_bytes=None, order="trajectory", cache_dir=None,
-                 horizon=1, augment=None):
+                 horizon=1, augment=None, node_weights=None):
+        if node_weights not in (None, "measure"):
+            raise ValueError(f'TrajectoryBank: node_weights must be None or "measure", got {node_weights!r}')
+        self._weights_kind = node_weights
         if dataset not in VALID_TYPES:
             raise ValueError(f"dataset must be one of {sorted(VALID_TYPES)}, got {dataset!r}")
         if order not in ("trajectory", "global"):
@@ -292,6 +298,15 @@ class TrajectoryBank:
             raise ValueError(f"TrajectoryBank.add: node_type must be [T,N,1], got {tuple(typ.shape)}")
         self._record_fields(fields, int(pos.shape[-1]))
         tr.pos_static, tr.type_static = bool((pos == pos[:1]).all()), bool((typ == typ[:1]).all())
+        measure = None
+        if self._weights_kind == "measure":           # refused before anything of this trajectory is uploaded or claimed
+            if fields.get("cells") is None:
+                raise ValueError('TrajectoryBank.add: node_weights="measure" needs the trajectory\'s "cells" (cfg.field_names)')
+            if not tr.pos_static:
+                raise ValueError('TrajectoryBank.add: node_weights="measure" needs static positions: one measure per trajectory')
+            from .hierarchy import lumped_node_measure
+            cells = np.asarray(fields["cells"])
+            measure = torch.from_numpy(lumped_node_measure(pos[0].numpy(), cells[0] if cells.ndim == 3 else cells, cfg.mesh_type))
         tr.entry = None
         if cfg.consist_mesh:
             if self._hier is None:
@@ -306,6 +321,7 @@ class TrajectoryBank:
         tr.state = self._put(state)
         tr.pos = self._put(pos[0] if tr.pos_static else pos)
         tr.type = self._put(typ[0] if tr.type_static else typ)
+        tr.weights = None if measure is None else self._put(measure)
         self._trajs.append(tr)
         return len(self._trajs) - 1
 
@@ -383,7 +399,19 @@ class TrajectoryBank:
             v = self._views[B] = ([g.unsqueeze(0).expand(B, *g.shape) for g in m_gs], [i.unsqueeze(0).expand(B, *i.shape) for i in m_ids])
         return v
 
-    def batch(self, picks, train=True, draw=None, return_noise=False, horizon=None, transforms=None, return_transforms=False):
+    def node_weights(self, picks):
+        """The node weights of the samples of `picks` as the step takes them: [B, N] on a consistent mesh, the flat concatenation
+        [rows] for variable meshes (a copy; the resident vectors are per trajectory)."""
+        if self._weights_kind is None:
+            raise ValueError('TrajectoryBank.node_weights: the bank was built without node_weights="measure"')
+        picks = list(picks)
+        if not picks:
+            raise ValueError("TrajectoryBank.node_weights: no picks")
+        w = [self._trajs[int(si)].weights for si, _ in picks]
+        return torch.stack(w) if self.cfg.consist_mesh else torch.cat(w)
+
+    def batch(self, picks, train=True, draw=None, return_noise=False, horizon=None, transforms=None, return_transforms=False,
+              return_weights=False):
         """The device batch of `picks`, a list of (trajectory, frame).  `train`: inject the training noise; `draw` selects the
         noise of this batch (None: the bank's running batch counter, which then advances).  Consistent mesh:
         [node_in [B,N,C+p+1], node_tar [B,N,C], node_mask [B,N,1], m_gs, m_ids]; variable meshes: the per-level LevelData list.
@@ -394,7 +422,10 @@ class TrajectoryBank:
         Frames: a bank with an `augment` sees a `train` batch through `augment.sample(p, B, seed, draw)`, one matrix per pick,
         applied before the noise to positions and vector fields, and to the later targets; `train=False` stays in the data's frame.
         `transforms` [B,p,p] (tensor or array) is applied instead, whatever `train` says and with or without an `augment`.
-        `return_transforms` appends the host fp32 array that was applied (None when the batch is in the data's frame)."""
+        `return_transforms` appends the host fp32 array that was applied (None when the batch is in the data's frame).
+        `return_weights` appends `node_weights(picks)` last (a bank with node_weights="measure" only)."""
+        if return_weights and self._weights_kind is None:
+            raise ValueError('TrajectoryBank.batch: return_weights needs a bank built with node_weights="measure"')
         horizon = self.horizon if horizon is None else int(horizon)
         if horizon < 1:
             raise ValueError(f"horizon must be >= 1, got {horizon}")
@@ -418,6 +449,8 @@ class TrajectoryBank:
         else:
             out = self._meshes.assemble([self._trajs[si].entry for si, _ in picks], node_in, node_tar, node_mask)
         extra = ([later] if later is not None else []) + ([noise] if return_noise else []) + ([xf] if return_transforms else [])
+        if return_weights:
+            extra.append(self.node_weights(picks))
         return (out, *extra) if extra else out
 
     def next_picks(self, B):

@@ -127,14 +127,14 @@ def global_masked_rmse(pred, tar, mask, group=None):
     return torch.sqrt(s / m / se.shape[-1])
 
 
-def global_masked_loss(pred, tar, mask, objective, std, group=None):
+def global_masked_loss(pred, tar, mask, objective, std, group=None, node_weights=None):
     """objective.masked_loss under data parallelism: the 1 + C fp64 sums (M, SE_c) are all-reduced, the value is identical on all
     ranks and the gradient flows through the local part only, as in global_masked_rmse (which the default objective is)."""
     from .objective import channel_sums, finish_loss
     if objective is None or objective.is_default:
         return global_masked_rmse(pred, tar, mask, group)
     objective.bind(pred.shape[-1])
-    M, SE = channel_sums(pred, tar, mask)
+    M, SE = channel_sums(pred, tar, mask, objective.check_node_weights(node_weights))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
         tot = torch.cat([M.detach().reshape(1), SE.detach()])
         dist.all_reduce(tot, op=dist.ReduceOp.SUM, group=group)
@@ -203,11 +203,14 @@ class DataParallel:
     def __call__(self, *a, **k):
         return self.model(*a, **k)
 
-    def step_loss_backward(self, data, consistent_mesh=True, later_targets=None):
+    def step_loss_backward(self, data, consistent_mesh=True, later_targets=None, node_weights=None):
         """One fwd + exact global loss + bwd + gradient reduction.  Returns the (global) loss.  `later_targets`: the targets
-        of steps 1 .. unroll-1 of an unrolled loss (step.FusedStep.__call__)."""
+        of steps 1 .. unroll-1 of an unrolled loss (step.FusedStep.__call__).  `node_weights`: this rank's node weights for an
+        objective with `node_weighted`: required with it, refused without."""
+        node_weights = self.objective.check_node_weights(node_weights)
         if self.fused is not None:
-            return self.fused(data, consistent_mesh) if later_targets is None else self.fused(data, consistent_mesh, later_targets)
+            kw = {} if node_weights is None else dict(node_weights=node_weights)
+            return self.fused(data, consistent_mesh, **kw) if later_targets is None else self.fused(data, consistent_mesh, later_targets, **kw)
         if later_targets is not None:
             raise ValueError("DataParallel: later_targets need the fused step")
         self.grads.zero()
@@ -217,7 +220,10 @@ class DataParallel:
         if self.objective.is_default:
             loss = global_masked_rmse(pred, tar, mask, self.group)
         else:
-            loss = global_masked_loss(pred, tar, mask, self.objective, self.model._targetNormalizer.std_with_epsilon(), self.group)
+            if node_weights is not None:
+                node_weights = node_weights.to(pred.device)
+            loss = global_masked_loss(pred, tar, mask, self.objective, self.model._targetNormalizer.std_with_epsilon(), self.group,
+                                      node_weights=node_weights)
         loss.backward()
         self.grads.finish()
         return loss

@@ -142,3 +142,56 @@ class BistrideMultiLayerGraph:
         """(m_gs, m_flat_es, m_ids) like the reference; `m_gs` here is the same list as `m_flat_es`
         (the reference returns its Graph wrappers there, which no caller on this path uses)."""
         return self.m_flat_es, self.m_flat_es, self.m_ids
+
+
+_CELL_DIM = {"line": 1, "flat": 1, "tri": 2, "quad": 2, "tetra": 3}
+
+
+def _tri_area(a, b):
+    """Area of the triangles spanned by the edge vectors a, b [n, p] (p = 2: the scalar cross product; p = 3: the norm of the cross product)."""
+    if a.shape[1] == 2:
+        return 0.5 * np.abs(a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0])
+    return 0.5 * np.linalg.norm(np.cross(a, b), axis=1)
+
+
+def lumped_node_measure64(pos, cells, mesh_type):
+    """`lumped_node_measure` before its rounding to float32: fp64 [N]."""
+    pos = np.asarray(pos, dtype=np.float64)
+    cells = np.asarray(cells)
+    if mesh_type not in _CELL_DIM:
+        raise ValueError(f"Unsupported mesh type {mesh_type} in lumped_node_measure.")
+    if pos.ndim != 2 or pos.shape[1] < _CELL_DIM[mesh_type] or pos.shape[1] > 3:
+        raise ValueError(f"lumped_node_measure: positions of shape {pos.shape} cannot hold {mesh_type!r} cells")
+    if mesh_type in ("line", "flat"):                 # [2, E] end points, as to_flat_edge reads them: every listed segment counts once
+        cells = cells.T
+    cells = cells.astype(np.int64)
+    corners = {"line": 2, "flat": 2, "tri": 3, "quad": 4, "tetra": 4}[mesh_type]
+    if cells.ndim != 2 or cells.shape[1] != corners:
+        raise ValueError(f"lumped_node_measure: {mesh_type!r} cells must have {corners} nodes each, got an array of shape {cells.shape}")
+    if cells.size and (cells.min() < 0 or cells.max() >= pos.shape[0]):
+        raise ValueError(f"lumped_node_measure: a cell names node {int(cells.max())} (or a negative one) of a mesh of {pos.shape[0]}")
+    x = pos[cells]                                    # [n_cells, corners, p]
+    if corners == 2:
+        size = np.linalg.norm(x[:, 1] - x[:, 0], axis=1)
+    elif mesh_type == "tri":
+        size = _tri_area(x[:, 1] - x[:, 0], x[:, 2] - x[:, 0])
+    elif mesh_type == "quad":                         # the two triangles on the diagonal 0-2
+        size = _tri_area(x[:, 1] - x[:, 0], x[:, 2] - x[:, 0]) + _tri_area(x[:, 2] - x[:, 0], x[:, 3] - x[:, 0])
+    else:
+        if pos.shape[1] != 3:
+            raise ValueError(f"lumped_node_measure: tetrahedra need 3-D positions, got {pos.shape[1]}-D")
+        size = np.abs(np.linalg.det(np.stack([x[:, 1] - x[:, 0], x[:, 2] - x[:, 0], x[:, 3] - x[:, 0]], axis=1))) / 6.0
+    out = np.zeros(pos.shape[0], dtype=np.float64)
+    share = size / corners
+    for k in range(corners):                          # np.add.at: cells in index order, so the sum at a node is reproducible
+        np.add.at(out, cells[:, k], share)
+    return out
+
+
+def lumped_node_measure(pos, cells, mesh_type):
+    """The measure every node of a mesh stands for, float32 [N]: each cell's length (line), area (tri; quad as two triangles) or
+    volume (tetra) is split equally among its nodes -- the lumped mass matrix of the discrete L2 norm.  Host NumPy
+    in fp64, rounded once; runs once per mesh.  `pos` [N, p]; `cells` as `to_flat_edge` takes them for the same `mesh_type`, and the
+    same types are accepted ("line" and "flat" are [2, E] end points: every LISTED segment counts, so an edge list that names both
+    directions gives twice the length everywhere -- a uniform factor, which no weighted loss sees)."""
+    return lumped_node_measure64(pos, cells, mesh_type).astype(np.float32)

@@ -9,7 +9,11 @@ channel weights (default 1):
     loss = Q  (kind = "mse")   or   sqrt(Q)  (kind = "rmse")
 
 `Objective()` -- physical, rmse, no weights -- is the reference's loss (trainer/trainer.py:96-97) and stays on the kernels it
-always ran on; everything else goes through bsms_error_sums + bsms_sim_objective_bwd (step.FusedStep) or `masked_loss` (autograd)."""
+always ran on; everything else goes through bsms_error_sums + bsms_sim_objective_bwd (step.FusedStep) or `masked_loss` (autograd).
+
+`node_weighted=True`: every node carries a weight omega >= 0 -- the measure it represents (`lumped_node_measure`), or
+any other importance -- and mu = m * omega takes the mask's place in M and SE_c: the discrete L2 norm of the error field instead of a
+mean over the mesher's points.  The weights come with every batch (`node_weights=`); the step runs the `_w` entries of the two kernels."""
 import math
 
 import torch
@@ -19,12 +23,12 @@ KINDS = {"rmse": 0, "mse": 1}                  # BSMS_LOSS_RMSE / BSMS_LOSS_MSE
 
 
 class Objective:
-    """A value: `space`, `kind`, `channel_weights` (a tuple of floats or None).  Validated here; the number of weights is checked
-    against a model's `out_dim` by `bind`."""
+    """A value: `space`, `kind`, `channel_weights` (a tuple of floats or None), `node_weighted` (bool).  Validated here; the number
+    of weights is checked against a model's `out_dim` by `bind`."""
 
-    __slots__ = ("space", "kind", "channel_weights")
+    __slots__ = ("space", "kind", "channel_weights", "node_weighted")
 
-    def __init__(self, space="physical", kind="rmse", channel_weights=None):
+    def __init__(self, space="physical", kind="rmse", channel_weights=None, node_weighted=False):
         if space not in SPACES:
             raise ValueError(f"Objective: space must be one of {sorted(SPACES)}, got {space!r}")
         if kind not in KINDS:
@@ -43,14 +47,17 @@ class Objective:
         object.__setattr__(self, "space", space)
         object.__setattr__(self, "kind", kind)
         object.__setattr__(self, "channel_weights", channel_weights)
+        if not isinstance(node_weighted, bool):
+            raise ValueError(f"Objective: node_weighted is a bool, got {node_weighted!r}")
+        object.__setattr__(self, "node_weighted", node_weighted)
 
     def __setattr__(self, name, value):
         raise AttributeError("Objective is immutable")
 
     @property
     def is_default(self):
-        """True exactly for physical / rmse / no weights: the reference's loss, on the default route."""
-        return self.space == "physical" and self.kind == "rmse" and self.channel_weights is None
+        """True exactly for physical / rmse / no weights of either kind: the reference's loss, on the default route."""
+        return self.space == "physical" and self.kind == "rmse" and self.channel_weights is None and not self.node_weighted
 
     def bind(self, out_dim):
         """Check the objective against a model with `out_dim` output channels; returns self."""
@@ -60,10 +67,12 @@ class Objective:
 
     @classmethod
     def from_cfg(cls, cfg):
-        """From the optional `loss_space`, `loss_kind`, `loss_channel_weights` of a model config; absent keys give the default."""
+        """From the optional `loss_space`, `loss_kind`, `loss_channel_weights`, `loss_node_weights` of a model config; absent keys
+        give the default."""
         w = getattr(cfg, "loss_channel_weights", None)
+        nw = getattr(cfg, "loss_node_weights", None)
         return cls(getattr(cfg, "loss_space", None) or "physical", getattr(cfg, "loss_kind", None) or "rmse",
-                   None if w is None else list(w))
+                   None if w is None else list(w), False if nw is None else nw)
 
     def weights_tensor(self, device):
         """fp64 [C] on `device`, or None for unit weights."""
@@ -78,22 +87,49 @@ class Objective:
             a = a / std.to(device=device, dtype=torch.float64).reshape(-1) ** 2
         return a
 
+    def _key(self):
+        return (self.space, self.kind, self.channel_weights, self.node_weighted)
+
     def __eq__(self, other):
-        return isinstance(other, Objective) and (self.space, self.kind, self.channel_weights) == (other.space, other.kind, other.channel_weights)
+        return isinstance(other, Objective) and self._key() == other._key()
 
     def __hash__(self):
-        return hash((self.space, self.kind, self.channel_weights))
+        return hash(self._key())
 
     def __repr__(self):
-        return f"Objective(space={self.space!r}, kind={self.kind!r}, channel_weights={self.channel_weights})"
+        tail = ", node_weighted=True" if self.node_weighted else ""
+        return f"Objective(space={self.space!r}, kind={self.kind!r}, channel_weights={self.channel_weights}{tail})"
+
+    def check_node_weights(self, node_weights):
+        """The pairing rule of every interface that takes `node_weights=`: a node-weighted objective needs them, any other refuses
+        them (ValueError); then `validate_node_weights`.  Returns the weights (or None)."""
+        if self.node_weighted and node_weights is None:
+            raise ValueError("Objective: node_weighted is set but no node_weights were given")
+        if node_weights is not None and not self.node_weighted:
+            raise ValueError("Objective: node_weights were given to an objective without node_weighted=True")
+        return None if node_weights is None else validate_node_weights(node_weights)
 
 
-def channel_sums(pred, tar, mask):
+def validate_node_weights(w):
+    """Node weights are a float32 tensor, finite and >= 0.  The values are looked at where the tensor lives on the host; a device
+    tensor is never read back (what it holds shows in the sums)."""
+    if not torch.is_tensor(w) or w.dtype != torch.float32:
+        raise ValueError(f"node_weights must be a float32 tensor, got {w.dtype if torch.is_tensor(w) else type(w).__name__}")
+    if not w.is_cuda and w.numel() and not bool((torch.isfinite(w) & (w >= 0)).all()):
+        raise ValueError("node_weights must be finite and >= 0")
+    return w
+
+
+def channel_sums(pred, tar, mask, node_weights=None):
     """(M, SE[C]) in fp64 from fp32 tensors [..., C] and a mask broadcastable to [..., 1]: d is rounded to fp32 once, products and
-    sums are fp64 -- the M and SE fields of bsms_error_sums, differentiable in `pred`."""
+    sums are fp64 -- the M and SE fields of bsms_error_sums, differentiable in `pred`.  `node_weights` (broadcastable to [..., 1]):
+    mu = double(mask) * double(weight) takes the mask's place -- the fields of bsms_error_sums_w."""
     C = pred.shape[-1]
     d = (pred - tar).double()
     m = mask.double().reshape(*pred.shape[:-1], 1)
+    if node_weights is not None:
+        w = node_weights.double()
+        m = m * (w.reshape(*w.shape, 1) if w.dim() < pred.dim() else w)     # [N] / [B, N] / [..., 1] against [..., 1]
     return m.sum(), (m * d * d).reshape(-1, C).sum(0)
 
 
@@ -105,12 +141,17 @@ def finish_loss(M, SE, objective, std):
     return (Q if objective.kind == "mse" else torch.sqrt(Q)).float(), terms
 
 
-def masked_loss(pred, tar, mask, objective=None, std=None):
+def masked_loss(pred, tar, mask, objective=None, std=None, node_weights=None):
     """The objective in torch.  `std`: the target normaliser's `std_with_epsilon()` (needed for space = "normalized").  The default
-    objective is `model.masked_rmse`, bit for bit."""
+    objective is `model.masked_rmse`, bit for bit.  `node_weights`: required by a node-weighted objective, refused by any other."""
+    if objective is None:
+        if node_weights is not None:
+            raise ValueError("masked_loss: node_weights need an Objective(node_weighted=True)")
+    else:
+        node_weights = objective.check_node_weights(node_weights)
     if objective is None or objective.is_default:
         from .model import masked_rmse
         return masked_rmse(pred, tar, mask)
     objective.bind(pred.shape[-1])
-    M, SE = channel_sums(pred, tar, mask)
+    M, SE = channel_sums(pred, tar, mask, node_weights)
     return finish_loss(M, SE, objective, std)[0]

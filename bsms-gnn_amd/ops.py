@@ -120,12 +120,14 @@ def _segment_view(t, what, S, seg_rows, width, stride):
     return t, stride
 
 
-def error_sums(pred, target, mask, seg_rows, *, pred_stride=None, target_stride=None, mask_stride=None):
+def error_sums(pred, target, mask, seg_rows, *, pred_stride=None, target_stride=None, mask_stride=None, weights=None):
     """Masked error sums of S segments of `seg_rows` rows (bsms_error_sums): fp64 [S, 1+3C] = [M | SE | AE | TT] per segment,
     d = fl32(pred - target).  `pred` is [S, seg_rows, C] (or contiguous [S * seg_rows, C]); `target` and `mask` hold the same
     segments, or ONE segment shared by all.  Segments may be views any whole number of rows apart -- a column block of a wider
     tensor, a stride-0 expand -- and the `*_stride` arguments (in rows) override what the views say.  One launch pair on the
-    current stream; nothing is copied and nothing synchronises."""
+    current stream; nothing is copied and nothing synchronises.
+    `weights` (float32, [seg_rows] shared by the segments or [S, seg_rows]): bsms_error_sums_w -- mask * weight takes the mask's
+    place in every sum.  None makes the unweighted call."""
     C, seg_rows = int(pred.shape[-1]), int(seg_rows)
     if seg_rows < 0:
         raise ValueError(f"error_sums: seg_rows = {seg_rows}")
@@ -141,6 +143,13 @@ def error_sums(pred, target, mask, seg_rows, *, pred_stride=None, target_stride=
     L = _abi.lib()
     sums = torch.empty(S, 1 + 3 * C, device=pred.device, dtype=torch.float64)
     work = _workspace(pred.device, L.bsms_error_sums_work_bytes(S, seg_rows))
+    if weights is not None:                              # bsms_error_sums_w: [seg_rows] shared by the segments, or [S, seg_rows]
+        if tuple(weights.shape) not in ((seg_rows,), (S, seg_rows)) or not weights.is_contiguous():
+            raise ValueError(f"error_sums: weights of shape {tuple(weights.shape)} are neither [{seg_rows}] nor [{S}, {seg_rows}] (contiguous)")
+        weights, ws = _segment_view(weights, "weights", S, seg_rows, 1, 0 if weights.dim() == 1 else seg_rows)
+        _abi.check(L.bsms_error_sums_w(pred.data_ptr(), target.data_ptr(), mask.data_ptr(), weights.data_ptr(), S, seg_rows, C, ps, ts, ms,
+                                       ws, sums.data_ptr(), work.data_ptr(), _stream()), "bsms_error_sums_w")
+        return sums
     _abi.check(L.bsms_error_sums(pred.data_ptr(), target.data_ptr(), mask.data_ptr(), S, seg_rows, C, ps, ts, ms, sums.data_ptr(),
                                  work.data_ptr(), _stream()), "bsms_error_sums")
     return sums

@@ -107,7 +107,8 @@ class FusedStep:
         gradient of the loss over all samples of the cycle so far (`reduction="batch"`), or the mean of the micro-batch gradients
         (`reduction="mean"`, what `(loss / M).backward()` gives); `ready` after the M-th, and the next call starts a new cycle.
         `objective` (objective.Objective): None or the default objective keeps the reference's masked RMSE on the kernels it
-        always ran on; any other runs bsms_error_sums after every forward and bsms_sim_objective_bwd in front of every backward.
+        always ran on; any other runs bsms_error_sums after every forward and bsms_sim_objective_bwd in front of every backward --
+        their `_w` entries with `objective.node_weighted`, which takes `node_weights=` with every call.
         `input_grad`: every backward also forms the gradient of the (K-step) loss w.r.t. `node_in` -- state, mesh
         positions and node type -- into a static [B, N, C+p+1] buffer, handed out by `input_grad()`.  Off: nothing changes.
         `param_grad=False` (with `input_grad=True`): the backward is data-only whatever `requires_grad` says -- no weight gradient is
@@ -307,6 +308,8 @@ class FusedStep:
                      work_obj=u8("work_obj", L.bsms_error_sums_work_bytes(1, R)))
             if self._obj_w is None or self._obj_w.device != dev:
                 self._obj_w = self._obj.weights_tensor(dev)
+            if self._obj.node_weighted:               # the step's own copy of the node weights, one per row
+                b["nw"] = f("nw", R)
         if self._input_grad:                          # shared by the K steps: every launch that touches them is on the caller's stream
             b["ig"] = dict(g_pos=f("g_pos", R, p), grad_in=f("grad_in", B, N, C + p + 1), g_pred=f("g_pred@0", R, C), g_nin=f("g_nin", R, C + 1),
                            pos_work=u8("pos_work", L.bsms_bsgmp_pos_work_bytes(pl, depth, B, p)))
@@ -373,6 +376,21 @@ class FusedStep:
             n *= int(d)
         return self._arena.bytes(name, 8 * n, dev).view(torch.float64).view(*shape)
 
+    def _set_node_weights(self, b, w, B, N):
+        """Copy this call's node weights into the step's own buffer of R floats: [N] is tiled over the B samples, [B, N]
+        and the flat [R] of a block-diagonal batch give a weight per row.  Both kernels then read a weight per row, whatever shape came
+        in.  The buffer is a view of the arena like every other, so a captured graph that reads it replays with whatever the copy in
+        front of the replay put there."""
+        if w is None:
+            return
+        R, shape = B * N, tuple(w.shape)
+        if shape not in ((N,), (B, N), (R,)):
+            raise ValueError(f"FusedStep: node_weights must be [N] = {(N,)}, [B, N] = {(B, N)} or flat [R] = {(R,)}, got {shape}")
+        if w.is_cuda and w.device != b["nw"].device:
+            raise RuntimeError(f"node_weights is on {w.device}, the batch on {b['nw'].device}")
+        n = w.numel()
+        b["nw"].view(-1, n).copy_(w.reshape(1, n).expand(R // n, n), non_blocking=True)
+
     def _loss_sums(self, b):
         """What data parallelism all-reduces (SUM) between the forwards and the backwards: the fp32 pairs of the default route, or
         the fp64 rows of bsms_error_sums (one contiguous message; the backward reads the 1 + C leading doubles of each row)."""
@@ -412,6 +430,10 @@ class FusedStep:
         ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), None, R, C, p,
                                no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["pred"].data_ptr(),
                                _ptr(next_in), _ptr(ic), None, work.data_ptr(), s), "bsms_sim_epilogue")
+        if self._obj.node_weighted:           # mu = mask * weight in the mask's place; the row [M | SE] downstream is none the wiser
+            ck(L.bsms_error_sums_w(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), b["nw"].data_ptr(), 1, R, C, R, R, R, R,
+                                   b["osums"].data_ptr(), b["work_obj"].data_ptr(), s), "bsms_error_sums_w")
+            return
         ck(L.bsms_error_sums(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), 1, R, C, R, R, R, b["osums"].data_ptr(),
                              b["work_obj"].data_ptr(), s), "bsms_error_sums")
 
@@ -434,12 +456,15 @@ class FusedStep:
             from .objective import KINDS, SPACES
             ni, o = m._inputNormalizer, self._obj
             c = chain or dict(w=1.0, g_pred_next=None, g_nin_next=None, g_pred=None)
-            ck(L.bsms_sim_objective_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), R, C, no._E_data.data_ptr(),
-                                        no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), ni._E_data.data_ptr(),
-                                        ni._E_data_squared.data_ptr(), ni.std_eps.data_ptr(), b["osums"].data_ptr(), _ptr(self._obj_w),
-                                        SPACES[o.space], KINDS[o.kind], c["w"], _ptr(c["g_pred_next"]), _ptr(c["g_nin_next"]),
-                                        b["loss"].data_ptr(), b["chan"].data_ptr(), _ptr(c["g_pred"]), b["g_np"].data_ptr(), s),
-               "bsms_sim_objective_bwd")
+            head = (b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr())
+            tail = (R, C, no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), ni._E_data.data_ptr(),
+                    ni._E_data_squared.data_ptr(), ni.std_eps.data_ptr(), b["osums"].data_ptr(), _ptr(self._obj_w), SPACES[o.space],
+                    KINDS[o.kind], c["w"], _ptr(c["g_pred_next"]), _ptr(c["g_nin_next"]), b["loss"].data_ptr(), b["chan"].data_ptr(),
+                    _ptr(c["g_pred"]), b["g_np"].data_ptr(), s)
+            if o.node_weighted:                       # the same call with the step's weights behind the mask: one per row, period R
+                ck(L.bsms_sim_objective_bwd_w(*head, b["nw"].data_ptr(), R, *tail), "bsms_sim_objective_bwd_w")
+            else:
+                ck(L.bsms_sim_objective_bwd(*head, *tail), "bsms_sim_objective_bwd")
         elif chain is None:
             ck(L.bsms_sim_loss_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), R, C, no._E_data.data_ptr(),
                                    no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["sums"].data_ptr(), b["loss"].data_ptr(),
@@ -478,9 +503,12 @@ class FusedStep:
         ck(L.bsms_side_lanes_join(s), "bsms_side_lanes_join")
 
     # ------------------------------------------------------------------------------------------------ the step
-    def __call__(self, data, consistent=True, later_targets=None):
+    def __call__(self, data, consistent=True, later_targets=None, node_weights=None):
         """`later_targets` (unroll = K > 1 only): the targets of steps 1 .. K-1, [K-1, B, N, C] for consistent meshes and
-        [K-1, rows, C] for variable meshes (frames t+2 .. t+K; TrajectoryBank(horizon=K) hands them out)."""
+        [K-1, rows, C] for variable meshes (frames t+2 .. t+K; TrajectoryBank(horizon=K) hands them out).
+        `node_weights`: float32 [N] (shared by the batch), [B, N], or flat [rows] for variable meshes; required by an
+        objective with `node_weighted`, refused by any other.  They are copied into a buffer the step owns; all K steps read it."""
+        node_weights = self.objective.check_node_weights(node_weights)
         node_in, tar, mask, m_gs, m_ids = self._unpack(data, consistent)
         if (self.unroll > 1) != (later_targets is not None):
             raise ValueError(f"FusedStep: unroll = {self.unroll} " + ("needs later_targets" if self.unroll > 1 else "takes no later_targets"))
@@ -491,6 +519,7 @@ class FusedStep:
         plans = [*plans, bottom]
         self._pointer_tables()
         b = self._buffers(B, N, plans, node_in.device)
+        self._set_node_weights(b, node_weights, B, N)
         self._decide_packs()
         world = self._world()
         if self.accumulate > 1:
@@ -876,7 +905,7 @@ def _input_gradient_key(K, step_weights, detach, objective, param_grad, recomput
 
 
 def input_gradient(model, data, consistent=True, later_targets=None, step_weights=None, detach=False, objective=None, param_grad=True,
-                   recompute=False):
+                   recompute=False, node_weights=None):
     """Sensitivity of a (rollout) objective of a trained `BSMS_Simulator`: returns `(loss, grad_node_in)`, the weighted K-step loss
     and its gradient w.r.t. `node_in` -- initial state, mesh positions, node type; [B, N, C+p+1], or [1, rows, C+p+1] for variable
     meshes.  K = 1 without `later_targets`, else `later_targets.shape[0] + 1`; `step_weights`, `detach` and
@@ -893,7 +922,9 @@ def input_gradient(model, data, consistent=True, later_targets=None, step_weight
     fp32 precision only.
 
     `recompute=True`: FusedStep's -- the adjoint through a long rollout holds the blocks' inputs per step instead of
-    their activations; loss and gradient keep their bits."""
+    their activations; loss and gradient keep their bits.
+
+    `node_weights`: FusedStep's, for an `objective` with `node_weighted`."""
     from .dp import GradBuckets
     from .objective import Objective
     K = 1 if later_targets is None else int(later_targets.shape[0]) + 1
@@ -908,5 +939,5 @@ def input_gradient(model, data, consistent=True, later_targets=None, step_weight
             cache["grads"] = GradBuckets(list(model.parameters()))
         step = cache[key] = FusedStep(model, cache["grads"] if param_grad else None, unroll=K, step_weights=step_weights, detach=detach,
                                       objective=objective, input_grad=True, param_grad=bool(param_grad), recompute=recompute)
-    loss = step(data, consistent, later_targets)
+    loss = step(data, consistent, later_targets, node_weights=node_weights)
     return loss, step.input_grad().clone()

@@ -337,6 +337,8 @@ class Trainer:
     autoregressive steps (step.FusedStep); `iter` then takes `(batch, later_targets)`, what TrajectoryBank(horizon=K) hands out;
     loss_space ("physical" / "normalized"), loss_kind ("rmse" / "mse"), loss_channel_weights -- the training objective
     (objective.Objective; absent: the reference's masked RMSE in physical units), which `iter` trains on and `get_loss` reports;
+    loss_node_weights (absent or false: off) -- the objective weights every node by what `iter(data, node_weights=)` and
+    `get_loss(data, node_weights=)` are given, e.g. the lumped measure; `get_error` and the rollout statistics stay unweighted;
     recompute_activations (absent or false: off) -- the fused step holds the U-Net blocks' inputs instead of their
     activations and recomputes in the backward: the same parameters after every step, bit for bit, less memory per unrolled step.
     Optional in `opt_cfg`: gradient_accumulation_steps = M (absent or 1: every `iter` is an optimizer step) and
@@ -434,13 +436,17 @@ class Trainer:
         """`ema=True` (here, in get_loss and in get_error): the averaged weights (`ema_model()`) instead of the live ones."""
         return self._model_forward(self.move_to_device(data), ema)
 
-    def get_loss(self, data, ema=False):
+    def get_loss(self, data, ema=False, node_weights=None):
+        """The training objective on `data` (autograd).  `node_weights`: as `iter` takes them, with model_cfg.loss_node_weights."""
+        node_weights = self.objective.check_node_weights(node_weights)
+        if node_weights is not None:
+            node_weights = node_weights.to(self.device)
         data = self.move_to_device(data)
         pred = self._model_forward(data, ema)
         tar, mask = self.get_label_mask(data)
         from .objective import masked_loss                    # the default objective: model.masked_rmse, the reference's formula
         std = None if self.objective.space == "physical" else self.model._targetNormalizer.std_with_epsilon()
-        return masked_loss(pred, tar, mask, self.objective, std)
+        return masked_loss(pred, tar, mask, self.objective, std, node_weights=node_weights)
 
     def get_error(self, data, relative=True, ema=False):
         """trainer/trainer.py:231-271: (error_mean, error_std) per channel as float32 NumPy arrays [C] -- the masked absolute
@@ -462,13 +468,17 @@ class Trainer:
             out = torch.stack([mean, std]).float().cpu().numpy()
         return out[0], out[1]
 
-    def iter(self, data):
+    def iter(self, data, node_weights=None):
         """One training iteration (trainer.py:134-156): statistics only during warm-up, otherwise
         fwd + loss + bwd (+ gradient all-reduce) + clip + AdamW + LR schedule.  With model_cfg.unroll_steps = K > 1 `data` is
         `(batch, later_targets)`; the warm-up iterations look at the batch only.  With opt_cfg.skip_nonfinite a step whose
         gradient norm is inf / NaN changes nothing on the device (FusedAdamW.skipped_steps() counts it); the non-finite loss is
         returned as ever and the LR schedule still advances -- what torch does around a skipped GradScaler step -- because
-        the host does not read the decision back."""
+        the host does not read the decision back.
+        `node_weights` (model_cfg.loss_node_weights): the batch's node weights -- [N], [B, N] or flat [rows], what
+        `TrajectoryBank(node_weights="measure").node_weights(picks)` hands out; required with the key, refused without it.  The warm-up
+        iterations check and then ignore them: they form no loss."""
+        node_weights = self.objective.check_node_weights(node_weights)
         later = None
         if self.unroll > 1:
             if not (isinstance(data, (tuple, list)) and len(data) == 2 and torch.is_tensor(data[1]) and not torch.is_tensor(data[0])):
@@ -482,7 +492,7 @@ class Trainer:
             if not self._synced:                                  # merge normaliser statistics once (dp.py)
                 self.dp.sync_normalizers(self._norm_base)
                 self._synced, self._norm_base = True, None
-            loss = self.dp.step_loss_backward(data, self.model_cfg.consistent_mesh, later)
+            loss = self.dp.step_loss_backward(data, self.model_cfg.consistent_mesh, later, node_weights=node_weights)
             if self.accumulate == 1 or self.dp.fused.ready:       # a micro-batch inside a cycle changes no parameter
                 if self.accumulate > 1:
                     self.last_accumulated_loss = self.dp.fused.accumulated_loss()

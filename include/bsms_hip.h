@@ -481,6 +481,30 @@ int bsms_sim_objective_bwd(const float* pred, const float* target, const float* 
                            const float* g_pred_next /* nullable */, const float* g_norm_in_next /* nullable */,
                            float* loss_out /* nullable */, float* chan_out /* nullable */, float* g_pred /* nullable */,
                            float* grad_norm_pred, bsms_stream_t stream);
+/* bsms_sim_objective_bwd for a NODE-WEIGHTED objective: every row carries a weight omega >= 0 (the measure its
+ * node represents, or any other importance) and mu = m * omega takes the mask's place in the LOSS -- not in the carry and not on the
+ * way out, which keep m: the mask also gates pred = state + delta * mask and the rollout rule, the weight does not.
+ *   row_weights     DEVICE float, `weight_period` entries; row r reads row_weights[r % weight_period].  weight_period must divide R:
+ *                   R gives a weight per row, N shares one mesh's weights between the B = R / N samples of a batch.
+ *   sums            = [ M | SE[0..C) ] with M = sum mu, SE[c] = sum mu d_c^2: the leading fields of a row of bsms_error_sums_w
+ *   a_c, Q, loss, chan_out, G    as bsms_sim_objective_bwd forms them, from the weighted sums
+ *   g_pred_k        = w * ((d * fl32(m * omega)) * fl32(G a_c)) + carry_k
+ *   grad_norm_pred  = float(double(g_pred_k * mask) * std_c)
+ * ORDER of the fp32 operations: mu = m * omega first (one rounding; exact for a 0/1 mask), then d * mu, then * fl32(G a_c), then
+ * * w, then + carry.  With omega == 1 mu IS m and every later operation is bsms_sim_objective_bwd's: unit weights reproduce that
+ * entry bit for bit.  omega -> 2^k omega scales the sums, and so 1 / G, by 2^k exactly: loss_out, chan_out, g_pred and
+ * grad_norm_pred keep their bits (short of overflow and of subnormals).
+ * Everything else -- the carried pair, in_*, the unguarded M == 0 -- is that entry's, and so is the order of the checks: R >= 1 and C
+ * in 1..8, then space and kind (BSMS_E_UNSUPPORTED, before any pointer is looked at); then null required pointers, `row_weights`
+ * among them, then a weight_period that is < 1 or does not divide R, then half a carried pair (BSMS_E_INVALID_ARG); all before
+ * any device call.  One launch; no atomics, no allocation, no synchronisation, nothing read back: capturable. */
+int bsms_sim_objective_bwd_w(const float* pred, const float* target, const float* mask, const float* row_weights,
+                             int64_t weight_period, int64_t R, int64_t C, const double* mean, const double* meansq,
+                             const double* std_eps, const double* in_mean /* nullable */, const double* in_meansq /* nullable */,
+                             const double* in_std_eps /* nullable */, const double* sums, const double* channel_weights /* nullable */,
+                             int space, int kind, float w, const float* g_pred_next /* nullable */,
+                             const float* g_norm_in_next /* nullable */, float* loss_out /* nullable */, float* chan_out /* nullable */,
+                             float* g_pred /* nullable */, float* grad_norm_pred, bsms_stream_t stream);
 /* The gradient of the K-step objective w.r.t. its INPUT, G = dJ / d in_0: one launch folds step k into
  * `grad_in` [R, C+p+1], which has the column layout of node_in = [state (C) | mesh_pos (p) | node_type].  in_0 reaches step k
  * through its positions and node type on every row, through its state on every row at k = 0, and at k > 0 through its state
@@ -529,6 +553,18 @@ size_t bsms_error_sums_work_bytes(int64_t S, int64_t seg_rows);
 int bsms_error_sums(const float* pred, const float* target, const float* mask, int64_t S, int64_t seg_rows, int64_t C,
                     int64_t pred_stride, int64_t target_stride, int64_t mask_stride, double* sums, void* work,
                     bsms_stream_t stream);
+/* bsms_error_sums with a weight per row: mu = double(mask) * double(omega) takes the mask's place in every sum,
+ *     M = sum mu    SE[c] = sum mu * d_c^2    AE[c] = sum mu * |d_c|    TT[c] = sum mu * target_c^2
+ * Segment s reads row_weights + s * weight_stride ([seg_rows] floats; weight_stride counts rows like mask_stride, 0 shares one weight
+ * vector between all segments).  Everything else is bsms_error_sums': the one fp32 rounding of d, the pieces of 1024 rows and their
+ * fixed trees, the finishing kernel, the limits, the checks and their order (a null row_weights with work to do is one of the null
+ * pointers, a negative weight_stride one of the negative strides), `work` of bsms_error_sums_work_bytes(S, seg_rows) bytes; no
+ * atomics, no allocation, no synchronisation, capturable.  The kernels are one template: with omega == 1 the sums are those of
+ * bsms_error_sums bit for bit, with omega in {0, 1} those of bsms_error_sums under the mask m * omega.  The weights are not looked
+ * at: negative or non-finite ones show in the sums. */
+int bsms_error_sums_w(const float* pred, const float* target, const float* mask, const float* row_weights, int64_t S,
+                      int64_t seg_rows, int64_t C, int64_t pred_stride, int64_t target_stride, int64_t mask_stride,
+                      int64_t weight_stride, double* sums, void* work, bsms_stream_t stream);
 
 /* ---------------------------------------------------------------- batch assembly from resident trajectories ---
  * The level-0 node tensors of a batch (datasets/base.py:238-289, `proc_data`, plus the collate) built by ONE launch from
