@@ -98,12 +98,17 @@ SIGNATURES = {
     "bsms_sim_objective_bwd_w": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, C.c_float, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bsms_sim_robust_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, C.c_float, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsms_sim_input_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p,
                                     c_int, c_int, c_void_p, c_void_p]),
     "bsms_error_sums_work_bytes": (c_size_t, [c_i64, c_i64]),
     "bsms_error_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "bsms_error_sums_w": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p,
                                   c_void_p, c_void_p]),
+    "bsms_robust_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p]),
     "bsms_batch_assemble": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, C.c_double, c_void_p, c_i64, C.c_uint64, C.c_uint64,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsms_batch_targets": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p]),

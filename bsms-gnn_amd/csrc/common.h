@@ -99,6 +99,14 @@ int launch_dyn_lds(const char* what, const char* build, unsigned grid, unsigned 
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
+// std_with_epsilon() of a normaliser from its statistics, op for op (normalizer.py:40-52): sim.hip and errsum.hip, both compiled
+// with -ffp-contract=off
+__device__ __forceinline__ double std_eps(double mean, double meansq, double eps) {
+  double s = sqrt(meansq - mean * mean);       // torch: sqrt(E2 - mean ** 2); pow(x, 2) is x * x
+  if (isnan(s)) s = 0.0;                       // nan_to_num
+  else if (isinf(s)) s = s > 0 ? 1.7976931348623157e308 : -1.7976931348623157e308;
+  return s > eps ? s : eps;                    // torch.max(std, eps)
+}
 #endif
 inline int device_cu_count() {
   static int cus[kMaxDevices] = {};

@@ -17,13 +17,6 @@ namespace {
 
 constexpr int kMaxC = 8;   // state / target channels handled in registers
 
-__device__ __forceinline__ double std_eps(double mean, double meansq, double eps) {
-  double s = sqrt(meansq - mean * mean);       // torch: sqrt(E2 - mean ** 2); pow(x, 2) is x * x
-  if (isnan(s)) s = 0.0;                       // nan_to_num
-  else if (isinf(s)) s = s > 0 ? 1.7976931348623157e308 : -1.7976931348623157e308;
-  return s > eps ? s : eps;                    // torch.max(std, eps)
-}
-
 // node_in [R, C+p+1] = [state(C) | mesh_pos(p) | node_type(1)]  ->  norm_in [R, C+1] = normalised [state | type], pos [R,p]
 __global__ __launch_bounds__(256) void k_sim_prologue(const float* node_in, int64_t R, int C, int p, const double* mean,
                                                       const double* meansq, const double* eps, float* norm_in, float* pos) {
@@ -336,6 +329,60 @@ __device__ __forceinline__ void sim_objective_bwd_row(const float* pred, const f
   }
 }
 
+// sim_objective_bwd_row for the robust objectives (include/bsms_hip.h: bsms_sim_robust_bwd).  `sums` = [M | S[0..C)]
+// (bsms_robust_sums), loss = sum_c w_c S_c / (M C): linear in the sums, so the coefficient of a row is fl32(w_c / (M C s_c)) whatever
+// the sums hold, and only the loss-gradient term differs: psi(u) = sign(u) or clamp(u, -delta, delta) of u = double(d) / s_c takes
+// d's place.  The step weight, the carry and the way out through the de-normalisation are that function's lines, op for op.
+// `row_weights` == nullptr: mu IS m (no product), the kernel of an objective without node weights.
+__global__ __launch_bounds__(256) void k_sim_robust_bwd(const float* pred, const float* target, const float* mask,
+                                                        const float* row_weights, int64_t weight_period, int64_t R, int C,
+                                                        const double* mean, const double* meansq, const double* eps,
+                                                        const double* in_mean, const double* in_meansq, const double* in_eps,
+                                                        const double* sums, const double* weights, const double* delta,
+                                                        int normalized, int huber, float w, const float* g_pred_next,
+                                                        const float* g_norm_in_next, float* loss_out, float* chan_out, float* g_pred,
+                                                        float* grad_norm_pred) {
+  const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  const double e = *eps;
+  const double MC = sums[0] * double(C);
+  double sd[kMaxC], sc[kMaxC], dl[kMaxC];
+  float coef[kMaxC];
+  double loss = 0.0;
+  for (int c = 0; c < C; ++c) {
+    sd[c] = std_eps(mean[c], meansq[c], e);
+    sc[c] = normalized ? sd[c] : 1.0;
+    dl[c] = huber ? delta[c] : 0.0;
+    const double wc = weights ? weights[c] : 1.0;
+    const double term = wc * sums[1 + c] / MC;
+    if (r == 0 && chan_out) chan_out[c] = float(term);
+    loss += term;
+    coef[c] = float(wc / (MC * sc[c]));
+  }
+  if (r == 0 && loss_out) *loss_out = float(loss);
+  if (r >= R) return;
+  const float m = mask[r];
+  const float mu = row_weights ? m * row_weights[r % weight_period] : m;
+  const bool carried = g_pred_next != nullptr && m != 0.f;
+  const double ie = g_pred_next ? *in_eps : 0.0;
+  for (int c = 0; c < C; ++c) {
+    const double u = double(pred[r * C + c] - target[r * C + c]) / sc[c];
+    double psi = u;                                                     // |u| <= delta; u == 0 (sign(0) = 0); a NaN stays one
+    if (huber) psi = u > dl[c] ? dl[c] : (u < -dl[c] ? -dl[c] : u);
+    else if (u > 0.0) psi = 1.0;
+    else if (u < 0.0) psi = -1.0;
+    float gp = float(psi) * mu * coef[c];
+    gp = w * gp;
+    if (carried) {
+      const float through_norm = float(double(g_norm_in_next[r * (C + 1) + c]) / std_eps(in_mean[c], in_meansq[c], ie));
+      const float g_state = g_pred_next[r * C + c] + through_norm;
+      gp = gp + g_state;
+    }
+    if (g_pred) g_pred[r * C + c] = gp;
+    const float gd = gp * m;
+    grad_norm_pred[r * C + c] = float(double(gd) * sd[c]);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_sim_objective_bwd(const float* pred, const float* target, const float* mask, int64_t R,
                                                            int C, const double* mean, const double* meansq, const double* eps,
                                                            const double* in_mean, const double* in_meansq, const double* in_eps,
@@ -409,6 +456,36 @@ extern "C" int bsms_sim_objective_bwd_w(const float* pred, const float* target, 
                      row_weights, weight_period, R, (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums,
                      channel_weights, int(space == BSMS_LOSS_NORMALIZED), int(kind == BSMS_LOSS_RMSE), w, g_pred_next, g_norm_in_next,
                      loss_out, chan_out, g_pred, grad_norm_pred);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}
+
+// The robust objectives' backward (include/bsms_hip.h): the checks of bsms_sim_objective_bwd_w in its order, with `row_weights`
+// nullable (then weight_period is not looked at) and `delta` among the required pointers under BSMS_ROBUST_HUBER.
+extern "C" int bsms_sim_robust_bwd(const float* pred, const float* target, const float* mask, const float* row_weights,
+                                   int64_t weight_period, int64_t R, int64_t C, const double* mean, const double* meansq,
+                                   const double* std_eps_dev, const double* in_mean, const double* in_meansq,
+                                   const double* in_std_eps_dev, const double* sums, const double* channel_weights,
+                                   const double* delta, int space, int rkind, float w, const float* g_pred_next,
+                                   const float* g_norm_in_next, float* loss_out, float* chan_out, float* g_pred,
+                                   float* grad_norm_pred, bsms_stream_t stream) {
+  BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "sim_robust_bwd: R=%lld C=%lld", (long long)R, (long long)C);
+  BSMS_REQUIRE((space == BSMS_LOSS_PHYSICAL || space == BSMS_LOSS_NORMALIZED) && (rkind == BSMS_ROBUST_MAE || rkind == BSMS_ROBUST_HUBER),
+               BSMS_E_UNSUPPORTED, "sim_robust_bwd: space=%d rkind=%d (each 0 or 1)", space, rkind);
+  BSMS_REQUIRE(pred && target && mask && mean && meansq && std_eps_dev && sums && grad_norm_pred &&
+                   (delta || rkind != BSMS_ROBUST_HUBER),
+               BSMS_E_INVALID_ARG, "sim_robust_bwd: null argument");
+  BSMS_REQUIRE(!row_weights || (weight_period >= 1 && weight_period <= R && R % weight_period == 0), BSMS_E_INVALID_ARG,
+               "sim_robust_bwd: weight_period=%lld does not divide R=%lld", (long long)weight_period, (long long)R);
+  BSMS_REQUIRE((g_pred_next == nullptr) == (g_norm_in_next == nullptr), BSMS_E_INVALID_ARG,
+               "sim_robust_bwd: the carried pair (g_pred_next, g_norm_in_next) is given together or not at all");
+  BSMS_REQUIRE(!g_pred_next || (in_mean && in_meansq && in_std_eps_dev), BSMS_E_INVALID_ARG,
+               "sim_robust_bwd: a carried gradient needs the input normaliser's statistics");
+  BSMS_REQUIRE(!g_pred || (g_pred != g_pred_next), BSMS_E_INVALID_ARG, "sim_robust_bwd: g_pred aliases g_pred_next");
+  hipLaunchKernelGGL(k_sim_robust_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask,
+                     row_weights, row_weights ? weight_period : 1, R, (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq,
+                     in_std_eps_dev, sums, channel_weights, delta, int(space == BSMS_LOSS_NORMALIZED), int(rkind == BSMS_ROBUST_HUBER), w,
+                     g_pred_next, g_norm_in_next, loss_out, chan_out, g_pred, grad_norm_pred);
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }

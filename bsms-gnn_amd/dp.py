@@ -128,13 +128,16 @@ def global_masked_rmse(pred, tar, mask, group=None):
 
 
 def global_masked_loss(pred, tar, mask, objective, std, group=None, node_weights=None):
-    """objective.masked_loss under data parallelism: the 1 + C fp64 sums (M, SE_c) are all-reduced, the value is identical on all
+    """objective.masked_loss under data parallelism: the 1 + C fp64 sums (M, SE_c) -- (M, S_c) of a robust objective -- are all-reduced, the value is identical on all
     ranks and the gradient flows through the local part only, as in global_masked_rmse (which the default objective is)."""
-    from .objective import channel_sums, finish_loss
+    from .objective import channel_sums, finish_loss, robust_sums
     if objective is None or objective.is_default:
         return global_masked_rmse(pred, tar, mask, group)
     objective.bind(pred.shape[-1])
-    M, SE = channel_sums(pred, tar, mask, objective.check_node_weights(node_weights))
+    if objective.is_robust:                   # (M, S_c) in (M, SE_c)'s place: the loss is linear in them (DESIGN.md 4.20)
+        M, SE = robust_sums(pred, tar, mask, objective, std, objective.check_node_weights(node_weights))
+    else:
+        M, SE = channel_sums(pred, tar, mask, objective.check_node_weights(node_weights))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
         tot = torch.cat([M.detach().reshape(1), SE.detach()])
         dist.all_reduce(tot, op=dist.ReduceOp.SUM, group=group)
@@ -154,7 +157,7 @@ class DataParallel:
         fused step implements it.
         `unroll` > 1: the loss runs over that many autoregressive steps (step.FusedStep; `step_weights` default 1/unroll,
         `detach` cuts the gradient between the steps).  Only the fused step implements it.
-        `objective` (objective.Objective): None reads the optional loss_space / loss_kind / loss_channel_weights of `model.cfg`;
+        `objective` (objective.Objective): None reads the optional loss_space / loss_kind / loss_delta / loss_channel_weights of `model.cfg`;
         without them it is the reference's masked RMSE.
         `input_grad`: the fused step also forms the gradient of the loss w.r.t. `node_in` (`engine.fused.input_grad()`, DESIGN.md
         4.12) -- local to this rank's samples, no collective; only the fused step implements it.

@@ -13,26 +13,53 @@ always ran on; everything else goes through bsms_error_sums + bsms_sim_objective
 
 `node_weighted=True`: every node carries a weight omega >= 0 -- the measure it represents (`lumped_node_measure`), or
 any other importance -- and mu = m * omega takes the mask's place in M and SE_c: the discrete L2 norm of the error field instead of a
-mean over the mesher's points.  The weights come with every batch (`node_weights=`); the step runs the `_w` entries of the two kernels."""
+mean over the mesher's points.  The weights come with every batch (`node_weights=`); the step runs the `_w` entries of the two kernels.
+
+The ROBUST kinds replace the square by a function that grows linearly: with s_c = 1 ("physical") or std_c
+("normalized"), u_c = double(d_c) / s_c, mu = m or m * omega and S_c = sum mu rho(u_c) (fp64),
+
+    rho(u) = |u|                                                     kind = "mae"
+    rho(u) = u^2 / 2 if |u| <= delta_c, else delta_c (|u| - delta_c / 2)   kind = "huber"   (`delta` in the units of the space)
+    loss   = sum_c w_c S_c / (M C)                                   no square root, and no 1 / std^2 on top of s_c
+
+on bsms_robust_sums + bsms_sim_robust_bwd in the step."""
 import math
 
 import torch
 
 SPACES = {"physical": 0, "normalized": 1}      # BSMS_LOSS_PHYSICAL / BSMS_LOSS_NORMALIZED
 KINDS = {"rmse": 0, "mse": 1}                  # BSMS_LOSS_RMSE / BSMS_LOSS_MSE
+ROBUST_KINDS = {"mae": 0, "huber": 1}          # BSMS_ROBUST_MAE / BSMS_ROBUST_HUBER
 
 
 class Objective:
-    """A value: `space`, `kind`, `channel_weights` (a tuple of floats or None), `node_weighted` (bool).  Validated here; the number
-    of weights is checked against a model's `out_dim` by `bind`."""
+    """A value: `space`, `kind`, `channel_weights` (a tuple of floats or None), `node_weighted` (bool), `delta` (the Huber threshold:
+    a float, a tuple of one float per channel, or None).  Validated here; the number of weights and of thresholds is checked against
+    a model's `out_dim` by `bind`."""
 
-    __slots__ = ("space", "kind", "channel_weights", "node_weighted")
+    __slots__ = ("space", "kind", "channel_weights", "node_weighted", "delta")
 
-    def __init__(self, space="physical", kind="rmse", channel_weights=None, node_weighted=False):
+    def __init__(self, space="physical", kind="rmse", channel_weights=None, node_weighted=False, *, delta=None):
         if space not in SPACES:
             raise ValueError(f"Objective: space must be one of {sorted(SPACES)}, got {space!r}")
-        if kind not in KINDS:
-            raise ValueError(f"Objective: kind must be one of {sorted(KINDS)}, got {kind!r}")
+        if not isinstance(kind, str) or (kind not in KINDS and kind not in ROBUST_KINDS):
+            raise ValueError(f"Objective: kind must be one of {sorted(KINDS) + sorted(ROBUST_KINDS)}, got {kind!r}")
+        if kind == "huber":
+            if delta is None:
+                raise ValueError('Objective: kind="huber" needs delta (a positive float, or one per channel)')
+            if torch.is_tensor(delta):
+                delta = delta.detach().reshape(-1).tolist() if delta.dim() else float(delta)
+            try:
+                if isinstance(delta, (bool, str)):
+                    raise TypeError
+                delta = tuple(float(x) for x in delta) if hasattr(delta, "__iter__") else float(delta)
+            except (TypeError, ValueError):
+                raise ValueError(f"Objective: delta must be a number or a sequence of numbers, got {delta!r}") from None
+            each = (delta,) if isinstance(delta, float) else delta
+            if not each or not all(math.isfinite(x) and x > 0.0 for x in each):
+                raise ValueError(f"Objective: delta must be finite and > 0, got {delta}")
+        elif delta is not None:
+            raise ValueError(f'Objective: delta belongs to kind="huber", not to kind={kind!r}')
         if channel_weights is not None:
             if torch.is_tensor(channel_weights):
                 channel_weights = channel_weights.detach().reshape(-1).tolist()
@@ -50,6 +77,7 @@ class Objective:
         if not isinstance(node_weighted, bool):
             raise ValueError(f"Objective: node_weighted is a bool, got {node_weighted!r}")
         object.__setattr__(self, "node_weighted", node_weighted)
+        object.__setattr__(self, "delta", delta)
 
     def __setattr__(self, name, value):
         raise AttributeError("Objective is immutable")
@@ -59,36 +87,60 @@ class Objective:
         """True exactly for physical / rmse / no weights of either kind: the reference's loss, on the default route."""
         return self.space == "physical" and self.kind == "rmse" and self.channel_weights is None and not self.node_weighted
 
+    @property
+    def is_robust(self):
+        """True for the kinds that are linear in their per-channel sums ("mae", "huber"): the route of bsms_robust_sums."""
+        return self.kind in ROBUST_KINDS
+
     def bind(self, out_dim):
         """Check the objective against a model with `out_dim` output channels; returns self."""
         if self.channel_weights is not None and len(self.channel_weights) != int(out_dim):
             raise ValueError(f"Objective: {len(self.channel_weights)} channel_weights for a model with out_dim = {out_dim}")
+        if isinstance(self.delta, tuple) and len(self.delta) != int(out_dim):
+            raise ValueError(f"Objective: {len(self.delta)} values of delta for a model with out_dim = {out_dim}")
         return self
 
     @classmethod
     def from_cfg(cls, cfg):
-        """From the optional `loss_space`, `loss_kind`, `loss_channel_weights`, `loss_node_weights` of a model config; absent keys
-        give the default."""
+        """From the optional `loss_space`, `loss_kind`, `loss_channel_weights`, `loss_node_weights`, `loss_delta` of a model config;
+        absent keys give the default."""
         w = getattr(cfg, "loss_channel_weights", None)
         nw = getattr(cfg, "loss_node_weights", None)
+        dl = getattr(cfg, "loss_delta", None)
         return cls(getattr(cfg, "loss_space", None) or "physical", getattr(cfg, "loss_kind", None) or "rmse",
-                   None if w is None else list(w), False if nw is None else nw)
+                   None if w is None else list(w), False if nw is None else nw,
+                   delta=dl if dl is None or isinstance(dl, (int, float)) else list(dl))
 
     def weights_tensor(self, device):
         """fp64 [C] on `device`, or None for unit weights."""
         return None if self.channel_weights is None else torch.tensor(self.channel_weights, dtype=torch.float64, device=device)
 
+    def delta_tensor(self, C, device):
+        """fp64 [C] on `device` (a scalar delta repeated), or None for every kind but "huber"."""
+        if self.delta is None:
+            return None
+        each = (self.delta,) * int(C) if isinstance(self.delta, float) else self.delta
+        return torch.tensor(each, dtype=torch.float64, device=device)
+
+    def scales(self, std, C, device):
+        """s_c of the robust kinds, fp64 [C]: ones in the physical space, the target normaliser's std in the normalized one."""
+        if self.space == "physical":
+            return torch.ones(C, dtype=torch.float64, device=device)
+        if std is None:
+            raise ValueError("Objective: the normalized space needs the target normaliser's std_with_epsilon()")
+        return std.to(device=device, dtype=torch.float64).reshape(-1)
+
     def coefficients(self, std, C, device):
-        """a_c, fp64 [C]."""
+        """a_c, fp64 [C] (the robust kinds: w_c alone -- their scaling is inside S_c)."""
         a = torch.ones(C, dtype=torch.float64, device=device) if self.channel_weights is None else self.weights_tensor(device)
-        if self.space == "normalized":
+        if self.space == "normalized" and not self.is_robust:
             if std is None:
                 raise ValueError("Objective: the normalized space needs the target normaliser's std_with_epsilon()")
             a = a / std.to(device=device, dtype=torch.float64).reshape(-1) ** 2
         return a
 
     def _key(self):
-        return (self.space, self.kind, self.channel_weights, self.node_weighted)
+        return (self.space, self.kind, self.channel_weights, self.node_weighted, self.delta)
 
     def __eq__(self, other):
         return isinstance(other, Objective) and self._key() == other._key()
@@ -98,6 +150,8 @@ class Objective:
 
     def __repr__(self):
         tail = ", node_weighted=True" if self.node_weighted else ""
+        if self.delta is not None:
+            tail += f", delta={self.delta}"
         return f"Objective(space={self.space!r}, kind={self.kind!r}, channel_weights={self.channel_weights}{tail})"
 
     def check_node_weights(self, node_weights):
@@ -133,12 +187,31 @@ def channel_sums(pred, tar, mask, node_weights=None):
     return m.sum(), (m * d * d).reshape(-1, C).sum(0)
 
 
+def robust_sums(pred, tar, mask, objective, std=None, node_weights=None):
+    """(M, S[C]) of a robust objective in fp64 -- the row of bsms_robust_sums, differentiable in `pred`: d is rounded to fp32 once
+    (as `channel_sums`), u = double(d) / s_c, S_c = sum mu rho(u_c)."""
+    C = pred.shape[-1]
+    u = (pred - tar).double() / objective.scales(std, C, pred.device)
+    m = mask.double().reshape(*pred.shape[:-1], 1)
+    if node_weights is not None:
+        w = node_weights.double()
+        m = m * (w.reshape(*w.shape, 1) if w.dim() < pred.dim() else w)
+    au = u.abs()
+    if objective.kind == "huber":
+        dl = objective.delta_tensor(C, pred.device)
+        rho = torch.where(au <= dl, 0.5 * (u * u), dl * (au - 0.5 * dl))
+    else:
+        rho = au                                            # autograd's sign(0) is 0
+    return m.sum(), (m * rho).reshape(-1, C).sum(0)
+
+
 def finish_loss(M, SE, objective, std):
-    """loss (fp32 scalar) and the per-channel terms a_c SE_c / (M C) (fp64 [C]) from the sums."""
+    """loss (fp32 scalar) and the per-channel terms a_c SE_c / (M C) (fp64 [C]) from the sums.  The robust kinds take their S_c in
+    SE's place: the coefficients are w_c alone and there is no square root."""
     C = SE.shape[0]
     terms = objective.coefficients(std, C, SE.device) * SE / (M * C)
     Q = terms.sum()
-    return (Q if objective.kind == "mse" else torch.sqrt(Q)).float(), terms
+    return (torch.sqrt(Q) if objective.kind == "rmse" else Q).float(), terms
 
 
 def masked_loss(pred, tar, mask, objective=None, std=None, node_weights=None):
@@ -153,5 +226,8 @@ def masked_loss(pred, tar, mask, objective=None, std=None, node_weights=None):
         from .model import masked_rmse
         return masked_rmse(pred, tar, mask)
     objective.bind(pred.shape[-1])
-    M, SE = channel_sums(pred, tar, mask, node_weights)
+    if objective.is_robust:
+        M, SE = robust_sums(pred, tar, mask, objective, std, node_weights)
+    else:
+        M, SE = channel_sums(pred, tar, mask, node_weights)
     return finish_loss(M, SE, objective, std)[0]

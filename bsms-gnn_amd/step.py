@@ -108,7 +108,9 @@ class FusedStep:
         (`reduction="mean"`, what `(loss / M).backward()` gives); `ready` after the M-th, and the next call starts a new cycle.
         `objective` (objective.Objective): None or the default objective keeps the reference's masked RMSE on the kernels it
         always ran on; any other runs bsms_error_sums after every forward and bsms_sim_objective_bwd in front of every backward --
-        their `_w` entries with `objective.node_weighted`, which takes `node_weights=` with every call.
+        their `_w` entries with `objective.node_weighted`, which takes `node_weights=` with every call.  A robust
+        objective (kind "mae" / "huber") runs bsms_robust_sums and bsms_sim_robust_bwd in their places, with or
+        without node weights; everything behind the sums and the loss gradient is the same step.
         `input_grad`: every backward also forms the gradient of the (K-step) loss w.r.t. `node_in` -- state, mesh
         positions and node type -- into a static [B, N, C+p+1] buffer, handed out by `input_grad()`.  Off: nothing changes.
         `param_grad=False` (with `input_grad=True`): the backward is data-only whatever `requires_grad` says -- no weight gradient is
@@ -167,6 +169,7 @@ class FusedStep:
         self._acc = None                            # accumulate > 1: dict(running fp64 [K,3], coef fp32 [2], loss fp32 [K]) on the device
         self._gsum = None                           # accumulate > 1 and unroll > 1: where a micro-batch t >= 1 sums its K steps
         self._obj_w = None                          # the channel weights on the device (fp64 [C]), or None for unit weights
+        self._obj_delta = None                      # a Huber objective: delta on the device (fp64 [C])
         self._gscratch, self._wts = None, None     # unroll > 1: scratch flat gradient buffer (GradBuckets layout), weights on the device
         self._shape_key, self._graphs, self._ptr_guard = None, None, None
         self._pg, self._pg_builds = None, 0   # pack group of the current pointer tables and buffers (_pack_group), built lazily; how often
@@ -308,6 +311,8 @@ class FusedStep:
                      work_obj=u8("work_obj", L.bsms_error_sums_work_bytes(1, R)))
             if self._obj_w is None or self._obj_w.device != dev:
                 self._obj_w = self._obj.weights_tensor(dev)
+            if self._obj.delta is not None and (self._obj_delta is None or self._obj_delta.device != dev):
+                self._obj_delta = self._obj.delta_tensor(C, dev)
             if self._obj.node_weighted:               # the step's own copy of the node weights, one per row
                 b["nw"] = f("nw", R)
         if self._input_grad:                          # shared by the K steps: every launch that touches them is on the caller's stream
@@ -430,6 +435,14 @@ class FusedStep:
         ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), None, R, C, p,
                                no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["pred"].data_ptr(),
                                _ptr(next_in), _ptr(ic), None, work.data_ptr(), s), "bsms_sim_epilogue")
+        if self._obj.is_robust:               # [M | S] into the first 1 + C fields of the same row; the rest of the row is not written
+            from .objective import ROBUST_KINDS, SPACES
+            nw = b["nw"].data_ptr() if self._obj.node_weighted else None
+            ck(L.bsms_robust_sums(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), nw, 1, R, C, R, R, R, R, no._E_data.data_ptr(),
+                                  no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), _ptr(self._obj_delta), SPACES[self._obj.space],
+                                  ROBUST_KINDS[self._obj.kind], b["osums"].data_ptr(), 1 + 3 * C, b["work_obj"].data_ptr(), s),
+               "bsms_robust_sums")
+            return
         if self._obj.node_weighted:           # mu = mask * weight in the mask's place; the row [M | SE] downstream is none the wiser
             ck(L.bsms_error_sums_w(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), b["nw"].data_ptr(), 1, R, C, R, R, R, R,
                                    b["osums"].data_ptr(), b["work_obj"].data_ptr(), s), "bsms_error_sums_w")
@@ -452,7 +465,17 @@ class FusedStep:
         ig = b["ig"] if self._input_grad else None
         if ig is not None and chain is None:          # the single step as a chain of one: w = 1, nothing carried, g_pred kept
             chain = dict(w=1.0, tabs=t, g_pred_next=None, g_nin_next=None, g_pred=ig["g_pred"], grad_x=ig["g_nin"], first_step=1, overwrite=1)
-        if self._obj is not None:
+        if self._obj is not None and self._obj.is_robust:
+            from .objective import ROBUST_KINDS, SPACES
+            ni, o = m._inputNormalizer, self._obj
+            c = chain or dict(w=1.0, g_pred_next=None, g_nin_next=None, g_pred=None)
+            ck(L.bsms_sim_robust_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), b["nw"].data_ptr() if o.node_weighted else None,
+                                     R, R, C, no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(),
+                                     ni._E_data.data_ptr(), ni._E_data_squared.data_ptr(), ni.std_eps.data_ptr(), b["osums"].data_ptr(),
+                                     _ptr(self._obj_w), _ptr(self._obj_delta), SPACES[o.space], ROBUST_KINDS[o.kind], c["w"],
+                                     _ptr(c["g_pred_next"]), _ptr(c["g_nin_next"]), b["loss"].data_ptr(), b["chan"].data_ptr(),
+                                     _ptr(c["g_pred"]), b["g_np"].data_ptr(), s), "bsms_sim_robust_bwd")
+        elif self._obj is not None:
             from .objective import KINDS, SPACES
             ni, o = m._inputNormalizer, self._obj
             c = chain or dict(w=1.0, g_pred_next=None, g_nin_next=None, g_pred=None)
@@ -667,9 +690,12 @@ class FusedStep:
         sums, no, o = self._loss_sums(b), self.model._targetNormalizer, self.objective
         row = self._obj is not None
         C = self.model.cfg.out_dim
+        # A robust loss is sum_c w_c S_c / (M C): the mse algebra of the PHYSICAL space on the row [M | S] (the scaling by s_c is
+        # already inside S_c) -- bsms_accum_coef forms that loss and its fold coefficients exactly, with no entry of their own.
+        space, kind = (SPACES["physical"], KINDS["mse"]) if o.is_robust else (SPACES[o.space], KINDS[o.kind])
         _abi.check(L.bsms_accum_coef(sums.data_ptr(), int(row), (1 + 3 * C) if row else 2, C, no._E_data.data_ptr(),
                                      no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), _ptr(self._obj_w) if row else None,
-                                     SPACES[o.space], KINDS[o.kind], REDUCTIONS[self.reduction], t, K, self._acc["running"].data_ptr(),
+                                     space, kind, REDUCTIONS[self.reduction], t, K, self._acc["running"].data_ptr(),
                                      self._acc["coef"].data_ptr(), self._acc["loss"].data_ptr(), s), "bsms_accum_coef")
         if t > 0 and self._any_live:
             _abi.check(L.bsms_grad_fold(self.grads.flat.data_ptr(), g.data_ptr(), self.grads.flat.numel(), self._acc["coef"].data_ptr(), s),
@@ -731,7 +757,7 @@ class FusedStep:
 
     def channel_losses(self):
         """Device [K, C]: the per-channel terms a_c SE_c / (M C) of every step of the last call -- they add up to Q, the loss under
-        kind = "mse" and its square under "rmse" (a copy).  Only the objective route (bsms_sim_objective_bwd's `chan_out`) forms them."""
+        kind = "mse" and its square under "rmse"; w_c S_c / (M C) of a robust objective (a copy).  Only the objective route (bsms_sim_objective_bwd's `chan_out`) forms them."""
         if self._obj is None:
             raise ValueError("FusedStep.channel_losses: the default objective runs the reference's kernels, which form no per-channel "
                              "terms; pass objective=Objective(channel_weights=[1.0] * out_dim) to get them for the same loss")

@@ -335,7 +335,9 @@ class Trainer:
     (`ema_model()`, `get_pred / get_loss / get_error(..., ema=True)`, `{step}_ema_params.pth` in `save`), skip_nonfinite.  Optional in `model_cfg`:
     unroll_steps (default 1: the reference's single-step loss), unroll_weights, unroll_detach -- the loss over that many
     autoregressive steps (step.FusedStep); `iter` then takes `(batch, later_targets)`, what TrajectoryBank(horizon=K) hands out;
-    loss_space ("physical" / "normalized"), loss_kind ("rmse" / "mse"), loss_channel_weights -- the training objective
+    loss_space ("physical" / "normalized"), loss_kind ("rmse" / "mse", or the robust "mae" / "huber" of DESIGN.md 4.20),
+    loss_delta (the Huber threshold in the units of loss_space, a float or one per channel: required by "huber", refused by every other
+    kind), loss_channel_weights -- the training objective
     (objective.Objective; absent: the reference's masked RMSE in physical units), which `iter` trains on and `get_loss` reports;
     loss_node_weights (absent or false: off) -- the objective weights every node by what `iter(data, node_weights=)` and
     `get_loss(data, node_weights=)` are given, e.g. the lumped measure; `get_error` and the rollout statistics stay unweighted;

@@ -505,6 +505,36 @@ int bsms_sim_objective_bwd_w(const float* pred, const float* target, const float
                              int space, int kind, float w, const float* g_pred_next /* nullable */,
                              const float* g_norm_in_next /* nullable */, float* loss_out /* nullable */, float* chan_out /* nullable */,
                              float* g_pred /* nullable */, float* grad_norm_pred, bsms_stream_t stream);
+/* bsms_sim_objective_bwd_w for the ROBUST objectives: masked MAE and Huber losses, which are linear in their
+ * per-channel sums.  With d = fl32(pred - tar), mu = m (row_weights == NULL) or m * omega, s_c = 1 (BSMS_LOSS_PHYSICAL) or the TARGET
+ * normaliser's std_c (BSMS_LOSS_NORMALIZED), u_c = double(d_c) / s_c and delta (DEVICE double[C], > 0, in the units of the space;
+ * read with BSMS_ROBUST_HUBER only):
+ *   rho(u)          = |u| (BSMS_ROBUST_MAE)   or   u^2 / 2 if |u| <= delta_c, else delta_c (|u| - delta_c / 2) (BSMS_ROBUST_HUBER)
+ *   psi(u)          = sign(u), sign(0) = 0    or   clamp(u, -delta_c, delta_c)
+ *   sums            = [ M | S[0..C) ]  DEVICE double, M = sum mu, S[c] = sum mu rho(u_c): the row bsms_robust_sums writes (all-reduced
+ *                     first under data parallelism)
+ *   loss            = sum_c w_c S[c] / (M C)  -> loss_out (fp32, NOT weighted by `w`; no square root);   chan_out[c] = w_c S[c] / (M C)
+ *   g_pred_k        = w * ((fl32(psi(u_c)) * mu) * fl32(w_c / (M C s_c))) + carry_k
+ *   grad_norm_pred  = float(double(g_pred_k * mask) * std_c)
+ * `space` only chooses s_c: there is no 1 / std^2 on top.  ORDER of the fp32 operations: mu = m * omega (one rounding; skipped
+ * without row_weights), then fl32(psi) * mu, then * fl32(w_c / (M C s_c)) -- the coefficient is formed in fp64 and rounded once --
+ * then * w, then + carry.  With omega == 1 mu IS m: all-ones weights reproduce row_weights == NULL bit for bit.  omega -> 2^k omega
+ * scales the sums by 2^k and the coefficient by 2^-k exactly: every output keeps its bits (short of overflow and of subnormals).
+ * With row_weights == NULL weight_period is ignored.  The carry, the carried pair, in_*, the mask of the way out and the unguarded
+ * M == 0 are bsms_sim_objective_bwd_w's, and so is the order of the checks: R >= 1 and C in 1..8, then space and rkind in {0, 1}
+ * (BSMS_E_UNSUPPORTED, before any pointer is looked at); then null required pointers -- `delta` with BSMS_ROBUST_HUBER among
+ * them --, then with row_weights a weight_period that is < 1 or does not divide R, then half a carried pair
+ * (BSMS_E_INVALID_ARG); all before any device call.  One launch, thread r owns row r; no atomics, no allocation, no
+ * synchronisation, nothing read back: capturable. */
+enum { BSMS_ROBUST_MAE = 0, BSMS_ROBUST_HUBER = 1 };         /* rkind */
+int bsms_sim_robust_bwd(const float* pred, const float* target, const float* mask, const float* row_weights /* nullable */,
+                        int64_t weight_period, int64_t R, int64_t C, const double* mean, const double* meansq,
+                        const double* std_eps, const double* in_mean /* nullable */, const double* in_meansq /* nullable */,
+                        const double* in_std_eps /* nullable */, const double* sums, const double* channel_weights /* nullable */,
+                        const double* delta /* nullable with BSMS_ROBUST_MAE */, int space, int rkind, float w,
+                        const float* g_pred_next /* nullable */, const float* g_norm_in_next /* nullable */,
+                        float* loss_out /* nullable */, float* chan_out /* nullable */, float* g_pred /* nullable */,
+                        float* grad_norm_pred, bsms_stream_t stream);
 /* The gradient of the K-step objective w.r.t. its INPUT, G = dJ / d in_0: one launch folds step k into
  * `grad_in` [R, C+p+1], which has the column layout of node_in = [state (C) | mesh_pos (p) | node_type].  in_0 reaches step k
  * through its positions and node type on every row, through its state on every row at k = 0, and at k > 0 through its state
@@ -565,6 +595,28 @@ int bsms_error_sums(const float* pred, const float* target, const float* mask, i
 int bsms_error_sums_w(const float* pred, const float* target, const float* mask, const float* row_weights, int64_t S,
                       int64_t seg_rows, int64_t C, int64_t pred_stride, int64_t target_stride, int64_t mask_stride,
                       int64_t weight_stride, double* sums, void* work, bsms_stream_t stream);
+/* The sums of the ROBUST training objectives (rho, u_c, s_c, delta, mu as at bsms_sim_robust_bwd above): per segment
+ *   sums + s * sums_stride = [ M | S[0..C) ],   M = sum mu,   S[c] = sum mu * rho(double(d_c) / s_c)      (products and sums in fp64)
+ * with mu = double(m) (row_weights == NULL: the unweighted kernel) or double(m) * double(omega) as in bsms_error_sums_w -- all-ones
+ * weights reproduce NULL bit for bit.  sums_stride >= 1 + C counts doubles; the fields of a row past 1 + C are NOT written (a caller
+ * keeps rows of 1 + 3C there and sends them as one message).  mean / meansq / std_eps: the TARGET normaliser's, DEVICE double, read
+ * with BSMS_LOSS_NORMALIZED only (nullable otherwise); delta: DEVICE double[C], read with BSMS_ROBUST_HUBER only.
+ * The kernel IS bsms_error_sums_w's, with another policy for what a row adds: the one fp32 rounding of d, pieces of 1024 rows counted
+ * from the segment's first row, per-thread rows in ascending order, the fixed shuffle tree, the four waves in order, the finishing
+ * kernel -- so a segment's sums depend on its own rows only and are bit-identical from run to run, and with BSMS_LOSS_PHYSICAL +
+ * BSMS_ROBUST_MAE S[c] is the AE[c] of bsms_error_sums(_w) on the same rows bit for bit (x / 1.0 is exact).  `work` holds
+ * bsms_error_sums_work_bytes(S, seg_rows) bytes.  No atomics, no allocation, no synchronisation: capturable.
+ * The loss sum_c w_c S[c] / (M C) is linear in the row, so bsms_accum_coef (below) with BSMS_ACCUM_SUMS_ROW, BSMS_LOSS_PHYSICAL and
+ * BSMS_LOSS_MSE on these rows forms exactly the robust loss and its fold coefficients: the scaling by s_c is already inside S[c].
+ * Checked in this order, all before any device call: C in 1..8, then space and rkind in {0, 1} (BSMS_E_UNSUPPORTED, before any pointer
+ * is looked at); then the S / seg_rows / stride limits of bsms_error_sums_w and sums_stride >= 1 + C (BSMS_E_INVALID_ARG); S == 0
+ * returns BSMS_OK; then null required pointers -- the statistics with BSMS_LOSS_NORMALIZED and delta with BSMS_ROBUST_HUBER among
+ * them -- give BSMS_E_INVALID_ARG. */
+int bsms_robust_sums(const float* pred, const float* target, const float* mask, const float* row_weights /* nullable */, int64_t S,
+                     int64_t seg_rows, int64_t C, int64_t pred_stride, int64_t target_stride, int64_t mask_stride,
+                     int64_t weight_stride, const double* mean /* nullable */, const double* meansq /* nullable */,
+                     const double* std_eps /* nullable */, const double* delta /* nullable with BSMS_ROBUST_MAE */, int space,
+                     int rkind, double* sums, int64_t sums_stride, void* work, bsms_stream_t stream);
 
 /* ---------------------------------------------------------------- batch assembly from resident trajectories ---
  * The level-0 node tensors of a batch (datasets/base.py:238-289, `proc_data`, plus the collate) built by ONE launch from
