@@ -5,9 +5,9 @@ libbsms_hip.so (include/bsms_hip.h).  Import name: `bsms_gnn_amd` (directory: `b
 from . import _abi  # noqa: F401
 from .graph import LevelData, LevelPlan, MeshBank, clear_plan_cache, collate_variable_meshes, concat_plans, plan_for  # noqa: F401
 from .model import BSMS_Simulator, Normalizer, masked_rmse  # noqa: F401
-from .objective import Objective, masked_loss  # noqa: F401
-from .ops import BSGMP, GMP, MLP, InferenceSession, Unpool, WeightedEdgeConv, degree, error_sums, scatter_sum  # noqa: F401
-from .eval import equivariance_error, error_mean_std  # noqa: F401
+from .objective import Objective, edge_difference_loss, edge_difference_sums, masked_loss  # noqa: F401
+from .ops import BSGMP, GMP, MLP, InferenceSession, Unpool, WeightedEdgeConv, degree, edge_diff_bwd, edge_diff_sums, error_sums, scatter_sum  # noqa: F401
+from .eval import edge_error_mean_std, equivariance_error, error_mean_std  # noqa: F401
 from .databank import Augment, TrajectoryBank, epoch_picks, transform_rows  # noqa: F401
 from .dp import DataParallel, GradBuckets, global_masked_rmse  # noqa: F401
 from .hierarchy import BistrideMultiLayerGraph, lumped_node_measure, to_flat_edge  # noqa: F401

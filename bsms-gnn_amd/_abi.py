@@ -109,6 +109,11 @@ SIGNATURES = {
                                   c_void_p, c_void_p]),
     "bsms_robust_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p]),
+    "bsms_edge_diff_work_bytes": (c_size_t, [c_i64, c_i64]),
+    "bsms_edge_diff_sums": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_i64,
+                                    c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
+    "bsms_edge_diff_bwd": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_i64,
+                                   c_i64, c_i64, c_i64, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
     "bsms_batch_assemble": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, C.c_double, c_void_p, c_i64, C.c_uint64, C.c_uint64,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bsms_batch_targets": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p]),

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libbsms_hip.so")
 SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "chain_d32.hip", "chain_d64.hip", "chain_d96.hip", "chain_d128.hip", "chain_d160.hip", "chain_d192.hip", "chain_d224.hip",
-           "chain_d256.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "mlp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip", "batch.hip", "errsum.hip"]
+           "chain_d256.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "mlp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip", "batch.hip", "errsum.hip", "edgediff.hip"]
 # chain.hip: prepack + dispatch on the latent width; chain_d<D>.hip: the chain kernels of one width (templates in chain_kernels.h /
 # chain_edge.h, launchers in chain_launch.h), one translation unit each so that they compile in parallel
 HEADERS = ["common.h", "chain.h", "host_orch.h", "gmp_block.h", "chain_dev.h", "chain_kernels.h", "chain_edge.h", "chain_launch.h", os.path.join("..", "..", "include", "bsms_hip.h")]
@@ -46,8 +46,8 @@ def build(force=False, verbose=True):
     def compile_one(src):
         obj = os.path.join(OBJ, os.path.basename(src).replace(".hip", ".o"))
         # no contraction: rowsum.hip rounds x*ew before the add like the reference; sim.hip keeps the fp64 normaliser roundings;
-        # batch.hip rounds g*noise before the add like the host's torch ops; errsum.hip keeps separate fp64 multiplies and adds
-        extra = ["-ffp-contract=off"] if src in ("rowsum.hip", "sim.hip", "batch.hip", "errsum.hip") else []
+        # batch.hip rounds g*noise before the add like the host's torch ops; errsum.hip and edgediff.hip keep separate fp64 multiplies and adds
+        extra = ["-ffp-contract=off"] if src in ("rowsum.hip", "sim.hip", "batch.hip", "errsum.hip", "edgediff.hip") else []
         if src.startswith("chain") and os.environ.get("BSMS_CHAIN_FLAGS"):   # A/B builds (chain.hip and the chain_d*.hip widths)
             extra += os.environ["BSMS_CHAIN_FLAGS"].split()
         cmd = [hipcc, *FLAGS, *extra, "-c", os.path.join(CSRC, src), "-o", obj]

@@ -1,0 +1,361 @@
+// Edge-difference (discrete H1) error sums and their adjoint (include/bsms_hip.h: bsms_edge_diff_sums, bsms_edge_diff_bwd; DESIGN.md
+// 4.21).  Per segment s (a sample of a batch, or a time step of a rolled-out trajectory) over the directed edges e = (i -> j) of the
+// plan's rows [row0, row0 + seg_rows) whose BOTH ends lie in that window:
+//   mu_e = double(m_i) * double(m_j)     omega_e = 1 ("difference") | 1 / l2_e, l2_e = sum_k (double(pos_ik) - double(pos_jk))^2
+//   ("quotient"; an edge with l2_e == 0 has mu_e = omega_e = 0)
+//   ME = sum mu_e    DE[c] = sum mu_e omega_e (d_ic - d_jc)^2    TE[c] = sum mu_e omega_e (t_ic - t_jc)^2,   d = fl32(pred - target)
+// d takes the ONE fp32 rounding of bsms_error_sums; every product and sum after it is fp64.
+// Deterministic, no atomics.  Sums: row r owns its INCOMING edges (the plan's dst-sorted CSR, stable in the caller's edge order) and
+// adds them one after the other; the rows are reduced like those of errsum.hip -- pieces of kPieceRows rows counted from the
+// segment's own first row, one row per thread, a fixed shuffle tree per wave, the sixteen waves in order, and k_edge_finish adds
+// the pieces in index order.  A segment's row therefore depends on its own rows and edges only: not on S, the
+// strides, its neighbours in the launch, or on whether the plan is the mesh's own or a block-diagonal union around it.
+// Backward: thread r owns grad[s, r, :]; per element ONE fp64 accumulator, incoming edges in CSR order, then outgoing edges in
+// transpose order, times 2 * coef[s, c] in fp64, ONE rounding to fp32.
+// An edge whose other end lies outside the window is not read: its index is replaced by the row's own (a load that is in bounds and
+// in cache) and its term is dropped by a select, so the loop carries no branch and the index / row loads of consecutive edges stay
+// independent.
+// Compiled with -ffp-contract=off (build.py): the sums keep the roundings of separate fp64 multiplies and adds.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+using namespace bsms;
+
+namespace {
+
+constexpr int kMaxC = 8;                                // state channels (errsum.hip keeps the same bound)
+constexpr int kMaxP = 3;                                // position columns
+constexpr int kMaxCols = 1 + 2 * kMaxC;                 // ME | DE | TE
+constexpr int kPieceRows = 1024;                        // rows of a segment per block of the sums: one row per thread, sixteen waves
+constexpr int kBwdThreads = 256;                        // rows per block of the backward
+constexpr int64_t kMaxBlocksPerLaunch = int64_t(1) << 21;   // 2^31 threads: below the 2^32 work items of one dispatch
+
+struct EdgeArgs {
+  const int32_t *rowptr, *src;                          // incoming edges of plan row n: src[rowptr[n] .. rowptr[n+1])
+  const int32_t *t_rowptr, *t_dst;                      // outgoing edges of plan row n (backward only)
+  const float *pred, *target, *mask, *pos;              // row 0 of segment 0
+  int64_t row0, seg_rows, pieces;                       // the window of the plan; blocks per segment
+  int64_t pred_stride, target_stride, mask_stride, pos_stride;   // rows between the segments
+  int64_t blk0;                                         // global index of this launch's first block
+  int p;
+};
+
+// C (and with it every loop below) is a compile-time constant: the rows of pred / target load as one or two wide loads (global
+// loads need dword alignment only) and nothing inside the edge loop branches -- with C, the position width or the window test as
+// run-time branches hipcc waits for every load before it issues the next one.
+template <int C>
+struct Node {                                           // what an edge reads of one of its ends
+  float d[C], t[C], x[kMaxP], m;
+};
+
+template <int C, bool kQuot>
+__device__ __forceinline__ Node<C> load_node(const float* __restrict__ pred, const float* __restrict__ target, const float* __restrict__ mask,
+                                             const float* __restrict__ pos, int p, int64_t r) {
+  Node<C> n;
+  float pr[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) pr[c] = pred[r * C + c];
+#pragma unroll
+  for (int c = 0; c < C; ++c) n.t[c] = target[r * C + c];
+#pragma unroll
+  for (int c = 0; c < C; ++c) n.d[c] = pr[c] - n.t[c];              // the fp32 subtraction of bsms_error_sums
+  n.m = mask[r];
+  if (kQuot) {                                          // p in 1..3: the columns past p re-read column 0 (in bounds); edge_weight drops them
+    const float* x = pos + r * p;
+    n.x[0] = x[0];
+    n.x[1] = x[p > 1 ? 1 : 0];
+    n.x[2] = x[p > 2 ? 2 : 0];
+  } else {
+    n.x[0] = n.x[1] = n.x[2] = 0.f;
+  }
+  return n;
+}
+
+// mu_e * omega_e of the edge between `a` and `b`; `mu` returns mu_e alone (what ME counts).  An edge without length ("quotient")
+// has both 0.
+template <int C, bool kQuot>
+__device__ __forceinline__ double edge_weight(const Node<C>& a, const Node<C>& b, int p, double& mu) {
+  mu = double(a.m) * double(b.m);
+  if (!kQuot) return mu;
+  double l2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < kMaxP; ++k) {
+    const double dx = double(a.x[k]) - double(b.x[k]);
+    const double sq = dx * dx;
+    l2 = k < p ? l2 + sq : l2;                          // a select: the sum runs over the p columns in order
+  }
+  const bool flat = l2 == 0.0;
+  const double w = 1.0 / (flat ? 1.0 : l2);
+  mu = flat ? 0.0 : mu;
+  return flat ? 0.0 : mu * w;
+}
+
+// U consecutive slots of a row per step: all index loads, then all neighbour loads, then the terms strictly in slot order.  A slot
+// past the row's end, or one whose other end lies outside the window, loads the row itself (in bounds, in cache) and is dropped by
+// a select: the accumulators see exactly the additions of the edges that count, in CSR order.
+template <int C>
+struct Batch {                                          // neighbour rows in flight per lane
+  static constexpr int kSums = C <= 4 ? 4 : C <= 6 ? 2 : 1;     // 1024 threads leave 128 registers, 2 (1 + 2C) of them accumulators
+  static constexpr int kBwd = C <= 4 ? 4 : 2;
+};
+
+template <int C, bool kQuot>
+__global__ __launch_bounds__(kPieceRows) void k_edge_pieces(const EdgeArgs a, double* __restrict__ partials) {
+  constexpr int ncol = 1 + 2 * C, U = Batch<C>::kSums;
+  __shared__ double red[kPieceRows / 64][ncol];
+  const int64_t blk = a.blk0 + int64_t(blockIdx.x);
+  const int64_t s = blk / a.pieces, piece = blk - s * a.pieces;
+  const float* pred = a.pred + s * a.pred_stride * C;
+  const float* target = a.target + s * a.target_stride * C;
+  const float* mask = a.mask + s * a.mask_stride;
+  const float* pos = kQuot ? a.pos + s * a.pos_stride * a.p : nullptr;
+
+  double acc[ncol];
+#pragma unroll
+  for (int k = 0; k < ncol; ++k) acc[k] = 0.0;
+  const int64_t r = piece * kPieceRows + int(threadIdx.x);          // row inside the segment
+  if (r < a.seg_rows) {
+    const int q0 = a.rowptr[a.row0 + r], q1 = a.rowptr[a.row0 + r + 1];
+    const Node<C> me = load_node<C, kQuot>(pred, target, mask, pos, a.p, r);
+    for (int q = q0; q < q1; q += U) {                  // CSR order = the caller's edge order
+      int64_t o[U];
+      bool counts[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const bool live = q + u < q1;
+        o[u] = int64_t(a.src[live ? q + u : q]) - a.row0;
+        counts[u] = live && o[u] >= 0 && o[u] < a.seg_rows;
+        o[u] = counts[u] ? o[u] : r;
+      }
+      Node<C> other[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) other[u] = load_node<C, kQuot>(pred, target, mask, pos, a.p, o[u]);
+      __builtin_amdgcn_sched_barrier(0);                // every neighbour load is in flight before the first add
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        double mu;
+        const double mw = edge_weight<C, kQuot>(other[u], me, a.p, mu);
+        acc[0] = counts[u] ? acc[0] + mu : acc[0];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const double dd = double(other[u].d[c]) - double(me.d[c]);
+          const double td = double(other[u].t[c]) - double(me.t[c]);
+          const double de = acc[1 + c] + mw * (dd * dd), te = acc[1 + C + c] + mw * (td * td);
+          acc[1 + c] = counts[u] ? de : acc[1 + c];
+          acc[1 + C + c] = counts[u] ? te : acc[1 + C + c];
+        }
+      }
+    }
+  }
+  // fixed trees: lanes of a wave by shuffle, then the sixteen waves in order
+  const int lane = int(threadIdx.x) & 63, wave = int(threadIdx.x) >> 6;
+#pragma unroll
+  for (int k = 0; k < ncol; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (int(threadIdx.x) < ncol) {
+    const int k = int(threadIdx.x);
+    double v = red[0][k];
+#pragma unroll
+    for (int w = 1; w < kPieceRows / 64; ++w) v += red[w][k];
+    partials[blk * ncol + k] = v;
+  }
+}
+
+// sums[s, col] = the pieces of segment s added in index order (zero pieces: zeros); one thread per output element
+__global__ __launch_bounds__(256) void k_edge_finish(const double* __restrict__ partials, int64_t S, int64_t pieces, int ncol,
+                                                    double* __restrict__ sums) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + int(threadIdx.x);
+  if (i >= S * ncol) return;
+  const int64_t s = i / ncol;
+  const int col = int(i - s * ncol);
+  const double* p = partials + s * pieces * ncol + col;
+  double v = 0.0;
+#pragma unroll 8
+  for (int64_t k = 0; k < pieces; ++k) v += p[k * ncol];
+  sums[i] = v;
+}
+
+// grad[s, r, c] = fl32(2 coef[s, c] * (sum over incoming, then outgoing edges of mu omega (d_rc - d_other,c))); one thread per row
+template <int C, bool kQuot>
+__global__ __launch_bounds__(kBwdThreads) void k_edge_bwd(const EdgeArgs a, const double* __restrict__ coef, int accumulate,
+                                                         float* __restrict__ grad, int64_t grad_stride) {
+  constexpr int U = Batch<C>::kBwd;
+  const int64_t blk = a.blk0 + int64_t(blockIdx.x);
+  const int64_t s = blk / a.pieces;
+  const int64_t r = (blk - s * a.pieces) * kBwdThreads + int(threadIdx.x);
+  if (r >= a.seg_rows) return;
+  const float* pred = a.pred + s * a.pred_stride * C;
+  const float* target = a.target + s * a.target_stride * C;
+  const float* mask = a.mask + s * a.mask_stride;
+  const float* pos = kQuot ? a.pos + s * a.pos_stride * a.p : nullptr;
+  const int in0 = a.rowptr[a.row0 + r], in1 = a.rowptr[a.row0 + r + 1];
+  const int out0 = a.t_rowptr[a.row0 + r], out1 = a.t_rowptr[a.row0 + r + 1];
+  const Node<C> me = load_node<C, kQuot>(pred, target, mask, pos, a.p, r);
+  double acc[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 0.0;
+#pragma unroll 1
+  for (int half = 0; half < 2; ++half) {                // incoming edges in CSR order, then outgoing edges in transpose order
+    const int32_t* __restrict__ nbr = half ? a.t_dst : a.src;
+    const int q0 = half ? out0 : in0, q1 = half ? out1 : in1;
+    for (int q = q0; q < q1; q += U) {
+      int64_t o[U];
+      bool counts[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const bool live = q + u < q1;
+        o[u] = int64_t(nbr[live ? q + u : q]) - a.row0;
+        counts[u] = live && o[u] >= 0 && o[u] < a.seg_rows;
+        o[u] = counts[u] ? o[u] : r;
+      }
+      Node<C> other[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) other[u] = load_node<C, kQuot>(pred, target, mask, pos, a.p, o[u]);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        double mu;
+        const double mw = edge_weight<C, kQuot>(other[u], me, a.p, mu);
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const double nxt = acc[c] + mw * (double(me.d[c]) - double(other[u].d[c]));
+          acc[c] = counts[u] ? nxt : acc[c];
+        }
+      }
+    }
+  }
+  float* g = grad + (s * grad_stride + r) * C;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const float v = float((2.0 * coef[s * C + c]) * acc[c]);        // the one rounding to fp32
+    g[c] = accumulate ? g[c] + v : v;
+  }
+}
+
+template <int C>
+void launch_pieces(bool quot, unsigned nb, hipStream_t s, const EdgeArgs& a, double* partials) {
+  if (quot) hipLaunchKernelGGL((k_edge_pieces<C, true>), dim3(nb), dim3(kPieceRows), 0, s, a, partials);
+  else hipLaunchKernelGGL((k_edge_pieces<C, false>), dim3(nb), dim3(kPieceRows), 0, s, a, partials);
+}
+
+template <int C>
+void launch_bwd(bool quot, unsigned nb, hipStream_t s, const EdgeArgs& a, const double* coef, int accumulate, float* grad, int64_t grad_stride) {
+  if (quot) hipLaunchKernelGGL((k_edge_bwd<C, true>), dim3(nb), dim3(kBwdThreads), 0, s, a, coef, accumulate, grad, grad_stride);
+  else hipLaunchKernelGGL((k_edge_bwd<C, false>), dim3(nb), dim3(kBwdThreads), 0, s, a, coef, accumulate, grad, grad_stride);
+}
+
+#define BSMS_EDGE_BY_C(C_, CALL)  \
+  switch (C_) {                   \
+    case 1: CALL(1); break;       \
+    case 2: CALL(2); break;       \
+    case 3: CALL(3); break;       \
+    case 4: CALL(4); break;       \
+    case 5: CALL(5); break;       \
+    case 6: CALL(6); break;       \
+    case 7: CALL(7); break;       \
+    default: CALL(8); break;      \
+  }
+
+inline int64_t pieces_of(int64_t seg_rows) { return ceil_div(seg_rows, kPieceRows); }
+
+// The checks both entries share, in the order of bsms_error_sums; fills `a` when there is work.  Returns BSMS_OK with *go = false when
+// S == 0.
+int edge_args(const char* who, const bsms_plan* plan, int64_t row0, int64_t seg_rows, const float* pred, const float* target,
+              const float* mask, const float* pos, int64_t S, int64_t C, int64_t p, int weighting, int64_t pred_stride,
+              int64_t target_stride, int64_t mask_stride, int64_t pos_stride, EdgeArgs* a, bool* go) {
+  *go = false;
+  BSMS_REQUIRE(C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "%s: C=%lld (C in 1..8)", who, (long long)C);
+  BSMS_REQUIRE(weighting == BSMS_EDGE_DIFFERENCE || weighting == BSMS_EDGE_QUOTIENT, BSMS_E_UNSUPPORTED, "%s: weighting=%d (0 or 1)", who,
+               weighting);
+  const bool quot = weighting == BSMS_EDGE_QUOTIENT;
+  BSMS_REQUIRE(!quot || (p >= 1 && p <= kMaxP), BSMS_E_UNSUPPORTED, "%s: p=%lld (p in 1..3 with the quotient weighting)", who, (long long)p);
+  BSMS_REQUIRE(S >= 0 && seg_rows >= 0 && seg_rows <= INT32_MAX && row0 >= 0, BSMS_E_INVALID_ARG,
+               "%s: S=%lld row0=%lld seg_rows=%lld (seg_rows in 0..2^31-1)", who, (long long)S, (long long)row0, (long long)seg_rows);
+  BSMS_REQUIRE(pred_stride >= 0 && target_stride >= 0 && mask_stride >= 0 && pos_stride >= 0, BSMS_E_INVALID_ARG,
+               "%s: negative segment stride (%lld, %lld, %lld, %lld)", who, (long long)pred_stride, (long long)target_stride,
+               (long long)mask_stride, (long long)pos_stride);
+  if (S == 0) return BSMS_OK;
+  BSMS_REQUIRE(plan, BSMS_E_INVALID_ARG, "%s: plan is null", who);
+  BSMS_REQUIRE(row0 + seg_rows <= plan->N, BSMS_E_SHAPE, "%s: rows [%lld, %lld) are not a window of a plan of %lld rows", who,
+               (long long)row0, (long long)(row0 + seg_rows), (long long)plan->N);
+  BSMS_REQUIRE(seg_rows == 0 || (pred && target && mask && (pos || !quot)), BSMS_E_INVALID_ARG, "%s: null argument", who);
+  a->rowptr = plan->rowptr; a->src = plan->src; a->t_rowptr = plan->t_rowptr; a->t_dst = plan->t_dst;
+  a->pred = pred; a->target = target; a->mask = mask; a->pos = quot ? pos : nullptr;
+  a->row0 = row0; a->seg_rows = seg_rows; a->pieces = pieces_of(seg_rows);
+  a->pred_stride = pred_stride; a->target_stride = target_stride; a->mask_stride = mask_stride; a->pos_stride = pos_stride;
+  a->blk0 = 0;
+  a->p = quot ? int(p) : 0;
+  *go = true;
+  return BSMS_OK;
+}
+
+}  // namespace
+
+extern "C" size_t bsms_edge_diff_work_bytes(int64_t S, int64_t seg_rows) {
+  if (S < 0 || seg_rows < 0) return 0;
+  return size_t(std::max<int64_t>(S, 1)) * size_t(std::max<int64_t>(pieces_of(seg_rows), 1)) * kMaxCols * sizeof(double) + 256;
+}
+
+extern "C" int bsms_edge_diff_sums(const bsms_plan_t* plan, int64_t row0, int64_t seg_rows, const float* pred, const float* target,
+                                   const float* mask, const float* pos, int64_t S, int64_t C, int64_t p, int weighting,
+                                   int64_t pred_stride, int64_t target_stride, int64_t mask_stride, int64_t pos_stride, double* sums,
+                                   void* work, bsms_stream_t stream) {
+  EdgeArgs a;
+  bool go;
+  if (int rc = edge_args("edge_diff_sums", plan, row0, seg_rows, pred, target, mask, pos, S, C, p, weighting, pred_stride, target_stride,
+                         mask_stride, pos_stride, &a, &go))
+    return rc;
+  if (!go) return BSMS_OK;
+  BSMS_REQUIRE(sums && (a.pieces == 0 || work), BSMS_E_INVALID_ARG, "edge_diff_sums: null argument");
+  const int ncol = 1 + 2 * int(C);
+  // the finishing kernel runs one thread per output element in one dispatch
+  BSMS_REQUIRE(S <= (int64_t(1) << 30) / ncol, BSMS_E_UNSUPPORTED, "edge_diff_sums: S=%lld segments of %d sums exceed one dispatch", (long long)S, ncol);
+  hipStream_t s = as_stream(stream);
+  double* partials = reinterpret_cast<double*>(work);
+  const int64_t blocks = S * a.pieces;
+  for (int64_t first = 0; first < blocks; first += kMaxBlocksPerLaunch) {
+    a.blk0 = first;
+    const unsigned nb = unsigned(std::min(kMaxBlocksPerLaunch, blocks - first));
+#define BSMS_EDGE_CALL(C_) launch_pieces<C_>(weighting == BSMS_EDGE_QUOTIENT, nb, s, a, partials)
+    BSMS_EDGE_BY_C(int(C), BSMS_EDGE_CALL)
+#undef BSMS_EDGE_CALL
+    BSMS_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_edge_finish, dim3(unsigned(ceil_div(S * ncol, 256))), dim3(256), 0, s, (const double*)partials, S, a.pieces,
+                     ncol, sums);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}
+
+extern "C" int bsms_edge_diff_bwd(const bsms_plan_t* plan, int64_t row0, int64_t seg_rows, const float* pred, const float* target,
+                                  const float* mask, const float* pos, int64_t S, int64_t C, int64_t p, int weighting,
+                                  int64_t pred_stride, int64_t target_stride, int64_t mask_stride, int64_t pos_stride, const double* coef,
+                                  int accumulate, float* grad, int64_t grad_stride, bsms_stream_t stream) {
+  EdgeArgs a;
+  bool go;
+  if (int rc = edge_args("edge_diff_bwd", plan, row0, seg_rows, pred, target, mask, pos, S, C, p, weighting, pred_stride, target_stride,
+                         mask_stride, pos_stride, &a, &go))
+    return rc;
+  if (!go || seg_rows == 0) return BSMS_OK;
+  BSMS_REQUIRE(coef && grad, BSMS_E_INVALID_ARG, "edge_diff_bwd: null argument");
+  BSMS_REQUIRE(grad_stride >= seg_rows, BSMS_E_INVALID_ARG, "edge_diff_bwd: grad_stride=%lld is shorter than a segment (%lld rows)",
+               (long long)grad_stride, (long long)seg_rows);
+  hipStream_t s = as_stream(stream);
+  a.pieces = ceil_div(seg_rows, kBwdThreads);            // blocks per segment: one thread per row
+  const int64_t blocks = S * a.pieces;
+  for (int64_t first = 0; first < blocks; first += kMaxBlocksPerLaunch) {
+    a.blk0 = first;
+    const unsigned nb = unsigned(std::min(kMaxBlocksPerLaunch, blocks - first));
+#define BSMS_EDGE_CALL(C_) launch_bwd<C_>(weighting == BSMS_EDGE_QUOTIENT, nb, s, a, coef, accumulate, grad, grad_stride)
+    BSMS_EDGE_BY_C(int(C), BSMS_EDGE_CALL)
+#undef BSMS_EDGE_CALL
+    BSMS_LAUNCH_CHECK();
+  }
+  return BSMS_OK;
+}

@@ -31,6 +31,24 @@ def error_mean_std(sums, rows_per_segment, relative=True):
     return mean, torch.sqrt(torch.clamp(e2 - mean ** 2, min=0.0))
 
 
+def edge_error_mean_std(sums, relative=True):
+    """(mean [C], std [C]) in fp64 over the samples of `sums` [B, 1+2C] = [ME | DE | TE] (`ops.edge_diff_sums`):
+
+        E[b,c] = sqrt(DE / ME)          divided by sqrt(TE / ME) when `relative`
+
+    the RMS difference of the error field along the mesh edges, against that of the target field.  The standard deviation is the
+    population one, as `error_mean_std` takes it."""
+    sums = sums.to(torch.float64)
+    if sums.dim() != 2 or (sums.shape[1] - 1) % 2 or sums.shape[1] < 3:
+        raise ValueError(f"edge_error_mean_std: sums [B, 1+2C] expected, got {tuple(sums.shape)}")
+    C = (sums.shape[1] - 1) // 2
+    ME, DE, TE = sums[:, :1], sums[:, 1:1 + C], sums[:, 1 + C:]
+    E = torch.sqrt(DE / ME)
+    if relative:
+        E = E / torch.sqrt(TE / ME)
+    return E.mean(0), E.std(0, unbiased=False)
+
+
 def equivariance_error(model, batch, transforms, groups, rows_per_sample=None):
     """How far `model` is from commuting with a change of frame, per channel, as a relative RMS difference (fp64 [C]):
 

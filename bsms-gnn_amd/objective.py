@@ -231,3 +231,112 @@ def masked_loss(pred, tar, mask, objective=None, std=None, node_weights=None):
     else:
         M, SE = channel_sums(pred, tar, mask, node_weights)
     return finish_loss(M, SE, objective, std)[0]
+
+
+# ------------------------------------------------------------------------------------ edge differences
+EDGE_WEIGHTINGS = ("difference", "quotient")   # BSMS_EDGE_DIFFERENCE / BSMS_EDGE_QUOTIENT
+
+
+def _edge_operands(pred, tar, mask, pos, weighting):
+    """pred / tar as [S, N, C], mask as [S or 1, N], pos as [S or 1, N, p] or None -- views, nothing is copied."""
+    if weighting not in EDGE_WEIGHTINGS:
+        raise ValueError(f"edge differences: weighting must be one of {list(EDGE_WEIGHTINGS)}, got {weighting!r}")
+    if pred.dim() not in (2, 3) or tar.shape != pred.shape:
+        raise ValueError(f"edge differences: pred and tar [B, N, C] or [R, C] expected, got {tuple(pred.shape)} and {tuple(tar.shape)}")
+    N, C = int(pred.shape[-2]), int(pred.shape[-1])
+    if mask.numel() % max(N, 1) or (N and mask.numel() // N not in (1, pred.numel() // max(N * C, 1))):
+        raise ValueError(f"edge differences: a mask of shape {tuple(mask.shape)} does not cover {tuple(pred.shape[:-1])} nodes")
+    if weighting == "quotient":
+        if pos is None:
+            raise ValueError('edge differences: weighting="quotient" needs pos')
+        if pos.dim() not in (2, 3) or int(pos.shape[-2]) != N or (pos.dim() == 3 and (pred.dim() != 3 or pos.shape[0] != pred.shape[0])):
+            raise ValueError(f"edge differences: pos [N, p] or [B, N, p] expected for pred {tuple(pred.shape)}, got {tuple(pos.shape)}")
+        pos = pos.reshape(-1, N, pos.shape[-1])
+    else:
+        pos = None
+    return pred.reshape(-1, N, C), tar.reshape(-1, N, C), mask.reshape(-1, N), pos
+
+
+def edge_difference_sums(pred, tar, mask, g, pos=None, weighting="difference"):
+    """The edge-difference sums in torch, on any device: fp64 [S, 1+2C] = [ME | DE | TE] per sample -- the row of bsms_edge_diff_sums,
+    differentiable in `pred` (and in `tar` and `pos`).  `pred` / `tar` are [B, N, C] with ONE edge list `g` [2, E] shared by the
+    samples, or [R, C] (one segment: the rows of a variable-mesh union with its edge list); `mask` covers the nodes of every sample or
+    of one, shared; `pos` is [N, p] or [B, N, p].  Over the directed edges e = (g[0, e] -> g[1, e]) -- a mesh edge listed in both
+    directions counts twice --
+
+        mu_e = m_i m_j        w_e = 1 ("difference")   or   1 / |x_i - x_j|^2 ("quotient"; an edge of length 0 has mu_e = w_e = 0)
+        ME = sum mu_e         DE_c = sum mu_e w_e (d_ic - d_jc)^2         TE_c = sum mu_e w_e (t_ic - t_jc)^2
+
+    with d = pred - tar rounded once in the tensors' own precision (fp32 tensors: the one fp32 rounding of the kernel) and every
+    product and sum after it in fp64."""
+    pred, tar, mask, pos = _edge_operands(pred, tar, mask, pos, weighting)
+    i, j = g[0].long(), g[1].long()
+    d, t, m = (pred - tar).double(), tar.double(), mask.double()
+    mu = m[:, i] * m[:, j]                                              # [S or 1, E]
+    w = torch.ones_like(mu)
+    if pos is not None:
+        x = pos.double()
+        l2 = ((x[:, i] - x[:, j]) ** 2).sum(-1)
+        flat = l2 == 0
+        w = torch.where(flat, torch.zeros_like(l2), 1.0 / torch.where(flat, torch.ones_like(l2), l2))
+        mu = torch.where(flat, torch.zeros_like(l2), mu)                # broadcasts a shared mask / shared positions
+    mw = (mu * w).unsqueeze(-1)
+    DE = (mw * (d[:, i] - d[:, j]) ** 2).sum(1)
+    TE = (mw * (t[:, i] - t[:, j]) ** 2).sum(1)
+    ME = mu.sum(1, keepdim=True).expand(DE.shape[0], 1)
+    return torch.cat([ME, DE, TE], dim=1)
+
+
+class _EdgeDiffSums(torch.autograd.Function):
+    """bsms_edge_diff_sums forward, bsms_edge_diff_bwd backward: the gradient of sum_{s,c} G[s, 1 + c] DE[s, c] with respect to pred
+    (G the incoming gradient of the sums, already on the device: nothing is read back).  ME and TE do not depend on pred."""
+
+    @staticmethod
+    def forward(ctx, pred, tar, mask, pos, plan, weighting):
+        from . import ops
+        ctx.save_for_backward(pred, tar, mask, *(() if pos is None else (pos,)))
+        ctx.plan, ctx.weighting = plan, weighting
+        return ops.edge_diff_sums(pred, tar, mask, plan, pos=pos, weighting=weighting, row0=0, seg_rows=pred.shape[1])
+
+    @staticmethod
+    def backward(ctx, grad_sums):
+        from . import ops
+        pred, tar, mask, *rest = ctx.saved_tensors
+        C = pred.shape[-1]
+        coef = grad_sums[:, 1:1 + C].to(torch.float64).contiguous()
+        grad = ops.edge_diff_bwd(pred, tar, mask, ctx.plan, coef, pos=rest[0] if rest else None, weighting=ctx.weighting, row0=0,
+                                 seg_rows=pred.shape[1])
+        return grad, None, None, None, None, None
+
+
+def edge_difference_loss(pred, tar, mask, g, pos=None, *, weighting="difference", space="physical", kind="mse", channel_weights=None,
+                         std=None):
+    """The edge-difference (discrete H1) loss term, an fp32 scalar:
+
+        H = sum_c a_c DE_c / (ME C)          term = H (kind = "mse")   or   sqrt(H) (kind = "rmse")
+
+    with DE and ME the sums of `edge_difference_sums` over all samples and a_c exactly the coefficients of `Objective`: w_c in the
+    physical space, w_c / std_c^2 in the normalized one (`std`: the target normaliser's `std_with_epsilon()`).  Shapes as
+    `edge_difference_sums` takes them.  On GPU tensors the sums are bsms_edge_diff_sums and the gradient with respect to `pred` is
+    bsms_edge_diff_bwd, with the coefficients k_c = g_out a_c / (ME C) ("mse") or g_out a_c / (2 term ME C) ("rmse") formed by fp64
+    torch ops on the device; `tar`, `mask` and `pos` get no gradient there.  On CPU tensors it is the torch definition.  Use it next
+    to the training objective: `loss = trainer.get_loss(data) + lam * edge_difference_loss(pred, tar, mask, g)`."""
+    if kind not in KINDS:
+        raise ValueError(f"edge_difference_loss: kind must be one of {sorted(KINDS)}, got {kind!r}")
+    objective = Objective(space, kind, channel_weights).bind(pred.shape[-1])
+    for what, t in (("tar", tar), ("mask", mask), ("g", g)) + ((("pos", pos),) if pos is not None and weighting == "quotient" else ()):
+        if t.device != pred.device:
+            raise RuntimeError(f"edge_difference_loss: {what} lives on {t.device}, pred on {pred.device}")
+    C = int(pred.shape[-1])
+    if pred.is_cuda:
+        from .graph import plan_for
+        p3, t3, m2, x3 = _edge_operands(pred, tar, mask, pos, weighting)
+        m2 = m2.contiguous()
+        sums = _EdgeDiffSums.apply(p3.contiguous(), t3.contiguous(), m2 if m2.shape[0] == p3.shape[0] else m2[0],
+                                   None if x3 is None else (x3.contiguous() if x3.shape[0] == p3.shape[0] else x3[0].contiguous()),
+                                   plan_for(g, p3.shape[1]), weighting)
+    else:
+        sums = edge_difference_sums(pred, tar, mask, g, pos, weighting)
+    a = objective.coefficients(std, C, pred.device)
+    H = (a * sums[:, 1:1 + C].sum(0)).sum() / (sums[:, 0].sum() * C)
+    return (torch.sqrt(H) if kind == "rmse" else H).float()

@@ -94,12 +94,12 @@ def _grad_targets_by_mlp(params, needs, group):
 
 
 # --------------------------------------------------------------------------------- evaluation sums
-def _segment_view(t, what, S, seg_rows, width, stride):
+def _segment_view(t, what, S, seg_rows, width, stride, who="error_sums"):
     """(tensor whose data_ptr is row 0 of segment 0, rows between segments) of a float32 device tensor read as S segments of
     [seg_rows, width]: contiguous, or [S, seg_rows(, width)] with dense segments and any row-aligned step between them (a
     column block of a wider tensor; a stride-0 expand).  `stride` overrides the step.  The span is checked against the storage."""
     if not t.is_cuda or t.dtype != torch.float32:
-        raise _abi.BsmsError(f"error_sums: {what} must be a float32 GPU tensor (got {t.dtype} on {t.device}); there is no CPU fallback")
+        raise _abi.BsmsError(f"{who}: {what} must be a float32 GPU tensor (got {t.dtype} on {t.device}); there is no CPU fallback")
     if stride is None:
         if t.numel() == S * seg_rows * width and t.is_contiguous():
             stride = seg_rows
@@ -108,15 +108,15 @@ def _segment_view(t, what, S, seg_rows, width, stride):
         else:
             seg = t[0] if t.dim() >= 2 and t.shape[0] == S else None
             if seg is None or seg.numel() != seg_rows * width or not seg.is_contiguous() or t.stride(0) % width:
-                raise ValueError(f"error_sums: {what} of shape {tuple(t.shape)} / strides {tuple(t.stride())} is not {S} dense segments of "
+                raise ValueError(f"{who}: {what} of shape {tuple(t.shape)} / strides {tuple(t.stride())} is not {S} dense segments of "
                                  f"[{seg_rows}, {width}] a whole number of rows apart")
             stride = t.stride(0) // width
     stride = int(stride)
     if stride < 0:
-        raise ValueError(f"error_sums: {what}_stride = {stride}")
+        raise ValueError(f"{who}: {what}_stride = {stride}")
     room = t.untyped_storage().nbytes() // 4 - t.storage_offset()
     if seg_rows and ((S - 1) * stride + seg_rows) * width > room:
-        raise ValueError(f"error_sums: {what}: {S} segments of {seg_rows} rows, {stride} rows apart, reach past the tensor's storage")
+        raise ValueError(f"{who}: {what}: {S} segments of {seg_rows} rows, {stride} rows apart, reach past the tensor's storage")
     return t, stride
 
 
@@ -153,6 +153,90 @@ def error_sums(pred, target, mask, seg_rows, *, pred_stride=None, target_stride=
     _abi.check(L.bsms_error_sums(pred.data_ptr(), target.data_ptr(), mask.data_ptr(), S, seg_rows, C, ps, ts, ms, sums.data_ptr(),
                                  work.data_ptr(), _stream()), "bsms_error_sums")
     return sums
+
+
+_EDGE_WEIGHTINGS = {"difference": 0, "quotient": 1}     # BSMS_EDGE_DIFFERENCE / BSMS_EDGE_QUOTIENT
+
+
+def _edge_diff_args(who, pred, target, mask, plan, pos, weighting, row0, seg_rows, pred_stride, target_stride, mask_stride, pos_stride):
+    """The arguments bsms_edge_diff_sums and bsms_edge_diff_bwd share, checked: (S, C, seg_rows, leading argument tuple)."""
+    if weighting not in _EDGE_WEIGHTINGS:
+        raise ValueError(f"{who}: weighting must be one of {sorted(_EDGE_WEIGHTINGS)}, got {weighting!r}")
+    quot = weighting == "quotient"
+    if quot and pos is None:
+        raise ValueError(f'{who}: weighting="quotient" needs pos')
+    for what, t in (("pred", pred), ("target", target), ("mask", mask)) + ((("pos", pos),) if quot else ()):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
+            raise _abi.BsmsError(f"{who}: {what} must be a float32 GPU tensor (got {getattr(t, 'dtype', type(t).__name__)} on "
+                                 f"{getattr(t, 'device', 'the host')}); there is no CPU fallback")
+        if t.device != pred.device:
+            raise _abi.BsmsError(f"{who}: {what} lives on {t.device}, pred on {pred.device}")
+    if not isinstance(plan, LevelPlan):
+        raise TypeError(f"{who}: plan must be a LevelPlan (graph.plan_for(g, N)), got {type(plan).__name__}")
+    if plan.device.type != "cuda" or (plan.device.index is not None and plan.device.index != pred.device.index):
+        raise _abi.BsmsError(f"{who}: the plan lives on {plan.device}, pred on {pred.device}")
+    row0 = int(row0)
+    seg_rows = plan.N - row0 if seg_rows is None else int(seg_rows)
+    if row0 < 0 or seg_rows < 0 or row0 + seg_rows > plan.N:
+        raise ValueError(f"{who}: rows [{row0}, {row0 + seg_rows}) are not a window of a plan of {plan.N} rows")
+    C = int(pred.shape[-1])
+    if pred.dim() == 3:
+        S = int(pred.shape[0])
+    elif seg_rows == 0 or pred.numel() % (seg_rows * C):
+        raise ValueError(f"{who}: pred of shape {tuple(pred.shape)} does not say how many segments of {seg_rows} rows it holds")
+    else:
+        S = pred.numel() // (seg_rows * C)
+    pred, ps = _segment_view(pred, "pred", S, seg_rows, C, pred_stride, who)
+    target, ts = _segment_view(target, "target", S, seg_rows, C, target_stride, who)
+    mask, ms = _segment_view(mask, "mask", S, seg_rows, 1, mask_stride, who)
+    p, pp, xs = 0, None, 0
+    if quot:
+        p = int(pos.shape[-1])
+        pos, xs = _segment_view(pos, "pos", S, seg_rows, p, pos_stride, who)
+        pp = pos.data_ptr()
+    return S, C, seg_rows, (plan.handle, row0, seg_rows, pred.data_ptr(), target.data_ptr(), mask.data_ptr(), pp, S, C, p,
+                            _EDGE_WEIGHTINGS[weighting], ps, ts, ms, xs)
+
+
+def edge_diff_sums(pred, target, mask, plan, *, pos=None, weighting="difference", row0=0, seg_rows=None, pred_stride=None,
+                   target_stride=None, mask_stride=None, pos_stride=None):
+    """Edge-difference (discrete H1) sums of S segments (bsms_edge_diff_sums): fp64 [S, 1+2C] = [ME | DE | TE] per
+    segment over the directed edges of `plan`'s rows [row0, row0 + seg_rows) (default: all rows from row0 on) with both ends in that
+    window.  `plan` is a `LevelPlan` (`graph.plan_for(g, N)`); the tensors hold the segments' OWN rows -- [S, seg_rows, C] / [S,
+    seg_rows(, 1)] / [S, seg_rows, p], or one segment shared by all -- as views any whole number of rows apart, exactly as
+    `error_sums` takes them.  `pos` is read with weighting="quotient" only.  One launch pair on the current stream; nothing is copied
+    and nothing synchronises."""
+    S, C, seg_rows, args = _edge_diff_args("edge_diff_sums", pred, target, mask, plan, pos, weighting, row0, seg_rows, pred_stride,
+                                           target_stride, mask_stride, pos_stride)
+    L = _abi.lib()
+    sums = torch.empty(S, 1 + 2 * C, device=pred.device, dtype=torch.float64)
+    work = _workspace(pred.device, L.bsms_edge_diff_work_bytes(S, seg_rows))
+    _abi.check(L.bsms_edge_diff_sums(*args, sums.data_ptr(), work.data_ptr(), _stream()), "bsms_edge_diff_sums")
+    return sums
+
+
+def edge_diff_bwd(pred, target, mask, plan, coef, *, pos=None, weighting="difference", row0=0, seg_rows=None, pred_stride=None,
+                  target_stride=None, mask_stride=None, pos_stride=None, out=None):
+    """The adjoint of `edge_diff_sums` (bsms_edge_diff_bwd): the gradient of sum_c coef[s, c] DE[s, c] with respect to `pred`,
+    float32 [S, seg_rows, C].  `coef` is fp64 [S, C] (or [C], shared) on the device.  `out` (contiguous [S, seg_rows, C]): the
+    gradient is ADDED to it in fp32 instead of being stored into a fresh tensor."""
+    S, C, seg_rows, args = _edge_diff_args("edge_diff_bwd", pred, target, mask, plan, pos, weighting, row0, seg_rows, pred_stride,
+                                           target_stride, mask_stride, pos_stride)
+    if not torch.is_tensor(coef) or coef.device != pred.device or coef.dtype != torch.float64:
+        raise _abi.BsmsError(f"edge_diff_bwd: coef must be a float64 tensor on {pred.device}")
+    if tuple(coef.shape) == (C,):
+        coef = coef.expand(S, C)
+    if tuple(coef.shape) != (S, C):
+        raise ValueError(f"edge_diff_bwd: coef of shape {tuple(coef.shape)} is neither [{C}] nor [{S}, {C}]")
+    coef = coef.contiguous()
+    if out is None:
+        grad, accumulate = torch.empty(S, seg_rows, C, device=pred.device, dtype=torch.float32), 0
+    else:
+        if out.dtype != torch.float32 or out.device != pred.device or out.numel() != S * seg_rows * C or not out.is_contiguous():
+            raise ValueError(f"edge_diff_bwd: out must be a contiguous float32 [{S}, {seg_rows}, {C}] on {pred.device}")
+        grad, accumulate = out, 1
+    _abi.check(_abi.lib().bsms_edge_diff_bwd(*args, coef.data_ptr(), accumulate, grad.data_ptr(), seg_rows, _stream()), "bsms_edge_diff_bwd")
+    return grad
 
 
 # --------------------------------------------------------------------------------- tensor prims

@@ -219,7 +219,8 @@ class RolloutErrors:
 
 
 @torch.no_grad()
-def rollout_bank(trainer, bank, indices=None, batch=8, use_graph=False, errors=None, keep_results=False):
+def rollout_bank(trainer, bank, indices=None, batch=8, use_graph=False, errors=None, keep_results=False, edge_errors=None,
+                 edge_weighting="difference"):
     """Rollout evaluation of the trajectories of a `databank.TrajectoryBank`, up to `batch` of them advanced together, with
     the error statistics taken on the device (`ops.error_sums` -> `RolloutErrors.add_sums`).  Returns the `RolloutErrors`;
     with `keep_results` also the list of [T-1, N_i, C] device results in `indices` order (views of their group's tensor).
@@ -232,6 +233,12 @@ def rollout_bank(trainer, bank, indices=None, batch=8, use_graph=False, errors=N
     error_sums launch with a segment per time step then reads strided views only: its column / row block of `results`, the
     bank's resident state[1:] as the target, and its frame-0 node mask shared by all steps.  The accumulators are fed in
     `indices` order whatever the grouping.
+
+    `edge_errors` (a second `RolloutErrors`): per trajectory one more launch pair, `ops.edge_diff_sums` over the same
+    strided views on the group's level-0 plan (variable meshes: the trajectory's window of the union, `row0` its first row), with
+    the positions copied contiguous once per group for `edge_weighting="quotient"`.  Its [T-1, 1+2C] sums [ME | DE | TE] are fed as
+    [ME | DE | 0 | TE] to `edge_errors.add_sums`, whose three accumulators thereby hold the edge-difference RMSEs sqrt(DE / ME)
+    overall, per channel and per time step.  Without the argument the function makes exactly the calls it made before.
 
     Not here: data-parallel sharding (`rollout_dataset` keeps that role), the sums fused into the step's epilogue, and
     groups of unequal T."""
@@ -259,16 +266,25 @@ def rollout_bank(trainer, bank, indices=None, batch=8, use_graph=False, errors=N
         stepper = _Stepper(model, ic, mask, m_gs, m_ids, C, use_graph and ic.is_cuda)
         for ti in range(T - 1):
             results[ti] = stepper.step()
+        if edge_errors is not None:
+            from .graph import plan_for
+            from .ops import edge_diff_sums
+            plan = plan_for(m_gs[0][0], ic.shape[1])
+            pos = ic[..., C:-1].contiguous() if edge_weighting == "quotient" else None
         row0 = 0
         for b, i in enumerate(group):
             state = bank.resident(i)[0]
             n = state.shape[1]
             if consistent:
-                mine, node_mask = results[:, b], mask[b, :, 0]
+                mine, node_mask, first, where = results[:, b], mask[b, :, 0], 0, b
             else:
-                mine, node_mask = results[:, 0, row0:row0 + n], mask[0, row0:row0 + n, 0]
+                mine, node_mask, first, where = results[:, 0, row0:row0 + n], mask[0, row0:row0 + n, 0], row0, 0
                 row0 += n
             errors.add_sums(error_sums(mine, state[1:], node_mask, n, mask_stride=0))
+            if edge_errors is not None:
+                es = edge_diff_sums(mine, state[1:], node_mask, plan, pos=None if pos is None else pos[where, first:first + n],
+                                    weighting=edge_weighting, row0=first, seg_rows=n, mask_stride=0, pos_stride=0)
+                edge_errors.add_sums(torch.cat([es[:, :1 + C], torch.zeros_like(es[:, 1:1 + C]), es[:, 1 + C:]], dim=1))
             if keep_results:
                 kept.append(mine)
     return (errors, kept) if keep_results else errors

@@ -470,6 +470,31 @@ class Trainer:
             out = torch.stack([mean, std]).float().cpu().numpy()
         return out[0], out[1]
 
+    def get_edge_error(self, data, relative=True, weighting="difference", ema=False):
+        """(mean, std) per channel as float32 NumPy arrays [C] of the EDGE-DIFFERENCE error: per sample the RMS
+        difference of the error field along the mesh edges, E = sqrt(DE / ME), divided by that of the target field, sqrt(TE / ME),
+        when `relative`; `weighting="quotient"` divides every squared difference by the squared edge length (the position columns
+        of node_in, copied contiguous once).  Mean and population standard deviation run over the batch's samples; a variable-mesh
+        batch is ONE sample of sum N rows, as in `get_error`.  One bsms_edge_diff_sums launch pair on the level-0 plan; 2C numbers
+        are copied back."""
+        from .eval import edge_error_mean_std
+        from .graph import plan_for
+        from .ops import edge_diff_sums
+        data = self.move_to_device(data)
+        with torch.no_grad():
+            pred = self.get_pred(data, ema)
+            tar, mask = self.get_label_mask(data)
+            if self.model_cfg.consistent_mesh:
+                node_in, g = data[0], data[3][0][0]
+            else:
+                node_in, g = data[0].x, data[0].edge_index
+            rows, C = pred.shape[-2], pred.shape[-1]
+            pos = node_in[..., C:-1].reshape(-1, rows, node_in.shape[-1] - C - 1).contiguous() if weighting == "quotient" else None
+            sums = edge_diff_sums(pred.reshape(-1, rows, C), tar.reshape(-1, rows, C), mask.reshape(-1, rows), plan_for(g, rows), pos=pos,
+                                  weighting=weighting)
+            out = torch.stack(edge_error_mean_std(sums, relative)).float().cpu().numpy()
+        return out[0], out[1]
+
     def iter(self, data, node_weights=None):
         """One training iteration (trainer.py:134-156): statistics only during warm-up, otherwise
         fwd + loss + bwd (+ gradient all-reduce) + clip + AdamW + LR schedule.  With model_cfg.unroll_steps = K > 1 `data` is

@@ -618,6 +618,49 @@ int bsms_robust_sums(const float* pred, const float* target, const float* mask, 
                      const double* std_eps /* nullable */, const double* delta /* nullable with BSMS_ROBUST_MAE */, int space,
                      int rkind, double* sums, int64_t sums_stride, void* work, bsms_stream_t stream);
 
+/* ---------------------------------------------------------------- evaluation: edge-difference (discrete H1) sums ---
+ * What bsms_error_sums is for the values of a field, these two entries are for its differences along the mesh edges (DESIGN.md
+ * 4.21).  A segment is seg_rows consecutive rows of a field; its graph is the plan's rows [row0, row0 + seg_rows) with the directed
+ * edges e = (i_e -> j_e) of the plan whose BOTH ends lie in that window (an edge with an end outside is skipped: not read, not
+ * counted, in the sums and in both halves of the backward -- one mesh of a block-diagonal union is summed through the union's
+ * plan).  A mesh edge listed in both directions counts twice.  With d = fl32(pred - target) (ONE fp32 rounding, as in
+ * bsms_error_sums), t = target, m = mask, every product and sum in fp64:
+ *   l2_e  = sum_k (double(pos[i_e,k]) - double(pos[j_e,k]))^2          mu_e = double(m[i_e]) * double(m[j_e])
+ *   w_e   = 1 (BSMS_EDGE_DIFFERENCE: pos is not read and may be NULL, p is ignored)
+ *         | 1 / l2_e (BSMS_EDGE_QUOTIENT; an edge with l2_e == 0 has mu_e = w_e = 0: it adds nothing to any field)
+ *   sums[s, :] = [ ME | DE[0..C) | TE[0..C) ]   (DEVICE double, row length 1 + 2C)
+ *     ME = sum_e mu_e     DE[c] = sum_e mu_e w_e (d[i_e,c] - d[j_e,c])^2     TE[c] = sum_e mu_e w_e (t[i_e,c] - t[j_e,c])^2
+ * The data pointers address the segment's OWN first row (plan row n is local row n - row0): segment s reads pred + s * pred_stride
+ * * C, target + s * target_stride * C, mask + s * mask_stride and pos + s * pos_stride * p; strides count rows, 0 shares one array
+ * between all segments; rows inside a segment are contiguous ([seg_rows, C] / [seg_rows] / [seg_rows, p]).
+ * bsms_edge_diff_bwd is the exact adjoint of sum_c k_c DE[c] with respect to pred, k = coef (DEVICE double [S, C]):
+ *   grad[s, r, c] = fl32( 2 k_c * [ sum_{e: j_e = r} mu_e w_e (d[r,c] - d[i_e,c]) + sum_{e: i_e = r} mu_e w_e (d[r,c] - d[j_e,c]) ] )
+ * stored (accumulate == 0) or added in fp32 to what grad holds (accumulate != 0); segment s writes grad + s * grad_stride * C,
+ * grad_stride >= seg_rows rows.
+ * Limits: C in 1..8, weighting 0 or 1, p in 1..3 with BSMS_EDGE_QUOTIENT (BSMS_E_UNSUPPORTED otherwise, all three checked before any
+ * pointer is looked at); S >= 0, seg_rows in 0..2^31-1, row0 >= 0, no negative stride (BSMS_E_INVALID_ARG); S == 0 returns BSMS_OK
+ * and touches nothing; then a null plan (BSMS_E_INVALID_ARG), row0 + seg_rows beyond the plan's rows (BSMS_E_SHAPE), null pointers
+ * with work to do (BSMS_E_INVALID_ARG).  seg_rows == 0 writes rows of zeros (sums) and writes nothing (bwd).
+ * The calls allocate nothing, do not synchronise and read nothing back: they can be captured into a HIP graph.  `work` holds
+ * bsms_edge_diff_work_bytes(S, seg_rows) bytes (non-decreasing in both arguments).
+ * DETERMINISM: no atomics.  Sums: row r owns its INCOMING edges and adds them one after the other in the plan's CSR order (the
+ * caller's edge order); the rows are cut into pieces of 1024 counted from the segment's own first row, a piece is reduced with
+ * per-thread rows in ascending order and a fixed tree, and a second kernel adds the pieces in index order -- a segment's row is
+ * bit-identical from run to run, whatever S, the strides or its neighbours in the launch, and whether it is summed through its own
+ * plan or as a window of a union.  Backward: one thread owns grad[s, r, :]; per element ONE fp64 accumulator, incoming edges in CSR
+ * order first, then outgoing edges in transpose order, times 2 * coef[s, c] in fp64, ONE rounding to fp32. */
+enum { BSMS_EDGE_DIFFERENCE = 0, BSMS_EDGE_QUOTIENT = 1 };   /* weighting */
+size_t bsms_edge_diff_work_bytes(int64_t S, int64_t seg_rows);
+int bsms_edge_diff_sums(const bsms_plan_t* plan, int64_t row0, int64_t seg_rows, const float* pred, const float* target,
+                        const float* mask, const float* pos /* nullable with BSMS_EDGE_DIFFERENCE */, int64_t S, int64_t C, int64_t p,
+                        int weighting, int64_t pred_stride, int64_t target_stride, int64_t mask_stride, int64_t pos_stride,
+                        double* sums /* [S, 1 + 2C] */, void* work, bsms_stream_t stream);
+int bsms_edge_diff_bwd(const bsms_plan_t* plan, int64_t row0, int64_t seg_rows, const float* pred, const float* target,
+                       const float* mask, const float* pos /* nullable with BSMS_EDGE_DIFFERENCE */, int64_t S, int64_t C, int64_t p,
+                       int weighting, int64_t pred_stride, int64_t target_stride, int64_t mask_stride, int64_t pos_stride,
+                       const double* coef /* DEVICE [S, C] */, int accumulate, float* grad /* [S, seg_rows, C] */, int64_t grad_stride,
+                       bsms_stream_t stream);
+
 /* ---------------------------------------------------------------- batch assembly from resident trajectories ---
  * The level-0 node tensors of a batch (datasets/base.py:238-289, `proc_data`, plus the collate) built by ONE launch from
  * trajectories that live in HBM.  `samples` is a HOST table; sample s contributes n rows, rows of consecutive samples
