@@ -149,6 +149,17 @@ SIGNATURES = {
 }
 
 
+# the companion library libbsms_hip_ext.so: name -> (restype, argtypes); one entry per declaration in include/bsms_hip_ext.h
+EXT_LIB_PATH = os.path.join(_HERE, "libbsms_hip_ext.so")
+EXT_SIGNATURES = {
+    "bsms_edge_diff_fold": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p]),
+    "bsms_sim_edge_objective_bwd": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                            C.c_double, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
+}
+
+
 class WgradJob(C.Structure):
     """bsms_wgrad_job (include/bsms_hip.h)."""
     _fields_ = [("G", c_void_p), ("A", c_void_p), ("dW", c_void_p), ("db", c_void_p), ("R", c_i64),
@@ -183,6 +194,25 @@ def lib():
             fn.restype, fn.argtypes = res, args
         _lib = handle
     return _lib
+
+
+_ext = None
+
+
+def ext():
+    """Load the companion library (once), behind libbsms_hip.so, which it links against.  Raises if it has not been built."""
+    global _ext
+    if _ext is None:
+        lib()
+        if not os.path.exists(EXT_LIB_PATH):
+            raise BsmsError(f"{EXT_LIB_PATH} not found: build it with `python bsms-gnn_amd/build.py` (or __graft_entry__.build()); "
+                            "there is no CPU/PyTorch fallback")
+        handle = C.CDLL(EXT_LIB_PATH)
+        for name, (res, args) in EXT_SIGNATURES.items():
+            fn = getattr(handle, name)  # AttributeError if the symbol is missing
+            fn.restype, fn.argtypes = res, args
+        _ext = handle
+    return _ext
 
 
 def check(rc, what):

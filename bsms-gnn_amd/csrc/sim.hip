@@ -8,6 +8,7 @@
 //   loss         sqrt( sum(se * mask) / sum(mask) / C )                                                 (trainer.py:96-97)
 // This file is compiled with -ffp-contract=off (build.py): a fused multiply-add would change the fp64 roundings.
 #include "common.h"
+#include "objective_row.h"
 
 #pragma clang fp contract(off)
 
@@ -282,7 +283,8 @@ namespace {
 // k_sim_unroll_bwd for the family of objectives (include/bsms_hip.h: bsms_sim_objective_bwd).  `sums` = [M | SE[0..C)] in fp64
 // (bsms_error_sums); every thread forms the C per-channel coefficients G * a_c from it in fp64 and rounds each to fp32 once.
 // The carry and the way out through the de-normalisation are those of k_sim_unroll_bwd, op for op.  No guard for M == 0 or
-// loss == 0, as in k_sim_loss_bwd: the non-finite coefficient reaches the output.
+// loss == 0, as in k_sim_loss_bwd: the non-finite coefficient reaches the output.  The head (coefficients) and the tail (step weight, carry,
+// way out) of a row live in objective_row.h, shared with the edge objective's backward (ext/edge_objective.hip).
 // kWeighted (bsms_sim_objective_bwd_w): row r's loss gradient carries mu = m * row_weights[r % period], ONE fp32 product formed first,
 // so (d * mu) * coef is the unweighted (d * m) * coef whenever the weight is 1.  The mask of the carry and of the way out stays m.
 template <bool kWeighted>
@@ -299,33 +301,24 @@ __device__ __forceinline__ void sim_objective_bwd_row(const float* pred, const f
   double sd[kMaxC], a[kMaxC];
   double Q = 0.0;
   for (int c = 0; c < C; ++c) {
-    sd[c] = std_eps(mean[c], meansq[c], e);
-    const double wc = weights ? weights[c] : 1.0;
-    a[c] = normalized ? wc / (sd[c] * sd[c]) : wc;
-    const double term = a[c] * sums[1 + c] / MC;
-    if (r == 0 && chan_out) chan_out[c] = float(term);
-    Q += term;
+    const ObjectiveChannel ch = objective_channel(c, mean, meansq, e, sums, weights, normalized, MC);
+    sd[c] = ch.sd;
+    a[c] = ch.a;
+    if (r == 0 && chan_out) chan_out[c] = float(ch.term);
+    Q += ch.term;
   }
-  const double loss = rmse ? sqrt(Q) : Q;
+  const double loss = objective_loss(Q, rmse);
   if (r == 0 && loss_out) *loss_out = float(loss);
   if (r >= R) return;
-  const double G = rmse ? 1.0 / (loss * MC) : 2.0 / MC;
+  const double G = objective_scale(loss, MC, rmse);
   const float m = mask[r];
   const float mu = kWeighted ? m * row_weights[r % weight_period] : m;
   const bool carried = g_pred_next != nullptr && m != 0.f;
   const double ie = g_pred_next ? *in_eps : 0.0;
   for (int c = 0; c < C; ++c) {
     const float coef = float(G * a[c]);
-    float gp = (pred[r * C + c] - target[r * C + c]) * mu * coef;
-    gp = w * gp;
-    if (carried) {
-      const float through_norm = float(double(g_norm_in_next[r * (C + 1) + c]) / std_eps(in_mean[c], in_meansq[c], ie));
-      const float g_state = g_pred_next[r * C + c] + through_norm;
-      gp = gp + g_state;
-    }
-    if (g_pred) g_pred[r * C + c] = gp;
-    const float gd = gp * m;
-    grad_norm_pred[r * C + c] = float(double(gd) * sd[c]);
+    const float gp = (pred[r * C + c] - target[r * C + c]) * mu * coef;
+    objective_tail(gp, w, m, carried, r, c, C, sd[c], in_mean, in_meansq, ie, g_pred_next, g_norm_in_next, g_pred, grad_norm_pred);
   }
 }
 

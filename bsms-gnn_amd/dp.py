@@ -127,10 +127,11 @@ def global_masked_rmse(pred, tar, mask, group=None):
     return torch.sqrt(s / m / se.shape[-1])
 
 
-def global_masked_loss(pred, tar, mask, objective, std, group=None, node_weights=None):
+def global_masked_loss(pred, tar, mask, objective, std, group=None, node_weights=None, g=None, pos=None):
     """objective.masked_loss under data parallelism: the 1 + C fp64 sums (M, SE_c) -- (M, S_c) of a robust objective -- are all-reduced, the value is identical on all
-    ranks and the gradient flows through the local part only, as in global_masked_rmse (which the default objective is)."""
-    from .objective import channel_sums, finish_loss, robust_sums
+    ranks and the gradient flows through the local part only, as in global_masked_rmse (which the default objective is).  With an
+    edge term (`g`, `pos` as `masked_loss` takes them) the 1 + C sums (ME, DE_c) travel in the same message."""
+    from .objective import _edge_sums_any, channel_sums, edge_term, finish_loss, robust_sums
     if objective is None or objective.is_default:
         return global_masked_rmse(pred, tar, mask, group)
     objective.bind(pred.shape[-1])
@@ -138,11 +139,24 @@ def global_masked_loss(pred, tar, mask, objective, std, group=None, node_weights
         M, SE = robust_sums(pred, tar, mask, objective, std, objective.check_node_weights(node_weights))
     else:
         M, SE = channel_sums(pred, tar, mask, objective.check_node_weights(node_weights))
+    C, ME, DE = SE.shape[0], None, None
+    if objective.has_edge_term:
+        if g is None or (pos is None and objective.edge_weighting == "quotient"):
+            raise ValueError("global_masked_loss: an objective with an edge term needs g (and pos for the quotient weighting)")
+        es = _edge_sums_any(pred, tar, mask, g, pos, objective.edge_weighting)
+        ME, DE = es[:, 0].sum(), es[:, 1:1 + C].sum(0)
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-        tot = torch.cat([M.detach().reshape(1), SE.detach()])
+        tot = torch.cat([M.detach().reshape(1), SE.detach(), *(() if ME is None else (ME.detach().reshape(1), DE.detach()))])
         dist.all_reduce(tot, op=dist.ReduceOp.SUM, group=group)
-        M, SE = tot[0], SE + (tot[1:] - SE.detach())
-    return finish_loss(M, SE, objective, std)[0]
+        M, SE = tot[0], SE + (tot[1:1 + C] - SE.detach())
+        if ME is not None:
+            ME, DE = tot[1 + C], DE + (tot[2 + C:] - DE.detach())
+    if ME is None:
+        return finish_loss(M, SE, objective, std)[0]
+    Q = (objective.coefficients(std, C, SE.device) * SE / (M * C)).sum()              # J as masked_loss forms it: fp64, rounded once
+    L = torch.sqrt(Q) if objective.kind == "rmse" else Q
+    T = edge_term(torch.cat([ME.reshape(1), DE]).reshape(1, 1 + C), objective, std, C)
+    return (L + objective.edge_weight * T).float()
 
 
 class DataParallel:
@@ -152,7 +166,7 @@ class DataParallel:
                  input_grad=False, accumulate=1, reduction="batch", recompute=False):
         """`recompute` (step.FusedStep): activation recomputation in the U-Net's backward -- the same gradients, bit for
         bit, from a fraction of the memory per (unrolled) step.  Only the fused step implements it.
-        `accumulate` > 1, `reduction` (step.FusedStep): every `step_loss_backward` is one micro-batch; the loss sums
+        `accumulate` > 1, `reduction` (step.FusedStep; refused there with an edge term): every `step_loss_backward` is one micro-batch; the loss sums
         are all-reduced per micro-batch, the flat gradient buffer once, after the last fold of the cycle (`fused.ready`).  Only the
         fused step implements it.
         `unroll` > 1: the loss runs over that many autoregressive steps (step.FusedStep; `step_weights` default 1/unroll,
@@ -225,8 +239,12 @@ class DataParallel:
         else:
             if node_weights is not None:
                 node_weights = node_weights.to(pred.device)
+            g = pos = None
+            if self.objective.has_edge_term:          # the level-0 edge list and the position columns of node_in
+                node_in, g = (data[0], data[3][0][0]) if consistent_mesh else (data[0].x, data[0].edge_index)
+                pos = node_in[..., pred.shape[-1]:-1]
             loss = global_masked_loss(pred, tar, mask, self.objective, self.model._targetNormalizer.std_with_epsilon(), self.group,
-                                      node_weights=node_weights)
+                                      node_weights=node_weights, g=g, pos=pos)
         loss.backward()
         self.grads.finish()
         return loss

@@ -22,7 +22,15 @@ The ROBUST kinds replace the square by a function that grows li
     rho(u) = u^2 / 2 if |u| <= delta_c, else delta_c (|u| - delta_c / 2)   kind = "huber"   (`delta` in the units of the space)
     loss   = sum_c w_c S_c / (M C)                                   no square root, and no 1 / std^2 on top of s_c
 
-on bsms_robust_sums + bsms_sim_robust_bwd in the step."""
+on bsms_robust_sums + bsms_sim_robust_bwd in the step.
+
+The EDGE TERM: `edge_weight=lam` adds the edge-difference (discrete H1) term of 4.21 to a "mse" / "rmse" objective.  With
+ME, DE_c the sums of `edge_difference_sums` over ALL samples of the batch (`edge_weighting`: "difference" or "quotient") and a_c the
+coefficients above,
+
+    H = sum_c a_c DE_c / (ME C)        T = H ("mse")  or  sqrt(H) ("rmse")        J = loss + lam T
+
+on bsms_edge_diff_sums + bsms_edge_diff_fold + bsms_sim_edge_objective_bwd in the step."""
 import math
 
 import torch
@@ -34,12 +42,14 @@ ROBUST_KINDS = {"mae": 0, "huber": 1}          # BSMS_ROBUST_MAE / BSMS_ROBUST_H
 
 class Objective:
     """A value: `space`, `kind`, `channel_weights` (a tuple of floats or None), `node_weighted` (bool), `delta` (the Huber threshold:
-    a float, a tuple of one float per channel, or None).  Validated here; the number of weights and of thresholds is checked against
+    a float, a tuple of one float per channel, or None), `edge_weight` (lambda of the edge term: None or a finite float > 0) and
+    `edge_weighting` ("difference" / "quotient").  Validated here; the number of weights and of thresholds is checked against
     a model's `out_dim` by `bind`."""
 
-    __slots__ = ("space", "kind", "channel_weights", "node_weighted", "delta")
+    __slots__ = ("space", "kind", "channel_weights", "node_weighted", "delta", "edge_weight", "edge_weighting")
 
-    def __init__(self, space="physical", kind="rmse", channel_weights=None, node_weighted=False, *, delta=None):
+    def __init__(self, space="physical", kind="rmse", channel_weights=None, node_weighted=False, *, delta=None, edge_weight=None,
+                 edge_weighting="difference"):
         if space not in SPACES:
             raise ValueError(f"Objective: space must be one of {sorted(SPACES)}, got {space!r}")
         if not isinstance(kind, str) or (kind not in KINDS and kind not in ROBUST_KINDS):
@@ -78,6 +88,20 @@ class Objective:
             raise ValueError(f"Objective: node_weighted is a bool, got {node_weighted!r}")
         object.__setattr__(self, "node_weighted", node_weighted)
         object.__setattr__(self, "delta", delta)
+        if edge_weighting not in EDGE_WEIGHTINGS:
+            raise ValueError(f"Objective: edge_weighting must be one of {list(EDGE_WEIGHTINGS)}, got {edge_weighting!r}")
+        if edge_weight is not None:
+            if isinstance(edge_weight, (bool, str)) or not isinstance(edge_weight, (int, float)):
+                raise ValueError(f"Objective: edge_weight must be None or a finite float > 0, got {edge_weight!r}")
+            edge_weight = float(edge_weight)
+            if not (math.isfinite(edge_weight) and edge_weight > 0.0):
+                raise ValueError(f"Objective: edge_weight must be None or a finite float > 0, got {edge_weight}")
+            if kind in ROBUST_KINDS:
+                raise ValueError(f'Objective: the edge term goes with kind "mse" / "rmse", not with the robust kind {kind!r}')
+            if node_weighted:
+                raise ValueError("Objective: the edge term with node_weighted=True is not built (no node-weighted edge sums)")
+        object.__setattr__(self, "edge_weight", edge_weight)
+        object.__setattr__(self, "edge_weighting", edge_weighting)
 
     def __setattr__(self, name, value):
         raise AttributeError("Objective is immutable")
@@ -85,7 +109,13 @@ class Objective:
     @property
     def is_default(self):
         """True exactly for physical / rmse / no weights of either kind: the reference's loss, on the default route."""
-        return self.space == "physical" and self.kind == "rmse" and self.channel_weights is None and not self.node_weighted
+        return (self.space == "physical" and self.kind == "rmse" and self.channel_weights is None and not self.node_weighted
+                and self.edge_weight is None)
+
+    @property
+    def has_edge_term(self):
+        """True with `edge_weight`: J = loss + edge_weight * T."""
+        return self.edge_weight is not None
 
     @property
     def is_robust(self):
@@ -102,14 +132,16 @@ class Objective:
 
     @classmethod
     def from_cfg(cls, cfg):
-        """From the optional `loss_space`, `loss_kind`, `loss_channel_weights`, `loss_node_weights`, `loss_delta` of a model config;
-        absent keys give the default."""
+        """From the optional `loss_space`, `loss_kind`, `loss_channel_weights`, `loss_node_weights`, `loss_delta`, `loss_edge_weight`,
+        `loss_edge_weighting` of a model config; absent keys give the default."""
         w = getattr(cfg, "loss_channel_weights", None)
         nw = getattr(cfg, "loss_node_weights", None)
         dl = getattr(cfg, "loss_delta", None)
         return cls(getattr(cfg, "loss_space", None) or "physical", getattr(cfg, "loss_kind", None) or "rmse",
                    None if w is None else list(w), False if nw is None else nw,
-                   delta=dl if dl is None or isinstance(dl, (int, float)) else list(dl))
+                   delta=dl if dl is None or isinstance(dl, (int, float)) else list(dl),
+                   edge_weight=getattr(cfg, "loss_edge_weight", None),
+                   edge_weighting=getattr(cfg, "loss_edge_weighting", None) or "difference")
 
     def weights_tensor(self, device):
         """fp64 [C] on `device`, or None for unit weights."""
@@ -140,7 +172,7 @@ class Objective:
         return a
 
     def _key(self):
-        return (self.space, self.kind, self.channel_weights, self.node_weighted, self.delta)
+        return (self.space, self.kind, self.channel_weights, self.node_weighted, self.delta, self.edge_weight, self.edge_weighting)
 
     def __eq__(self, other):
         return isinstance(other, Objective) and self._key() == other._key()
@@ -152,6 +184,8 @@ class Objective:
         tail = ", node_weighted=True" if self.node_weighted else ""
         if self.delta is not None:
             tail += f", delta={self.delta}"
+        if self.edge_weight is not None:
+            tail += f", edge_weight={self.edge_weight}, edge_weighting={self.edge_weighting!r}"
         return f"Objective(space={self.space!r}, kind={self.kind!r}, channel_weights={self.channel_weights}{tail})"
 
     def check_node_weights(self, node_weights):
@@ -214,9 +248,21 @@ def finish_loss(M, SE, objective, std):
     return (torch.sqrt(Q) if objective.kind == "rmse" else Q).float(), terms
 
 
-def masked_loss(pred, tar, mask, objective=None, std=None, node_weights=None):
+def edge_term(sums, objective, std, C=None):
+    """T (fp64 scalar) from the rows [ME | DE | ..] of `edge_difference_sums` over all samples: H = sum_c a_c DE_c / (ME C), T = H
+    ("mse") or sqrt(H) ("rmse").  `C`: the channels, for rows that are not [ME | DE | TE] (dp.global_masked_loss: one row [ME | DE])."""
+    C = (sums.shape[-1] - 1) // 2 if C is None else int(C)
+    a = objective.coefficients(std, C, sums.device)
+    H = (a * sums[:, 1:1 + C].sum(0) / (sums[:, 0].sum() * C)).sum()
+    return torch.sqrt(H) if objective.kind == "rmse" else H
+
+
+def masked_loss(pred, tar, mask, objective=None, std=None, node_weights=None, g=None, pos=None):
     """The objective in torch.  `std`: the target normaliser's `std_with_epsilon()` (needed for space = "normalized").  The default
-    objective is `model.masked_rmse`, bit for bit.  `node_weights`: required by a node-weighted objective, refused by any other."""
+    objective is `model.masked_rmse`, bit for bit.  `node_weights`: required by a node-weighted objective, refused by any other.
+    `g` [2, E] (required by an objective with an edge term: the edge list the samples share, or that of a variable-mesh union) and
+    `pos` ([N, p] or [B, N, p]; required by edge_weighting = "quotient"): J = loss + edge_weight * T, formed in fp64 and rounded once;
+    the sums are `edge_difference_sums` on CPU tensors and bsms_edge_diff_sums / bsms_edge_diff_bwd on GPU tensors."""
     if objective is None:
         if node_weights is not None:
             raise ValueError("masked_loss: node_weights need an Objective(node_weighted=True)")
@@ -230,7 +276,17 @@ def masked_loss(pred, tar, mask, objective=None, std=None, node_weights=None):
         M, SE = robust_sums(pred, tar, mask, objective, std, node_weights)
     else:
         M, SE = channel_sums(pred, tar, mask, node_weights)
-    return finish_loss(M, SE, objective, std)[0]
+    if not objective.has_edge_term:
+        return finish_loss(M, SE, objective, std)[0]
+    if g is None:
+        raise ValueError("masked_loss: an objective with an edge term needs g (the [2, E] edge list)")
+    if objective.edge_weighting == "quotient" and pos is None:
+        raise ValueError('masked_loss: edge_weighting="quotient" needs pos')
+    C = SE.shape[0]
+    Q = (objective.coefficients(std, C, SE.device) * SE / (M * C)).sum()
+    L = torch.sqrt(Q) if objective.kind == "rmse" else Q
+    T = edge_term(_edge_sums_any(pred, tar, mask, g, pos, objective.edge_weighting), objective, std)
+    return (L + objective.edge_weight * T).float()
 
 
 # ------------------------------------------------------------------------------------ edge differences
@@ -309,6 +365,18 @@ class _EdgeDiffSums(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
+def _edge_sums_any(pred, tar, mask, g, pos, weighting):
+    """[S, 1+2C] fp64, differentiable in `pred`: the torch definition on CPU tensors, the two kernels on GPU tensors."""
+    if not pred.is_cuda:
+        return edge_difference_sums(pred, tar, mask, g, pos, weighting)
+    from .graph import plan_for
+    p3, t3, m2, x3 = _edge_operands(pred, tar, mask, pos, weighting)
+    m2 = m2.contiguous()
+    return _EdgeDiffSums.apply(p3.contiguous(), t3.contiguous(), m2 if m2.shape[0] == p3.shape[0] else m2[0],
+                               None if x3 is None else (x3.contiguous() if x3.shape[0] == p3.shape[0] else x3[0].contiguous()),
+                               plan_for(g, p3.shape[1]), weighting)
+
+
 def edge_difference_loss(pred, tar, mask, g, pos=None, *, weighting="difference", space="physical", kind="mse", channel_weights=None,
                          std=None):
     """The edge-difference (discrete H1) loss term, an fp32 scalar:
@@ -328,15 +396,7 @@ def edge_difference_loss(pred, tar, mask, g, pos=None, *, weighting="difference"
         if t.device != pred.device:
             raise RuntimeError(f"edge_difference_loss: {what} lives on {t.device}, pred on {pred.device}")
     C = int(pred.shape[-1])
-    if pred.is_cuda:
-        from .graph import plan_for
-        p3, t3, m2, x3 = _edge_operands(pred, tar, mask, pos, weighting)
-        m2 = m2.contiguous()
-        sums = _EdgeDiffSums.apply(p3.contiguous(), t3.contiguous(), m2 if m2.shape[0] == p3.shape[0] else m2[0],
-                                   None if x3 is None else (x3.contiguous() if x3.shape[0] == p3.shape[0] else x3[0].contiguous()),
-                                   plan_for(g, p3.shape[1]), weighting)
-    else:
-        sums = edge_difference_sums(pred, tar, mask, g, pos, weighting)
+    sums = _edge_sums_any(pred, tar, mask, g, pos, weighting)
     a = objective.coefficients(std, C, pred.device)
     H = (a * sums[:, 1:1 + C].sum(0)).sum() / (sums[:, 0].sum() * C)
     return (torch.sqrt(H) if kind == "rmse" else H).float()

@@ -39,6 +39,10 @@ Frozen parameters: an MLP -- encoder, decoder, a block's node o
 `requires_grad == False` gets NULL entries in the gradient tables; the backward then launches nothing for its weight gradients.
 With nothing trainable (or `param_grad=False`) and `input_grad=True` the backward is data-only.
 
+An objective with an EDGE TERM (`Objective(edge_weight=)`): behind bsms_error_sums every forward runs bsms_edge_diff_sums on
+the level-0 plan and bsms_edge_diff_fold into the tail of the step's fp64 sums row, which widens to [M | SE | AE | TT | ME | DE]; the backward
+starts with bsms_sim_edge_objective_bwd in bsms_sim_objective_bwd's place.  Everything behind the loss gradient is the same step.
+
 `recompute=True`: the U-Net's forward keeps only the inputs of its blocks (the lean `s_proc`, BSMS_FWD_LEAN) and its
 backward rebuilds every block's activations just before it needs them (BSMS_BWD_RECOMPUTE), into two blobs in `work`, which all K steps
 share.  Every loss, prediction and gradient keeps its bits; a backward costs one more U-Net forward; what a step holds per unrolled
@@ -162,9 +166,13 @@ class FusedStep:
             if input_grad:
                 raise ValueError("FusedStep: input_grad=True with accumulate > 1: the static input-gradient buffer carries one call's "
                                  "loss coefficient; use accumulate=1")
+            if self.objective.has_edge_term:
+                raise ValueError("FusedStep: accumulate > 1 with an edge term: the objective has two ratios with different denominators "
+                                 "and bsms_accum_coef folds one; use accumulate=1")
             if unroll > 1 and reduction == "batch" and self.objective.kind == "rmse":
                 raise ValueError("FusedStep: accumulate > 1 with unroll > 1 and an rmse loss has no exact batch gradient (the steps' "
                                  'coefficients scale differently): use reduction="mean" or loss_kind="mse"')
+        self._edge = self.objective.has_edge_term   # J = L + lambda T: the widened sums row and the edge entries
         self._micro = 0                             # micro-batches of the current cycle that have run
         self._acc = None                            # accumulate > 1: dict(running fp64 [K,3], coef fp32 [2], loss fp32 [K]) on the device
         self._gsum = None                           # accumulate > 1 and unroll > 1: where a micro-batch t >= 1 sums its K steps
@@ -307,8 +315,12 @@ class FusedStep:
                  work_dec=u8("work_dec", L.bsms_mlp_work_bytes(R, D, D, C, H)),       # the decoder's weight gradients run under the U-Net's first block
                  in_static=None)
         if self._obj is not None:                     # fp64 [M | SE | AE | TT] of bsms_error_sums, the per-channel terms, its scratch
-            b.update(osums=self._f64("osums", dev, 1, 1 + 3 * C)[0], chan=f("chan", 1, C)[0],
+            b.update(osums=self._f64("osums", dev, 1, self._row(C))[0], chan=f("chan", 1, C)[0],
                      work_obj=u8("work_obj", L.bsms_error_sums_work_bytes(1, R)))
+            if self._edge:                            # the per-sample rows [ME | DE | TE], their scratch, (L, T) of the step
+                h0 = plans[0].handle
+                b.update(esums=self._f64("esums", dev, B, 1 + 2 * C), work_edge=u8("work_edge", L.bsms_edge_diff_work_bytes(B, N)),
+                         parts=f("parts", 2), plan0=h0.value if hasattr(h0, "value") else h0)
             if self._obj_w is None or self._obj_w.device != dev:
                 self._obj_w = self._obj.weights_tensor(dev)
             if self._obj.delta is not None and (self._obj_delta is None or self._obj_delta.device != dev):
@@ -381,6 +393,10 @@ class FusedStep:
             n *= int(d)
         return self._arena.bytes(name, 8 * n, dev).view(torch.float64).view(*shape)
 
+    def _row(self, C):
+        """Doubles in a step's sums row: [M | SE | AE | TT] of bsms_error_sums, and [ME | DE] behind it with an edge term."""
+        return 2 + 4 * C if self._edge else 1 + 3 * C
+
     def _set_node_weights(self, b, w, B, N):
         """Copy this call's node weights into the step's own buffer of R floats: [N] is tiled over the B samples, [B, N]
         and the flat [R] of a block-diagonal batch give a weight per row.  Both kernels then read a weight per row, whatever shape came
@@ -398,7 +414,8 @@ class FusedStep:
 
     def _loss_sums(self, b):
         """What data parallelism all-reduces (SUM) between the forwards and the backwards: the fp32 pairs of the default route, or
-        the fp64 rows of bsms_error_sums (one contiguous message; the backward reads the 1 + C leading doubles of each row)."""
+        the fp64 rows of bsms_error_sums (one contiguous message; the backward reads the 1 + C leading doubles of each row -- and, with an
+        edge term, the 1 + C trailing ones [ME | DE] of the widened row)."""
         if self._obj is None:
             return b["sums_all"] if self.unroll > 1 else b["sums"]
         return b["osums_all"] if self.unroll > 1 else b["osums"]
@@ -449,6 +466,13 @@ class FusedStep:
             return
         ck(L.bsms_error_sums(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), 1, R, C, R, R, R, b["osums"].data_ptr(),
                              b["work_obj"].data_ptr(), s), "bsms_error_sums")
+        if self._edge:                        # B segments of N rows through the level-0 plan (a variable-mesh batch: one, the union's)
+            from .objective import EDGE_WEIGHTINGS
+            o = self._obj
+            ck(L.bsms_edge_diff_sums(b["plan0"], 0, N, b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), b["pos"].data_ptr(), B, C, p,
+                                     EDGE_WEIGHTINGS.index(o.edge_weighting), N, N, N, N, b["esums"].data_ptr(), b["work_edge"].data_ptr(), s),
+               "bsms_edge_diff_sums")
+            ck(_abi.ext().bsms_edge_diff_fold(b["esums"].data_ptr(), B, C, b["osums"][1 + 3 * C:].data_ptr(), s), "bsms_edge_diff_fold")
 
     def _backward(self, b, tar, mask, ews, B, N, events=None, chain=None, tabs=None):
         """`events`: (pointer array, keep-alive) of 2L+1 hipEvent_t for bsms_bsgmp_bwd_ev, or None.
@@ -475,6 +499,17 @@ class FusedStep:
                                      _ptr(self._obj_w), _ptr(self._obj_delta), SPACES[o.space], ROBUST_KINDS[o.kind], c["w"],
                                      _ptr(c["g_pred_next"]), _ptr(c["g_nin_next"]), b["loss"].data_ptr(), b["chan"].data_ptr(),
                                      _ptr(c["g_pred"]), b["g_np"].data_ptr(), s), "bsms_sim_robust_bwd")
+        elif self._obj is not None and self._edge:
+            from .objective import EDGE_WEIGHTINGS, KINDS, SPACES
+            ni, o = m._inputNormalizer, self._obj
+            c = chain or dict(w=1.0, g_pred_next=None, g_nin_next=None, g_pred=None)
+            ck(_abi.ext().bsms_sim_edge_objective_bwd(b["plan0"], N, B, b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), b["pos"].data_ptr(), C, p,
+                                             EDGE_WEIGHTINGS.index(o.edge_weighting), no._E_data.data_ptr(), no._E_data_squared.data_ptr(),
+                                             no.std_eps.data_ptr(), ni._E_data.data_ptr(), ni._E_data_squared.data_ptr(),
+                                             ni.std_eps.data_ptr(), b["osums"].data_ptr(), b["osums"][1 + 3 * C:].data_ptr(), _ptr(self._obj_w),
+                                             SPACES[o.space], KINDS[o.kind], o.edge_weight, c["w"], _ptr(c["g_pred_next"]),
+                                             _ptr(c["g_nin_next"]), b["loss"].data_ptr(), b["parts"].data_ptr(), b["chan"].data_ptr(),
+                                             _ptr(c["g_pred"]), b["g_np"].data_ptr(), s), "bsms_sim_edge_objective_bwd")
         elif self._obj is not None:
             from .objective import KINDS, SPACES
             ni, o = m._inputNormalizer, self._obj
@@ -588,12 +623,15 @@ class FusedStep:
         sums = ar.f32("sums_all", dev, K, 2)              # ONE buffer: the data-parallel all-reduce of the sums is one message
         losses = ar.f32("loss_all", dev, K)
         if self._obj is not None:
-            osums, chans = self._f64("osums_all", dev, K, 1 + 3 * C), ar.f32("chan_all", dev, K, C)
+            osums, chans = self._f64("osums_all", dev, K, self._row(C)), ar.f32("chan_all", dev, K, C)
+            parts = ar.f32("parts_all", dev, K, 2) if self._edge else None
         steps = []
         for k in range(K):
             bk = dict(b)
             if self._obj is not None:
                 bk["osums"], bk["chan"] = osums[k], chans[k]
+                if self._edge:
+                    bk["parts"] = parts[k]
             for name in self._PER_STEP:
                 if name == "sums":
                     bk[name] = sums[k]
@@ -608,6 +646,8 @@ class FusedStep:
                  g_nin=ar.f32("g_nin", dev, R, C + 1))
         if self._obj is not None:
             b.update(osums_all=osums, chan_all=chans)
+            if self._edge:
+                b["parts_all"] = parts
         if self._wts is None or self._wts.device != dev:
             self._wts = torch.tensor(self.step_weights, device=dev, dtype=torch.float32)
         return steps
@@ -762,6 +802,15 @@ class FusedStep:
             raise ValueError("FusedStep.channel_losses: the default objective runs the reference's kernels, which form no per-channel "
                              "terms; pass objective=Objective(channel_weights=[1.0] * out_dim) to get them for the same loss")
         return (self._buf["chan_all"] if self.unroll > 1 else self._buf["chan"].reshape(1, -1)).clone()
+
+    def loss_parts(self):
+        """Device fp32 [2]: (L, T) of the last call -- the pointwise loss and the edge term of J = L + edge_weight * T, each weighted
+        over the unroll steps like the value a call returns (a copy).  Only an objective with an edge term forms them."""
+        if not self._edge:
+            raise ValueError("FusedStep.loss_parts: the objective has no edge term (Objective(edge_weight=))")
+        if self._shape_key is None:
+            raise RuntimeError("FusedStep.loss_parts: the step has not run yet")
+        return self._wts @ self._buf["parts_all"] if self.unroll > 1 else self._buf["parts"].clone()
 
     # ------------------------------------------------------------------------------------------------ overlapped all-reduce
     # False (BSMS_OVERLAP_ALLREDUCE=0): ONE all-reduce of the whole flat buffer after the backward (rounds 1-3)

@@ -337,7 +337,7 @@ class Trainer:
     autoregressive steps (step.FusedStep); `iter` then takes `(batch, later_targets)`, what TrajectoryBank(horizon=K) hands out;
     loss_space ("physical" / "normalized"), loss_kind ("rmse" / "mse", or the robust "mae" / "huber" of DESIGN.md 4.20),
     loss_delta (the Huber threshold in the units of loss_space, a float or one per channel: required by "huber", refused by every other
-    kind), loss_channel_weights -- the training objective
+    kind), loss_channel_weights, loss_edge_weight / loss_edge_weighting (the edge term) -- the training objective
     (objective.Objective; absent: the reference's masked RMSE in physical units), which `iter` trains on and `get_loss` reports;
     loss_node_weights (absent or false: off) -- the objective weights every node by what `iter(data, node_weights=)` and
     `get_loss(data, node_weights=)` are given, e.g. the lumped measure; `get_error` and the rollout statistics stay unweighted;
@@ -448,7 +448,11 @@ class Trainer:
         tar, mask = self.get_label_mask(data)
         from .objective import masked_loss                    # the default objective: model.masked_rmse, the reference's formula
         std = None if self.objective.space == "physical" else self.model._targetNormalizer.std_with_epsilon()
-        return masked_loss(pred, tar, mask, self.objective, std, node_weights=node_weights)
+        g = pos = None
+        if self.objective.has_edge_term:              # J = L + lambda T: the level-0 edge list, the mesh positions
+            node_in, g = (data[0], data[3][0][0]) if self.model_cfg.consistent_mesh else (data[0].x, data[0].edge_index)
+            pos = node_in[..., pred.shape[-1]:-1]
+        return masked_loss(pred, tar, mask, self.objective, std, node_weights=node_weights, g=g, pos=pos)
 
     def get_error(self, data, relative=True, ema=False):
         """trainer/trainer.py:231-271: (error_mean, error_std) per channel as float32 NumPy arrays [C] -- the masked absolute
