@@ -136,6 +136,9 @@ inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 // bsms_plan_concat (plan.hip: host side; rowsum.hip: the kernel -- plan.hip is also compiled as plain C++ for the sanitizer build):
 // the index blocks of up to kCatParts plans copied into the blocks of their block-diagonal union, node / edge / pooled offsets added
 constexpr size_t kIdxAlign = 64;   // int32 elements (256 bytes) between the arrays of a plan's index block
+// The padding words between the arrays are written (0; -1 behind ids / inv) in a plan bsms_plan_create / bsms_plan_set_pool uploaded and UNDEFINED in one
+// bsms_plan_concat built (its blocks come from the recycling pool and the kernel writes the logical words only): no kernel reads an
+// index array past its logical end (tests/test_hip_plan_concat.py builds unions in recycled blocks and runs the row sums on them).
 #ifdef __HIPCC__
 #define BSMS_HD __host__ __device__
 #else
@@ -191,4 +194,8 @@ struct bsms_plan {
   int32_t *block = nullptr, *pool_block = nullptr;   // the two device allocations the pointers above point into
   size_t block_cap = 0, pool_cap = 0;                // their capacities in bytes (plan.hip recycles them)
   int device = 0;                                    // the device the blocks live on (current device at bsms_plan_create)
+  // bsms_plan_concat only: recorded on the caller's stream behind the kernels that write the blocks.  The HOST readers of the blocks
+  // (bsms_plan_export*, bsms_plan_set_pool) wait for it: their plain hipMemcpy is not ordered against a non-blocking stream.  Null
+  // for a plan bsms_plan_create built (its upload is complete when the call returns).
+  hipEvent_t written = nullptr;
 };

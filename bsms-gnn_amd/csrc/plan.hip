@@ -259,6 +259,13 @@ int upload_block(int32_t** dev, size_t* cap, const std::vector<int32_t>& host) {
   }
   return BSMS_OK;
 }
+
+// A plan bsms_plan_concat built is complete in STREAM order only.  Before the host reads its blocks (or hands one back to the
+// recycling pool) it waits for the event recorded behind the kernels; a plan bsms_plan_create built has none and costs nothing.
+int wait_written(const bsms_plan* p) {
+  if (p->written) BSMS_HIP_CHECK(hipEventSynchronize(p->written));
+  return BSMS_OK;
+}
 }  // namespace
 
 extern "C" int bsms_plan_create(const int64_t* coo, int64_t E, int64_t N, bsms_plan_t** out) {
@@ -348,6 +355,7 @@ extern "C" int bsms_plan_set_pool(bsms_plan_t* p, const int64_t* ids, int64_t Nk
   BSMS_REQUIRE(p != nullptr, BSMS_E_INVALID_ARG, "plan_set_pool: plan is null");
   BSMS_REQUIRE(Nk >= 0 && Nk <= p->N && (ids != nullptr || Nk == 0), BSMS_E_SHAPE,
                "plan_set_pool: bad Nk=%lld for N=%lld", (long long)Nk, (long long)p->N);
+  { int rc_ = wait_written(p); if (rc_) return rc_; }   // a union still being written: its blocks are read back / recycled below
   const size_t nK = idx_pad(size_t(Nk)), nNinv = idx_pad(size_t(p->N));
   std::vector<int32_t> head(nK + nNinv, -1);
   int32_t *h_ids = head.data(), *h_inv = h_ids + nK;
@@ -520,6 +528,18 @@ extern "C" int bsms_plan_concat(const bsms_plan_t* const* parts, int nparts, con
   }
   if (p->min_out_degree == INT64_MAX) p->min_out_degree = 0;
   if (bound) p->w_bound = ew_cat;
+  // what the host readers wait for (wait_written).  Not under a stream capture: a captured record is a graph node, not something
+  // the host can wait for -- a captured union is complete when the graph's launch is, which the caller synchronises anyway.
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(as_stream(stream), &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+  if (cap == hipStreamCaptureStatusNone) {
+    hipError_t e = hipEventCreateWithFlags(&p->written, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(p->written, as_stream(stream));
+    if (e != hipSuccess) {
+      bsms_plan_destroy(p);
+      BSMS_REQUIRE(false, BSMS_E_HIP, "plan_concat: recording the completion event: %s", hipGetErrorString(e));
+    }
+  }
   *out = p;
   return BSMS_OK;
 }
@@ -553,6 +573,7 @@ extern "C" int64_t bsms_plan_export_ex(const bsms_plan_t* p, int which, int32_t*
     default: return -1;
   }
   if (host && n > 0 && ptr) {
+    if (wait_written(p) != BSMS_OK) return -1;
     if (hipMemcpy(host, ptr, size_t(n) * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -1; }
   }
   return n;
@@ -562,6 +583,7 @@ extern "C" int bsms_plan_destroy(bsms_plan_t* p) {
   if (!p) return BSMS_OK;
   release_block(p->block, p->block_cap, p->device);
   release_block(p->pool_block, p->pool_cap, p->device);
+  if (p->written) (void)hipEventDestroy(p->written);
   delete p;
   return BSMS_OK;
 }
@@ -586,6 +608,7 @@ extern "C" int64_t bsms_plan_max_source(const bsms_plan_t* p) { return p ? p->ma
 extern "C" int bsms_plan_export(const bsms_plan_t* p, int32_t* rowptr, int32_t* src_sorted, int32_t* perm,
                                 int32_t* t_rowptr) {
   BSMS_REQUIRE(p != nullptr, BSMS_E_INVALID_ARG, "plan_export: plan is null");
+  { int rc_ = wait_written(p); if (rc_) return rc_; }
   if (rowptr) BSMS_HIP_CHECK(hipMemcpy(rowptr, p->rowptr, (p->N + 1) * 4, hipMemcpyDeviceToHost));
   if (src_sorted && p->E) BSMS_HIP_CHECK(hipMemcpy(src_sorted, p->src, p->E * 4, hipMemcpyDeviceToHost));
   if (perm && p->E) BSMS_HIP_CHECK(hipMemcpy(perm, p->perm, p->E * 4, hipMemcpyDeviceToHost));

@@ -405,7 +405,7 @@ def concat_plans(parts, ew_cat=None, want_index=True):
     L = _abi.lib()
     dev = parts[0].device
     E, Nk = sum(q.E for q in parts), sum(q.Nk for q in parts)
-    pooled = parts[0].Nk > 0
+    pooled = any(q.Nk > 0 for q in parts)   # (not parts[0] alone: a part may be pooled with no node kept, an empty mesh for one)
     coo = torch.empty(2, E, dtype=torch.int64, device=dev) if want_index else None
     ids = torch.empty(Nk, dtype=torch.int64, device=dev) if (want_index and pooled) else None
     pl, keep = _abi.ptr_array([q.handle.value if hasattr(q.handle, "value") else q.handle for q in parts])

@@ -132,7 +132,8 @@ int64_t bsms_plan_max_source(const bsms_plan_t* plan);  /* max(g[0]); degree() l
  * order; every part must then be bound (bsms_plan_bind_edge_weights), the union is bound to `ew_cat` and its gathered weight
  * copies are the parts'.  `coo_out` (nullable): DEVICE int64 [2, E] that receives the union's edge list in the caller's edge
  * order; `ids_out` (nullable): DEVICE int64 [Nk], its kept ids (what PyG's Batch would have produced).  The arrays of the new
- * plan are complete in STREAM ORDER: use it on `stream`, or synchronise first. */
+ * plan are complete in STREAM ORDER: use it on `stream`, or synchronise first.  The calls that read a plan's arrays on the HOST
+ * (bsms_plan_export, bsms_plan_export_ex, bsms_plan_set_pool on the union) wait for that themselves. */
 int bsms_plan_concat(const bsms_plan_t* const* parts, int nparts, const float* ew_cat, int64_t* coo_out, int64_t* ids_out,
                      bsms_stream_t stream, bsms_plan_t** out);
 /* debug/test accessors: copy index arrays to HOST int32 buffers (sizes N+1, E, E, E). */
