@@ -118,7 +118,7 @@ Work carve_work(void* base, const Shape& s, bool recompute = false) {
   return w;
 }
 
-constexpr int kBwdFlags = BSMS_BWD_DEFER_JOIN | BSMS_BWD_RECOMPUTE;
+constexpr int kBwdFlags = BSMS_BWD_DEFER_JOIN | BSMS_BWD_RECOMPUTE | BSMS_BWD_FROZEN_BF16;   // (the last changes no size)
 constexpr int kFwdReuse = 1 | 2 | BSMS_FWD_LEAN;
 
 int make_shape(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int H, int precision, Shape* s, const char* who) {
@@ -429,7 +429,7 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
   bool lanes[2 * kMaxLevels + 1];
   for (int k = 0; k <= 2 * L; ++k) {
     bool nlive, elive;
-    if ((rc = gmp_check_grads(block(grads, k, hidden), hidden, precision, "bsgmp_bwd", &nlive, &elive))) return rc;
+    if ((rc = gmp_check_grads(block(grads, k, hidden), hidden, precision, "bsgmp_bwd", &nlive, &elive, flags & BSMS_BWD_FROZEN_BF16))) return rc;
     lanes[k] = nlive || elive;
   }
   Work w = carve_work(work, s, recompute);
@@ -478,6 +478,7 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
     if (recompute && (r = gmp_fwd_core(c, w.discard, nullptr, true, st))) return r;
     GmpBwdOpts o;
     o.defer_slot = slot; o.grad_pos = gp[level]; o.pos_work = pw.scratch; o.pos_accumulate = pos_acc;
+    o.frozen_bf16 = flags & BSMS_BWD_FROZEN_BF16;
     if ((r = gmp_bwd_core(c, g_in, gx, block(grads, k, hidden), o, st))) return r;
     // Gradient-bucket hand-off (bsms_bsgmp_bwd_ev): lane 1's mark of this block covers lane 0's (gmp_marks_chained) and both
     // lanes are in-order streams, so an event recorded on lane 1 HERE completes when every weight gradient of this block,

@@ -272,6 +272,8 @@ constexpr int kEdgeFusedMaxWg = 256;
 bool edge_fused_supported(int64_t D, int H, int64_t p, int precision);
 size_t edge_fused_part_floats(int64_t rows);   // for a launch over `rows` edge rows: one partial per workgroup, at most kEdgeFusedMaxWg
 int launch_edge_fused_bwd(EdgeFusedBwdArgs a, int* nwg_out, hipStream_t s);
+// the data-only form for a frozen edge MLP: the same g0, bit for bit; `part`, `gmax` and `timing` are not used
+int launch_edge_data_bwd(EdgeFusedBwdArgs a, hipStream_t s);
 int launch_edge_fused_reduce(const float* part, int nwg, float* const dW[3], float* const db[3], hipStream_t s);
 
 // efwd.hip: the edge MLP forward of the bf16 precisions with the three D x D weights resident in LDS (D = 128, hidden = 3):
@@ -297,7 +299,8 @@ int launch_edge_fwd_res(EdgeFwdResArgs a, hipStream_t s);
 // from rowsum.hip
 int rowsum_plan_order(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* out, hipStream_t s);
 int rowsum_by_source(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* out, hipStream_t s);
-int rowsum_source_and_target(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* outS, float* outD, hipStream_t s);
+int rowsum_source_and_target(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* outS, float* outD, hipStream_t s,
+                             bool x_bf16 = false);
 int rowsum_source_target_fiber(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* outS, float* outD,
                                const float* fiber, int ld, int ncols, float* part, int64_t part_blocks, int* nwg, hipStream_t s,
                                bool x_bf16);

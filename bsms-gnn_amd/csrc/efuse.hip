@@ -26,6 +26,7 @@
 // ds_read_b64_tr_b16 -- the K-slot -> feature map of chain.h is exactly what the transposing read delivers.  No loader
 // wave, no ring, no chunk barriers.  LDS: 3 x 36 KB weights + 2 x 18 KB staging + 3 KB side tables = 147 KB.
 // Determinism: every workgroup writes its partial dW / db once; k_ef_reduce sums them in a fixed order (no atomics).
+// A FROZEN edge MLP takes k_edge_data_bwd below instead: the chain wave alone, on all eight waves, no dW / db at all.
 #include "chain.h"
 
 #pragma clang fp contract(off)
@@ -501,6 +502,157 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
+// ---- the data-only form: the edge MLP is FROZEN, so nothing reads dW / db -- no gradient waves, no staging tiles, no
+// X / Y barriers, no partials, no bound slot.  What is left is the chain wave of k_edge_fused_bwd, statement for statement (gather,
+// a_0..a_2, LayerNorm backward, three dgrad stages, deferred bf16 stores of g_0): every row sees the same operations on the same
+// operands in the same product order, so g_0 is bit-identical to the fused kernel's.  LDS = the three resident weight images + the
+// side tables (111 KB: still one workgroup per CU), so ALL EIGHT waves are chain waves and a tile has 128 rows; two waves share a
+// SIMD as a chain and a gradient wave did, within the same register budget.  After the prologue the waves never synchronise.
+constexpr int DT_ROWS = 128;                  // rows of a tile = 8 chain waves x 16
+constexpr int OFF_SIDE_D = 3 * W_BYTES;
+constexpr int LDS_BYTES_D = OFF_SIDE_D + SIDE_B2 + D * 4;
+static_assert(LDS_BYTES_D <= 160 * 1024 && 2 * LDS_BYTES_D > 160 * 1024, "one workgroup per CU");
+static_assert(DT_ROWS <= 2 * kPadRows, "the last tile's stores stay inside pad_rows(R)");
+
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_edge_data_bwd(EdgeFusedBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // ---- prologue of k_edge_fused_bwd: the three PACK_ROWS_BF16 images by LDS-DMA, the fiber weights and two biases by plain stores
+  {
+    const int uwave = __builtin_amdgcn_readfirstlane(wave);
+    for (int piece = uwave; piece < 3 * (W_BYTES / 1024); piece += 8) {
+      const int l = piece / (W_BYTES / 1024), k = piece - l * (W_BYTES / 1024);
+      const char* src = reinterpret_cast<const char*>(a.wr[l]) + k * 1024 + lane * 16;
+      glds16(src, __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds + unsigned(piece) * 1024u));
+    }
+  }
+  {
+    float* side = reinterpret_cast<float*>(lds + OFF_SIDE_D);
+    for (int o = tid; o < 4 * D; o += 512) side[SIDE_WFT / 4 + o] = o < (a.p + 1) * D ? a.wft[o] : 0.f;
+    if (tid < D) side[SIDE_B1 / 4 + tid] = a.b[0][tid];
+    else if (tid < 2 * D) side[SIDE_B2 / 4 + tid - D] = a.b[1][tid - D];
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const int my_tiles = (a.ntiles - int(blockIdx.x) + int(gridDim.x) - 1) / int(gridDim.x);
+  const char* const W1 = lds, * const W2 = lds + W_BYTES, * const W3 = lds + 2 * W_BYTES;
+  const int r = lane & 15, g = lane >> 4;
+  const unsigned tb = unsigned((4 * g + (r >> 2)) * ROWB + 8 * ((r & 3) ^ g));   // supplier base of the transposing reads
+  const int s = (r >> 2) & 3;
+  const unsigned fb = unsigned(r * ROWB + 8 * (g ^ s));                    // base of the forward A-fragments
+  const float* const wft = reinterpret_cast<const float*>(lds + OFF_SIDE_D + SIDE_WFT);
+  const float* const b1 = reinterpret_cast<const float*>(lds + OFF_SIDE_D + SIDE_B1);
+  const float* const b2 = reinterpret_cast<const float*>(lds + OFF_SIDE_D + SIDE_B2);
+  const unsigned uE = unsigned(a.E), uN = unsigned(a.N);
+
+  struct Where { unsigned row, srow; bool live; unsigned isrc, idst; };
+  const float rcpE = 1.f / float(a.E);
+  auto locate = [&](int tile) {
+    Where wq;
+    const int64_t row64 = int64_t(tile) * DT_ROWS + wave * 16 + r;
+    wq.live = row64 < a.R;
+    wq.srow = unsigned(row64);                 // rows past R are padding of g0: the last tile ends below pad_rows(R) (chain.h), never read
+    wq.row = wq.live ? unsigned(row64) : 0u;   // lanes past the end read row 0
+    int b = int(float(wq.row) * rcpE);
+    int q = int(wq.row) - b * int(uE);
+    if (q < 0) { q += int(uE); --b; }
+    if (q >= int(uE)) { q -= int(uE); ++b; }
+    if (unsigned(q) >= uE) { b = int(wq.row / uE); q = int(wq.row - unsigned(b) * uE); }
+    wq.isrc = unsigned(b) * uN + unsigned(a.src[q]);
+    wq.idst = unsigned(b) * uN + unsigned(a.dst[q]);
+    return wq;
+  };
+  f32x4 ps[NB], pd[NB];
+  float4 fib;
+  Where cur = locate(int(blockIdx.x));
+  load_rows<NB>(ps, a.Ps + size_t(cur.isrc) * D, g);
+  load_rows<NB>(pd, a.Pd + size_t(cur.idst) * D, g);
+  fib = *reinterpret_cast<const float4*>(a.fiber + size_t(cur.row) * 4);
+  u32x4 g0p[4] = {};   // g_0 of the PREVIOUS tile, packed: stored two feature blocks at a time between the phases of the next tile
+  unsigned g0row = 0;
+  auto store_g0 = [&](int t0) {
+    u32x2* op = reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(a.g0) + size_t(g0row) * D + 4 * g);
+    op[4 * t0] = u32x2{g0p[t0 >> 1][0], g0p[t0 >> 1][1]};
+    op[4 * t0 + 4] = u32x2{g0p[t0 >> 1][2], g0p[t0 >> 1][3]};
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  for (int it = 0; it < my_tiles; ++it) {
+    const int tile = int(blockIdx.x) + it * int(gridDim.x);
+    f32x4 dy[NB];
+    u32x2 yb[NB];
+    load_rows<NB>(dy, a.dy + size_t(cur.idst) * D, g);
+    {
+      const u32x2* yp = reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned short*>(a.y) + size_t(cur.row) * D + 4 * g);
+#pragma unroll
+      for (int t = 0; t < NB; ++t) yb[t] = yp[4 * t];
+    }
+    const float rstd = a.rstd[cur.row];
+    const bool more = it + 1 < my_tiles;
+    const Where nxt = locate(more ? tile + int(gridDim.x) : tile);
+    // ---- a_0 = relu(Ps[src] + Pd[dst] + Wf . fiber)
+    f32x4 act[NB];
+#pragma unroll
+    for (int t = 0; t < NB; ++t) act[t] = ps[t] + pd[t];
+    {
+      const float fv[4] = {fib.x, fib.y, fib.z, fib.w};
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        if (c < a.p) axpy_features(act, wft + c * D, fv[c], g);
+      const float nrm = a.p == 1 ? fib.y : (a.p == 2 ? fib.z : fib.w);
+      axpy_features(act, wft + a.p * D, nrm, g);
+    }
+    u32x4 a0p[4], a1p[4], a2p[4];
+    relu_pack(a0p, act);
+    if (it > 0) store_g0(0);
+    f32x4 acc[NB];
+    stage_fwd(acc, a0p, W1, b1, fb, g);
+    relu_pack(a1p, acc);
+    if (it > 0) store_g0(2);
+    stage_fwd(acc, a1p, W2, b2, fb, g);
+    relu_pack(a2p, acc);
+    if (it > 0) store_g0(4);
+    // ---- LayerNorm backward (no affine), the two fused multiply-adds per element of k_edge_fused_bwd
+    f32x4 gr[NB];
+    {
+      f32x2 sa = {0.f, 0.f}, sb = {0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < NB; ++t) {
+        act[t] = f32x4{bf16_lo(yb[t][0]), bf16_hi(yb[t][0]), bf16_lo(yb[t][1]), bf16_hi(yb[t][1])};
+        const f32x2 d0 = {dy[t][0], dy[t][1]}, d1 = {dy[t][2], dy[t][3]}, y0 = {act[t][0], act[t][1]}, y1 = {act[t][2], act[t][3]};
+        sa += d0 + d1;
+        sb = __builtin_elementwise_fma(d0, y0, sb);
+        sb = __builtin_elementwise_fma(d1, y1, sb);
+      }
+      const float m1 = group_sum(sa[0] + sa[1]) * (1.f / D);
+      const float m2 = group_sum(sb[0] + sb[1]) * (1.f / D);
+      const float c0 = cur.live ? rstd : 0.f;
+      const float c1 = c0 * m2, c2 = -(c0 * m1);
+      const f32x4 v0 = {c0, c0, c0, c0}, v1 = {-c1, -c1, -c1, -c1}, v2 = {c2, c2, c2, c2};
+#pragma unroll
+      for (int t = 0; t < NB; ++t) gr[t] = __builtin_elementwise_fma(v1, act[t], __builtin_elementwise_fma(v0, dy[t], v2));
+    }
+    if (it > 0) store_g0(6);
+    // ---- the next tile's endpoint rows are requested now: they land under the three gradient stages
+    load_rows<NB>(ps, a.Ps + size_t(nxt.isrc) * D, g);
+    load_rows<NB>(pd, a.Pd + size_t(nxt.idst) * D, g);
+    fib = *reinterpret_cast<const float4*>(a.fiber + size_t(nxt.row) * 4);
+    u32x4 gb[4];
+    pack(gb, gr);
+    stage_bwd(acc, gb, W3, tb);        // Linear 3: g_2 = (W_3^T g_3) . [a_2 > 0]
+    mask_pack(gb, acc, a2p);
+    stage_bwd(acc, gb, W2, tb);        // Linear 2
+    mask_pack(gb, acc, a1p);
+    stage_bwd(acc, gb, W1, tb);        // Linear 1
+    mask_pack(g0p, acc, a0p);          // g_0 (bf16: input of the scatter and of the position gradient), kept packed for the deferred stores
+    g0row = cur.srow;
+    cur = nxt;
+  }
+  if (my_tiles > 0) {   // the last tile's g_0
+    store_g0(0); store_g0(2); store_g0(4); store_g0(6);
+  }
+}
+
 // dW_l = sum over workgroups of their partials, in workgroup order per split and split order at the end (fixed: run-to-run
 // reproducible).  Block = 32 float4 outputs x 8 splits of the workgroup range; the last blocks sum the bias gradients.
 __global__ __launch_bounds__(256) void k_ef_reduce(const float* part, int nwg, float* dW0, float* dW1, float* dW2, float* db0, float* db1,
@@ -582,6 +734,22 @@ int launch_edge_fused_bwd(EdgeFusedBwdArgs a, int* nwg_out, hipStream_t s) {
   *nwg_out = nwg;
   if (nwg > 0) {
     hipLaunchKernelGGL(k_edge_fused_bwd, dim3(nwg), dim3(512), LDS_BYTES, s, a);
+    BSMS_LAUNCH_CHECK();
+  }
+  return BSMS_OK;
+}
+
+// the data-only backward of a frozen edge MLP: one launch, no reduction, nothing of `part` / `gmax` is touched
+int launch_edge_data_bwd(EdgeFusedBwdArgs a, hipStream_t s) {
+  BSMS_REQUIRE(a.R < (int64_t(1) << 31) && a.p >= 1 && a.p <= 3, BSMS_E_UNSUPPORTED, "edge_data_bwd: R = %lld, p = %d", (long long)a.R, a.p);
+  static DynLdsAttr attr_dev;
+  const hipError_t attr = attr_dev.ensure(reinterpret_cast<const void*>(&k_edge_data_bwd), LDS_BYTES_D);
+  BSMS_REQUIRE(attr == hipSuccess, BSMS_E_HIP, "edge_data_bwd: cannot reserve %d bytes of LDS", LDS_BYTES_D);
+  a.ntiles = int(ceil_div(a.R, DT_ROWS));
+  a.part = nullptr; a.gmax = nullptr; a.timing = nullptr;
+  const int nwg = int(std::min<int64_t>(a.ntiles, std::min(device_cus_ef(), kEdgeFusedMaxWg)));
+  if (nwg > 0) {
+    hipLaunchKernelGGL(k_edge_data_bwd, dim3(nwg), dim3(512), LDS_BYTES_D, s, a);
     BSMS_LAUNCH_CHECK();
   }
   return BSMS_OK;

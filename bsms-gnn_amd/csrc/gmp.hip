@@ -216,12 +216,12 @@ GmpShape abi_shape(int64_t B, int64_t N, int64_t E, int64_t D, int H) {
 }  // namespace
 
 // Frozen MLPs: which of a block's two MLPs get their weight gradients.  A host check, before any launch.
-int bsms::gmp_check_grads(float* const* grads, int H, int precision, const char* who, bool* node_live, bool* edge_live) {
+int bsms::gmp_check_grads(float* const* grads, int H, int precision, const char* who, bool* node_live, bool* edge_live, bool frozen_bf16) {
   const int n = 2 * (H + 1);
   const int ns = grads_state(grads, n), es = grads_state(grads ? grads + n : nullptr, n);
   BSMS_REQUIRE(ns >= 0 && es >= 0, BSMS_E_INVALID_ARG, "%s: the gradient entries of the %s MLP are partly null (an MLP is frozen as a whole: all "
                "%d entries null, or none)", who, ns < 0 ? "node" : "edge", n);
-  BSMS_REQUIRE(precision == BSMS_F32 || (ns == 1 && es == 1), BSMS_E_UNSUPPORTED, "%s: null gradient entries (a frozen MLP) need the fp32 "
+  BSMS_REQUIRE(precision == BSMS_F32 || frozen_bf16 || (ns == 1 && es == 1), BSMS_E_UNSUPPORTED, "%s: null gradient entries (a frozen MLP) need the fp32 "
                "precision: the fused edge backward of the bf16 precisions forms its weight gradients on chip", who);
   *node_live = ns == 1;
   *edge_live = es == 1;
@@ -481,8 +481,11 @@ struct GmpBwd {
       for (int l = 1; l <= 3; ++l) { a.wr[l - 1] = reinterpret_cast<const float4*>(sv.e_wr[l]); a.b[l - 1] = pe[2 * l + 1]; }
       a.dy = wk.daggr; a.y = sv.e_y; a.rstd = sv.e_rstd; a.g0 = wk.gE[0];
       a.gmax = g_node_bf3 ? nullptr : sv.bound + size_t(16 + H) * kBoundWidth;   // only the projections' weight gradients used it
-      a.part = wk.ef_part;
       a.timing = g_timing;
+      // a frozen edge MLP (BSMS_BWD_FROZEN_BF16): the data-only kernel -- the same rows of g_0, no gradient waves, no partials, no
+      // bound (its only reader, the projections' weight-gradient jobs, is skipped)
+      if (!elive) { a.gmax = nullptr; return launch_edge_data_bwd(a, s); }
+      a.part = wk.ef_part;
       return launch_edge_fused_bwd(a, &ef_nwg, s);
     }
     ChainBwdArgs a{};
@@ -566,10 +569,10 @@ struct GmpBwd {
     // a frozen edge MLP: only the scatter is left -- the plain pair, which sums every row's slots in the same order as the fused
     // kernel (rowsum.hip: rowsum_body / fiber_batch), so dPs / dPd are bit-identical
     if (!elive) {
-      if ((rc = rowsum_source_and_target(c.plan, wk.gE[0], B, D, wk.dPs, wk.dPd, s))) return rc;
+      if ((rc = rowsum_source_and_target(c.plan, wk.gE[0], B, D, wk.dPs, wk.dPd, s, bf))) return rc;
     } else if ((rc = rowsum_source_target_fiber(c.plan, wk.gE[0], B, D, wk.dPs, wk.dPd, sv.e_fiber, fiber_ld(p), int(p + 1),
                                                 reinterpret_cast<float*>(wk.sw), small_wgrad_part_blocks(wk.sw_bytes, (int)D), &nwg, s, bf))) return rc;
-    BSMS_REQUIRE(nwg > 0 || !bf, BSMS_E_UNSUPPORTED, "gmp_bwd: bf16 precision needs the fused scatter kernel (D = 128 / 256, pos_dim <= 3)");
+    BSMS_REQUIRE(nwg > 0 || !bf || !elive, BSMS_E_UNSUPPORTED, "gmp_bwd: bf16 precision needs the fused scatter kernel (D = 128 / 256, pos_dim <= 3)");
     if (nwg == 0 && elive) {   // shape not built into the fused kernel (D < 128, pos_dim > 3): separate passes
       if (overlap2) {
         if ((rc = side_fork(lane2, s))) return rc;
@@ -641,7 +644,7 @@ int bsms::gmp_bwd_core(const GmpCall& c, const float* grad_out, float* grad_x, f
   if (rc) return rc;
   BSMS_REQUIRE(c.x && c.pos && grad_out && c.params && c.saved && c.work && grad_x, BSMS_E_INVALID_ARG, "gmp_bwd: null argument");
   bool nlive = true, elive = true;
-  if ((rc = gmp_check_grads(grads, c.H, c.precision, "gmp_bwd", &nlive, &elive))) return rc;
+  if ((rc = gmp_check_grads(grads, c.H, c.precision, "gmp_bwd", &nlive, &elive, o.frozen_bf16))) return rc;
   GmpBwd b(c, grad_out, grad_x, grads, nlive, elive, o, s);   // (an error return below joins the lanes forked so far: LaneScope)
   if ((rc = b.node_chain()) || (rc = b.edge_chain()) || (rc = b.lane0_wgrads()) || (rc = b.scatter_strand()) || (rc = b.input_grad()) ||
       (rc = b.pos_grad()))

@@ -53,6 +53,7 @@ struct GmpBwdOpts {
   float* grad_pos = nullptr;
   void* pos_work = nullptr;
   bool pos_accumulate = false;
+  bool frozen_bf16 = false;   // BSMS_BWD_FROZEN_BF16: null `grads` entries are accepted in the bf16 precisions
 };
 
 size_t gmp_pack_bytes(int64_t D, int hidden);   // inference packs of one block (upper bound)
@@ -65,8 +66,9 @@ int gmp_pack_group_add(PackGroup* g, const GmpCall& c);
 int gmp_fwd_core(const GmpCall& c, float* out, const float* resid2, bool do_prepack, hipStream_t stream);
 // The `grads` table of one block: 2 (H + 1) node-MLP entries, then 2 (H + 1) edge-MLP entries; each group
 // all there or all null (the MLP is frozen), `grads` == NULL = both frozen.  BSMS_E_INVALID_ARG for a partly null group,
-// BSMS_E_UNSUPPORTED for null entries in a bf16 precision.  A host check: nothing is launched.
-int gmp_check_grads(float* const* grads, int hidden, int precision, const char* who, bool* node_live, bool* edge_live);
+// BSMS_E_UNSUPPORTED for null entries in a bf16 precision unless `frozen_bf16` (BSMS_BWD_FROZEN_BF16).  A host check: nothing is launched.
+int gmp_check_grads(float* const* grads, int hidden, int precision, const char* who, bool* node_live, bool* edge_live,
+                    bool frozen_bf16 = false);
 bool gmp_marks_chained();   // deferred-join mode: waiting for lane 1's mark of a slot is enough
 int gmp_bwd_core(const GmpCall& c, const float* grad_out, float* grad_x, float* const* grads, const GmpBwdOpts& o, hipStream_t stream);
 

@@ -196,6 +196,16 @@ __global__ __launch_bounds__(256) void k_rowsum_pair(RowSumArgs a0, RowSumArgs a
   else rowsum_body<LPR, false, false, DEEP, false, false>(a);
 }
 
+// the same pair over a bf16 x (the first edge gradient of the bf16 precisions with a frozen edge MLP): D == 4 * LPR.
+// Every row's slots are added one after the other in slot order, as both halves of k_rowsum_pair_fiber<.., true> add them (the batch
+// sizes differ -- 32 / 8 here, 16 / 8 in fiber_batch -- the sequence of additions does not): bit-identical dPs / dPd.
+template <int LPR, bool DEEP>
+__global__ __launch_bounds__(256) void k_rowsum_pair_bf16(RowSumArgs a0, RowSumArgs a1) {
+  const RowSumArgs& a = blockIdx.y ? a1 : a0;
+  if (a.xidx) rowsum_body<LPR, false, false, DEEP, true, false, true>(a);
+  else rowsum_body<LPR, false, false, DEEP, false, false, true>(a);
+}
+
 // ---- the two scatters of the first edge gradient + the narrow weight gradient of the first edge Linear, ONE launch.
 // blockIdx.y = 0: by source (transpose CSR, gathered rows), as k_rowsum_pair.  blockIdx.y = 1: by target -- the rows of
 // a target are contiguous in plan order, and while a lane streams them it also accumulates, for the fiber columns s
@@ -513,8 +523,10 @@ int rowsum_source_target_fiber(const bsms_plan* p, const float* x, int64_t B, in
   return BSMS_OK;
 }
 // by source and by target at once: outS[b,i,:] = sum_{e: src(e)=i} x[b,slot(e),:], outD[b,j,:] = sum_{e: dst(e)=j} x[b,slot(e),:]
-int rowsum_source_and_target(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* outS, float* outD, hipStream_t s) {
-  if (D != 128) {   // the pair kernel is built for the 32-lanes-per-row shape only
+// `x_bf16`: x holds bf16 rows (D = 128 / 256 only); the sums and both outputs are fp32
+int rowsum_source_and_target(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* outS, float* outD, hipStream_t s, bool x_bf16) {
+  BSMS_REQUIRE(!x_bf16 || D == 128 || D == 256, BSMS_E_UNSUPPORTED, "bf16 scatter pair: D=%lld (128, 256)", (long long)D);
+  if (D != 128 && !x_bf16) {   // the pair kernel is built for the 32-lanes-per-row shape only
     int rc = rowsum_by_source(p, x, B, D, outS, s);
     return rc ? rc : rowsum_plan_order(p, x, B, D, outD, s);
   }
@@ -526,6 +538,20 @@ int rowsum_source_and_target(const bsms_plan* p, const float* x, int64_t B, int6
   a0.n_out = a1.n_out = (int32_t)p->N; a0.B = a1.B = (int32_t)B; a0.D = a1.D = (int32_t)D;
   const int64_t workers = B * p->N;
   if (workers == 0) return BSMS_OK;
+  if (x_bf16) {   // the lanes per row, and the DEEP levels, of the fused pair kernel the live path runs
+    const int lpr = int(D / 4);
+    const dim3 gridb((unsigned)ceil_div(workers * lpr, 256), 2);
+    const bool deep = workers * lpr < kDeepBelowThreads;
+    if (D == 128) {
+      if (deep) hipLaunchKernelGGL((k_rowsum_pair_bf16<32, true>), gridb, dim3(256), 0, s, a0, a1);
+      else hipLaunchKernelGGL((k_rowsum_pair_bf16<32, false>), gridb, dim3(256), 0, s, a0, a1);
+    } else {
+      if (deep) hipLaunchKernelGGL((k_rowsum_pair_bf16<64, true>), gridb, dim3(256), 0, s, a0, a1);
+      else hipLaunchKernelGGL((k_rowsum_pair_bf16<64, false>), gridb, dim3(256), 0, s, a0, a1);
+    }
+    BSMS_LAUNCH_CHECK();
+    return BSMS_OK;
+  }
   const dim3 grid((unsigned)ceil_div(workers * 32, 256), 2);
   if (workers * 32 < kDeepBelowThreads) hipLaunchKernelGGL((k_rowsum_pair<32, true>), grid, dim3(256), 0, s, a0, a1);
   else hipLaunchKernelGGL((k_rowsum_pair<32, false>), grid, dim3(256), 0, s, a0, a1);

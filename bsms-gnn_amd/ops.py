@@ -766,6 +766,7 @@ class InferenceSession:
 
 
 FWD_LEAN, BWD_RECOMPUTE = 4, 2     # include/bsms_hip.h: BSMS_FWD_LEAN (a bit of `reuse`), BSMS_BWD_RECOMPUTE (a bit of `flags`)
+BWD_FROZEN_BF16 = 32               # BSMS_BWD_FROZEN_BF16 (a bit of `flags`): null `grads` entries in the bf16 precisions
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16_nodes": 2}   # include/bsms_hip.h: bsms_precision (bf16: edge MLP; bf16_nodes: edge + node MLP)
 
 

@@ -54,7 +54,7 @@ import torch
 import torch.distributed as dist
 
 from . import _abi
-from .ops import BWD_RECOMPUTE, FWD_LEAN, PRECISIONS, _param_ptrs, _stream
+from .ops import BWD_FROZEN_BF16, BWD_RECOMPUTE, FWD_LEAN, PRECISIONS, _param_ptrs, _stream
 
 
 REDUCTIONS = {"batch": 0, "mean": 1}             # BSMS_ACCUM_BATCH / BSMS_ACCUM_MEAN
@@ -149,6 +149,7 @@ class FusedStep:
         if grads is None and self._param_grad:
             raise ValueError("FusedStep: weight gradients need a GradBuckets (grads=None goes with param_grad=False)")
         self._any_live = False                      # some MLP gets weight gradients (set by _pointer_tables)
+        self._frozen_bit = 0                        # BSMS_BWD_FROZEN_BF16 iff a bf16 precision and an MLP is frozen (set by _pointer_tables)
         if not input_grad and not any(p.requires_grad for q in _mlps(model) for p in q.flat_params()):
             raise ValueError("FusedStep: nothing is trainable and input_grad is off: the step would compute nothing")
         self._guard_params = [q.flat_params()[0] for q in _mlps(model)]
@@ -193,12 +194,13 @@ class FusedStep:
     @staticmethod
     def supports(model):
         """A standard one-call BSMS_Simulator whose MLPs (encoder, decoder, each block's node and edge MLP) are each all-trainable
-        or all-frozen; anything frozen needs the fp32 precision."""
+        or all-frozen; anything frozen needs the fp32 precision or, in a bf16 precision, a latent width of 128 or 256
+        (DESIGN.md 4.23)."""
         from .model import BSMS_Simulator
         if not isinstance(model, BSMS_Simulator) or model.process.per_block:
             return False
         states = [_freeze_state(q) for q in _mlps(model)]
-        return None not in states and (all(states) or model.process.precision == "f32")
+        return None not in states and (all(states) or model.process.precision == "f32" or model.cfg.latent_dim in (128, 256))
 
     collectives_at_world_one = False     # tests: issue the step's collectives in a process group of ONE rank as well (a sum over one
                                          # rank is the identity) -- the only way to run the RCCL path on a single-GPU box
@@ -255,8 +257,8 @@ class FusedStep:
         if guard != self._ptr_guard:                # parameters were re-pointed (optimizer flat buffer, .to(), load) or (un)frozen
             if None in states:
                 raise ValueError("FusedStep: an MLP with some frozen and some trainable parameters (an MLP is frozen as a whole)")
-            if not all(states) and m.process.precision != "f32":
-                raise ValueError("FusedStep: frozen parameters need the fp32 precision")
+            # a bf16 precision with a frozen MLP: the U-Net's backward takes null entries under BSMS_BWD_FROZEN_BF16
+            self._frozen_bit = BWD_FROZEN_BF16 if (not all(states) and m.process.precision != "f32") else 0
             if not any(states) and not self._input_grad:
                 raise ValueError("FusedStep: nothing is trainable and input_grad is off: the step would compute nothing")
             live = {}
@@ -537,7 +539,7 @@ class FusedStep:
         ck(L.bsms_mlp_bwd_ex(b["h1"].data_ptr(), b["g_np"].data_ptr(), R, D, D, C, H, 0, t["dec"][0][0], b["s_dec"].data_ptr(),
                              b["work_dec"].data_ptr(), b["gh1"].data_ptr(), t["dec"][1][0], 1, s), "bsms_mlp_bwd(decode)")   # 1 = BSMS_BWD_DEFER_JOIN
         ewp, keep = _abi.ptr_array([e.data_ptr() for e in ews])
-        flags = 1 | self._proc_flags                  # BSMS_BWD_DEFER_JOIN (| BSMS_BWD_RECOMPUTE)
+        flags = 1 | self._proc_flags | self._frozen_bit      # BSMS_BWD_DEFER_JOIN (| BSMS_BWD_RECOMPUTE) (| BSMS_BWD_FROZEN_BF16)
         # BSMS_BWD_DEFER_JOIN: the weight gradients of the last (level-0) block are still running on the engine's side
         # streams (~0.2 ms on half the chip) while the encoder's backward -- own scratch, own gradient slots -- runs here
         if ig is None:
@@ -994,7 +996,7 @@ def input_gradient(model, data, consistent=True, later_targets=None, step_weight
 
     `param_grad=False`: the backward is data-only whatever `requires_grad` says -- no weight gradient is formed,
     no `GradBuckets` is created and no `p.grad` is touched or created; loss and gradient are bit-identical to `param_grad=True`'s.
-    fp32 precision only.
+    Every precision; a bf16 precision at latent width 128 or 256.
 
     `recompute=True`: FusedStep's -- the adjoint through a long rollout holds the blocks' inputs per step instead of
     their activations; loss and gradient keep their bits.

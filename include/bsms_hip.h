@@ -288,7 +288,7 @@ int bsms_gmp_bwd_pos(const bsms_plan_t* plan, const float* x, const float* pos, 
  * FROZEN MLPs (every bsms_bsgmp_bwd* entry): per block as for bsms_gmp_bwd -- the node MLP's and the edge MLP's
  * `grads` entries all there or all NULL; `grads` = NULL freezes the whole U-Net (a data-only backward: grad_h, grad_pos).  Every
  * block's entries are checked on the host before the first launch: a partly null MLP is BSMS_E_INVALID_ARG, null entries with a
- * bf16 precision are BSMS_E_UNSUPPORTED.  grad_h, grad_pos and the remaining gradients are bit-identical to the call with every
+ * bf16 precision are BSMS_E_UNSUPPORTED unless `flags` has BSMS_BWD_FROZEN_BF16 (below).  grad_h, grad_pos and the remaining gradients are bit-identical to the call with every
  * entry.  A block whose two MLPs are frozen runs no side lane: under BSMS_BWD_DEFER_JOIN it marks nothing, and its
  * `block_done_events` entry (bsms_bsgmp_bwd_ev) is recorded on the CALLER's stream -- it orders the block itself, not the weight
  * gradients of earlier blocks or of a deferred bsms_mlp_bwd_ex; wait for the entry of a block that has weight gradients, or for
@@ -349,6 +349,12 @@ enum { BSMS_BWD_DEFER_JOIN = 1 };
  * BSMS_E_INVALID_ARG, checked before anything else.  The one-block bsms_gmp_* entries have no such mode. */
 enum { BSMS_FWD_LEAN = 4 };
 enum { BSMS_BWD_RECOMPUTE = 2 };
+/* FROZEN MLPs IN THE bf16 PRECISIONS: a bit of `flags` of bsms_bsgmp_bwd_ex / _ev / _pos_ev.  With it, NULL `grads`
+ * entries (frozen MLPs, as above) are accepted under BSMS_BF16 / BSMS_BF16_NODES for D = 128 / 256: a frozen edge MLP takes the
+ * data-only edge backward, which forms no weight gradient on chip.  grad_h, grad_pos and the remaining gradients are bit-identical to
+ * the call with every entry.  Without the bit such a call stays BSMS_E_UNSUPPORTED; in fp32 and with every entry there the bit
+ * changes nothing.  The `_ex` size queries accept it and return the sizes they return without it. */
+enum { BSMS_BWD_FROZEN_BF16 = 32 };
 size_t bsms_bsgmp_saved_bytes_ex(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden, int precision,
                                  int flags);
 size_t bsms_bsgmp_work_bytes_ex(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int hidden, int precision,
