@@ -1,8 +1,8 @@
 // The objective with an edge-difference term (include/bsms_hip_ext.h: bsms_edge_diff_fold, bsms_sim_edge_objective_bwd),
 // built into the companion library libbsms_hip_ext.so: the surface of libbsms_hip.so is closed (its entries are pinned one by one),
 // so entries that come later live here, on the same plans, error reporting and device code.
-// The fold adds the segments' rows in index order, one thread per column.  The backward is the row of sim_objective_bwd_row
-// (objective_row.h: the same head and tail) with the adjoint's gather (edge_gather.h: the one copy k_edge_bwd runs too) added to the loss
+// The fold adds the segments' rows in index order, one thread per column.  The backward is the row of k_sim_objective_bwd
+// (sim.hip; objective_row.h: the one head and the one tail) with the adjoint's gather (edge_gather.h: the one copy k_edge_bwd runs too) added to the loss
 // gradient in front of the step weight.  Compiled with -ffp-contract=off (build.py).
 #include <cmath>
 
@@ -19,16 +19,14 @@ using namespace bsms::edge;
 namespace {
 
 // The objective with an edge term, backward (include/bsms_hip_ext.h: bsms_sim_edge_objective_bwd): the row of
-// sim_objective_bwd_row (objective_row.h: the same head and tail) with the edge term's gradient added to the loss gradient before the
+// k_sim_objective_bwd (objective_row.h: the one head and the one tail) with the edge term's gradient added to the loss gradient before the
 // step weight.  Thread gr owns row gr of the R = S * seg_rows rows; segment s = gr / seg_rows, the plan's row r = gr - s * seg_rows.
 struct EdgeObjArgs {
-  const double *mean, *meansq, *eps, *in_mean, *in_meansq, *in_eps;
-  const double *sums, *edge_sums, *weights;             // [M | SE], [ME | DE] (the fold's row), channel weights or null
-  const float *g_pred_next, *g_norm_in_next;
-  float *loss_out, *parts_out, *chan_out, *g_pred, *grad_norm_pred;
+  LossBwdArgs row;                                      // sums = fp64 [M | SE]
+  const double* edge_sums;                              // [ME | DE] (the fold's row)
+  float* parts_out;
   double lambda;
   int64_t R;
-  float w;
   int normalized, rmse;
 };
 
@@ -49,16 +47,17 @@ __global__ __launch_bounds__(kBwdThreads) void k_edge_objective_bwd(const EdgeAr
     me = load_node<C, kQuot>(pred, target, mask, pos, a.p, r);
     edge_gather<C, kQuot>(a, pred, target, mask, pos, r, me, acc);
   }
-  const double e = *o.eps;
-  const double MC = o.sums[0] * double(C);
+  const double* sums = static_cast<const double*>(o.row.sums);
+  const double e = *o.row.eps;
+  const double MC = sums[0] * double(C);
   double sd[C], ac[C];
   double Q = 0.0;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    const ObjectiveChannel ch = objective_channel(c, o.mean, o.meansq, e, o.sums, o.weights, o.normalized, MC);
+    const ObjectiveChannel ch = objective_channel(c, o.row.mean, o.row.meansq, e, sums, o.row.weights, o.normalized, MC);
     sd[c] = ch.sd;
     ac[c] = ch.a;
-    if (gr == 0 && o.chan_out) o.chan_out[c] = float(ch.term);
+    if (gr == 0 && o.row.chan_out) o.row.chan_out[c] = float(ch.term);
     Q += ch.term;
   }
   const double loss = objective_loss(Q, o.rmse);
@@ -69,13 +68,12 @@ __global__ __launch_bounds__(kBwdThreads) void k_edge_objective_bwd(const EdgeAr
   for (int c = 0; c < C; ++c) H += ac[c] * o.edge_sums[1 + c] / MEC;
   const double T = o.rmse ? sqrt(H) : H;
   if (gr == 0) {
-    if (o.loss_out) *o.loss_out = float(loss + o.lambda * T);
+    if (o.row.loss_out) *o.row.loss_out = float(loss + o.lambda * T);
     if (o.parts_out) { o.parts_out[0] = float(loss); o.parts_out[1] = float(T); }
   }
   if (!row) return;
   const float m = me.m;
-  const bool carried = o.g_pred_next != nullptr && m != 0.f;
-  const double ie = o.g_pred_next ? *o.in_eps : 0.0;
+  const LossBwdCarry carry = loss_bwd_carry(o.row, m);
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     const double k = o.rmse ? (o.lambda * ac[c]) / ((2.0 * T) * MEC) : (o.lambda * ac[c]) / MEC;
@@ -83,8 +81,7 @@ __global__ __launch_bounds__(kBwdThreads) void k_edge_objective_bwd(const EdgeAr
     const float coef = float(G * ac[c]);
     float gp = me.d[c] * m * coef;
     gp = gp + ge;
-    objective_tail(gp, o.w, m, carried, gr, c, C, sd[c], o.in_mean, o.in_meansq, ie, o.g_pred_next, o.g_norm_in_next, o.g_pred,
-                   o.grad_norm_pred);
+    objective_tail(gp, m, carry, gr, c, C, sd[c], o.row);
   }
 }
 
@@ -130,19 +127,14 @@ extern "C" int bsms_sim_edge_objective_bwd(const bsms_plan_t* plan, int64_t seg_
                weighting);
   const bool quot = weighting == BSMS_EDGE_QUOTIENT;
   BSMS_REQUIRE(!quot || (p >= 1 && p <= kMaxP), BSMS_E_UNSUPPORTED, "%s: p=%lld (p in 1..3 with the quotient weighting)", who, (long long)p);
-  BSMS_REQUIRE((space == BSMS_LOSS_PHYSICAL || space == BSMS_LOSS_NORMALIZED) && (kind == BSMS_LOSS_MSE || kind == BSMS_LOSS_RMSE),
-               BSMS_E_UNSUPPORTED, "%s: space=%d kind=%d (each 0 or 1)", who, space, kind);
+  if (int rc = check_space_kind(who, space, kind)) return rc;
   BSMS_REQUIRE(S >= 1 && seg_rows >= 1 && seg_rows <= INT32_MAX && S <= INT32_MAX / seg_rows, BSMS_E_INVALID_ARG,
                "%s: S=%lld seg_rows=%lld (each >= 1, S * seg_rows below 2^31)", who, (long long)S, (long long)seg_rows);
   BSMS_REQUIRE(std::isfinite(edge_lambda) && edge_lambda >= 0.0, BSMS_E_INVALID_ARG, "%s: edge_lambda=%g (finite and >= 0)", who, edge_lambda);
   BSMS_REQUIRE(plan, BSMS_E_INVALID_ARG, "%s: plan is null", who);
   BSMS_REQUIRE(pred && target && mask && (pos || !quot) && mean && meansq && std_eps_dev && sums && edge_sums && grad_norm_pred,
                BSMS_E_INVALID_ARG, "%s: null argument", who);
-  BSMS_REQUIRE((g_pred_next == nullptr) == (g_norm_in_next == nullptr), BSMS_E_INVALID_ARG,
-               "%s: the carried pair (g_pred_next, g_norm_in_next) is given together or not at all", who);
-  BSMS_REQUIRE(!g_pred_next || (in_mean && in_meansq && in_std_eps_dev), BSMS_E_INVALID_ARG,
-               "%s: a carried gradient needs the input normaliser's statistics", who);
-  BSMS_REQUIRE(!g_pred || (g_pred != g_pred_next), BSMS_E_INVALID_ARG, "%s: g_pred aliases g_pred_next", who);
+  if (int rc = check_carry(who, g_pred_next, g_norm_in_next, in_mean, in_meansq, in_std_eps_dev, g_pred)) return rc;
   BSMS_REQUIRE(seg_rows == plan->N, BSMS_E_SHAPE, "%s: seg_rows=%lld, the plan has %lld rows", who, (long long)seg_rows, (long long)plan->N);
   EdgeArgs a{};
   a.rowptr = plan->rowptr; a.src = plan->src; a.t_rowptr = plan->t_rowptr; a.t_dst = plan->t_dst;
@@ -152,11 +144,9 @@ extern "C" int bsms_sim_edge_objective_bwd(const bsms_plan_t* plan, int64_t seg_
   a.blk0 = 0;
   a.p = quot ? int(p) : 0;
   EdgeObjArgs o{};
-  o.mean = mean; o.meansq = meansq; o.eps = std_eps_dev; o.in_mean = in_mean; o.in_meansq = in_meansq; o.in_eps = in_std_eps_dev;
-  o.sums = sums; o.edge_sums = edge_sums; o.weights = channel_weights;
-  o.g_pred_next = g_pred_next; o.g_norm_in_next = g_norm_in_next;
-  o.loss_out = loss_out; o.parts_out = parts_out; o.chan_out = chan_out; o.g_pred = g_pred; o.grad_norm_pred = grad_norm_pred;
-  o.lambda = edge_lambda; o.R = S * seg_rows; o.w = w;
+  o.row = {mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, channel_weights, w, g_pred_next, g_norm_in_next, loss_out,
+           chan_out, g_pred, grad_norm_pred};
+  o.edge_sums = edge_sums; o.parts_out = parts_out; o.lambda = edge_lambda; o.R = S * seg_rows;
   o.normalized = int(space == BSMS_LOSS_NORMALIZED); o.rmse = int(kind == BSMS_LOSS_RMSE);
   const unsigned nb = unsigned(ceil_div(o.R, kBwdThreads));
   hipStream_t s = as_stream(stream);

@@ -1,5 +1,5 @@
 // Model-level glue of BSMS_Simulator (models/model.py:127-164) and the masked-RMSE loss (trainer/trainer.py:96-97) as
-// three small fused kernels.  In the reference (and in the autograd mirror, bsms-gnn_amd/model.py) this is ~40
+// small fused kernels: prologue, epilogue, and the loss gradients (pair sums, squared-objective row, robust row: one tail, objective_row.h).  In the reference (and in the autograd mirror, bsms-gnn_amd/model.py) this is ~40
 // element-wise / reduction launches per training step on [B,N,<=4] tensors -- ~0.35 ms of a 7 ms step on the GPU and
 // most of the host time that is not the engine's own.  The arithmetic is kept op for op:
 //   normalise    float( (double(x) - mean) / std ),  std = max(nan_to_num(sqrt(E[x^2] - mean^2)), eps)   (fp64, normalizer.py:40-52,88-90)
@@ -97,22 +97,26 @@ __global__ __launch_bounds__(256) void k_sim_sum_partials(const float2* partials
   if (threadIdx.x == 0) { sums[0] = float(red[0].x); sums[1] = float(red[0].y); }
 }
 
-// loss = sqrt(S / M / C) from the (possibly all-reduced) sums; grad w.r.t. the decoder output
-__global__ __launch_bounds__(256) void k_sim_loss_bwd(const float* pred, const float* target, const float* mask, int64_t R,
-                                                      int C, const double* mean, const double* meansq, const double* eps,
-                                                      const float* sums, float* loss_out, float* grad_norm_pred) {
+// The masked RMSE on the fp32 pair `sums` = [S, M] of bsms_sim_epilogue: loss = sqrt(S / M / C) from the (possibly all-reduced) sums,
+// and one step k of its (K-step) gradient w.r.t. the decoder output, through the one tail of objective_row.h: the step weight and
+// the gradient carried back from step k+1 through in_{k+1} = where(mask == 0, in_0, cat[pred_k, ...]) (utils/rollout_utils.py:57-62).
+// bsms_sim_loss_bwd is the launch with w = 1.0f, no carried pair and no g_pred: 1.0f * x is exact, so the single step's gradient
+// is (d * m) * coef to the bit, as if the product were not there (tests/test_hip_unroll.py::test_sim_unroll_bwd_kernel).
+__global__ __launch_bounds__(256) void k_sim_pair_bwd(const float* pred, const float* target, const float* mask, int64_t R, int C,
+                                                      const LossBwdArgs o) {
   const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  const float* sums = static_cast<const float*>(o.sums);
   const float S = sums[0], M = sums[1];
   const float loss = sqrtf(S / M / float(C));
-  if (r == 0 && loss_out) *loss_out = loss;
+  if (r == 0 && o.loss_out) *o.loss_out = loss;
   if (r >= R) return;
-  const double e = *eps;
+  const double e = *o.eps;
   const float m = mask[r];
   const float coef = 1.f / (loss * M * float(C));           // dL/dS * 2 = 1 / (L M C)
+  const LossBwdCarry carry = loss_bwd_carry(o, m);
   for (int c = 0; c < C; ++c) {
     const float gp = (pred[r * C + c] - target[r * C + c]) * m * coef;   // dL/dpred
-    const float gd = gp * m;                                              // through `delta * mask`
-    grad_norm_pred[r * C + c] = float(double(gd) * std_eps(mean[c], meansq[c], e));   // through the fp64 de-normalisation
+    objective_tail(gp, m, carry, r, c, C, std_eps(o.mean[c], o.meansq[c], e), o);
   }
 }
 
@@ -165,49 +169,12 @@ extern "C" int bsms_sim_loss_bwd(const float* pred, const float* target, const f
   BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "sim_loss_bwd: R=%lld C=%lld", (long long)R, (long long)C);
   BSMS_REQUIRE(pred && target && mask && mean && meansq && std_eps_dev && sums && grad_norm_pred, BSMS_E_INVALID_ARG,
                "sim_loss_bwd: null argument");
-  hipLaunchKernelGGL(k_sim_loss_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask, R,
-                     (int)C, mean, meansq, std_eps_dev, sums, loss_out, grad_norm_pred);
+  const LossBwdArgs o{mean, meansq, std_eps_dev, nullptr, nullptr, nullptr, sums, nullptr, 1.0f, nullptr, nullptr, loss_out, nullptr, nullptr,
+                      grad_norm_pred};
+  hipLaunchKernelGGL(k_sim_pair_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask, R, (int)C, o);
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
-
-namespace {
-
-// One step k of the unrolled (K-step) loss, backward: k_sim_loss_bwd with the step weight and the gradient carried back from step
-// k+1 through in_{k+1} = where(mask == 0, in_0, cat[pred_k, ...]) (utils/rollout_utils.py:57-62).  Step k+1's state columns
-// reach its loss twice: through the identity term of pred = state + delta * mask (g_pred_next) and through the encoder's
-// input, behind the fp64 input normalisation (g_norm_in_next / std_in).  Dirichlet rows took in_0, not pred_k: no carry.
-__global__ __launch_bounds__(256) void k_sim_unroll_bwd(const float* pred, const float* target, const float* mask, int64_t R,
-                                                        int C, const double* mean, const double* meansq, const double* eps,
-                                                        const double* in_mean, const double* in_meansq, const double* in_eps,
-                                                        const float* sums, float w, const float* g_pred_next,
-                                                        const float* g_norm_in_next, float* loss_out, float* g_pred,
-                                                        float* grad_norm_pred) {
-  const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  const float S = sums[0], M = sums[1];
-  const float loss = sqrtf(S / M / float(C));
-  if (r == 0 && loss_out) *loss_out = loss;
-  if (r >= R) return;
-  const double e = *eps;
-  const float m = mask[r];
-  const float coef = 1.f / (loss * M * float(C));
-  const bool carried = g_pred_next != nullptr && m != 0.f;
-  const double ie = g_pred_next ? *in_eps : 0.0;
-  for (int c = 0; c < C; ++c) {
-    float gp = (pred[r * C + c] - target[r * C + c]) * m * coef;          // as k_sim_loss_bwd forms it
-    gp = w * gp;
-    if (carried) {
-      const float through_norm = float(double(g_norm_in_next[r * (C + 1) + c]) / std_eps(in_mean[c], in_meansq[c], ie));
-      const float g_state = g_pred_next[r * C + c] + through_norm;
-      gp = gp + g_state;
-    }
-    if (g_pred) g_pred[r * C + c] = gp;
-    const float gd = gp * m;
-    grad_norm_pred[r * C + c] = float(double(gd) * std_eps(mean[c], meansq[c], e));
-  }
-}
-
-}  // namespace
 
 extern "C" int bsms_sim_unroll_bwd(const float* pred, const float* target, const float* mask, int64_t R, int64_t C,
                                    const double* mean, const double* meansq, const double* std_eps_dev, const double* in_mean,
@@ -217,14 +184,10 @@ extern "C" int bsms_sim_unroll_bwd(const float* pred, const float* target, const
   BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "sim_unroll_bwd: R=%lld C=%lld", (long long)R, (long long)C);
   BSMS_REQUIRE(pred && target && mask && mean && meansq && std_eps_dev && sums && grad_norm_pred, BSMS_E_INVALID_ARG,
                "sim_unroll_bwd: null argument");
-  BSMS_REQUIRE((g_pred_next == nullptr) == (g_norm_in_next == nullptr), BSMS_E_INVALID_ARG,
-               "sim_unroll_bwd: the carried pair (g_pred_next, g_norm_in_next) is given together or not at all");
-  BSMS_REQUIRE(!g_pred_next || (in_mean && in_meansq && in_std_eps_dev), BSMS_E_INVALID_ARG,
-               "sim_unroll_bwd: a carried gradient needs the input normaliser's statistics");
-  BSMS_REQUIRE(!g_pred || (g_pred != g_pred_next), BSMS_E_INVALID_ARG, "sim_unroll_bwd: g_pred aliases g_pred_next");
-  hipLaunchKernelGGL(k_sim_unroll_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask, R,
-                     (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, w, g_pred_next, g_norm_in_next,
-                     loss_out, g_pred, grad_norm_pred);
+  if (int rc = check_carry("sim_unroll_bwd", g_pred_next, g_norm_in_next, in_mean, in_meansq, in_std_eps_dev, g_pred)) return rc;
+  const LossBwdArgs o{mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, nullptr, w, g_pred_next, g_norm_in_next, loss_out,
+                      nullptr, g_pred, grad_norm_pred};
+  hipLaunchKernelGGL(k_sim_pair_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask, R, (int)C, o);
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
@@ -233,7 +196,7 @@ namespace {
 
 // One step k of the K-step input gradient G = dJ / d in_0 (include/bsms_hip.h: bsms_sim_input_grad), folded into grad_in
 // [R, C+p+1] in the column layout of node_in.  t = float(double(g_norm_in) / std_in) is the way back through the fp64 input
-// normalisation, formed as k_sim_unroll_bwd forms its `through_norm`.  Thread r owns row r, the map of every k_sim_* kernel: a
+// normalisation, formed as objective_tail (objective_row.h) forms the carried one.  Thread r owns row r, the map of every k_sim_* kernel: a
 // row is at most 17 floats in and 16 out, a wave covers 64 consecutive rows, so every cache line it touches is used in full
 // over the column loop; the launch is glue (launch-bound), not a streaming kernel worth an element-per-lane map.
 __global__ __launch_bounds__(256) void k_sim_input_grad(const float* g_pred, const float* g_norm_in, const float* g_pos,
@@ -280,123 +243,98 @@ extern "C" int bsms_sim_input_grad(const float* g_pred, const float* g_norm_in, 
 
 namespace {
 
-// k_sim_unroll_bwd for the family of objectives (include/bsms_hip.h: bsms_sim_objective_bwd).  `sums` = [M | SE[0..C)] in fp64
+// k_sim_pair_bwd for the family of objectives (include/bsms_hip.h: bsms_sim_objective_bwd, _w).  `sums` = [M | SE[0..C)] in fp64
 // (bsms_error_sums); every thread forms the C per-channel coefficients G * a_c from it in fp64 and rounds each to fp32 once.
-// The carry and the way out through the de-normalisation are those of k_sim_unroll_bwd, op for op.  No guard for M == 0 or
-// loss == 0, as in k_sim_loss_bwd: the non-finite coefficient reaches the output.  The head (coefficients) and the tail (step weight, carry,
-// way out) of a row live in objective_row.h, shared with the edge objective's backward (ext/edge_objective.hip).
-// kWeighted (bsms_sim_objective_bwd_w): row r's loss gradient carries mu = m * row_weights[r % period], ONE fp32 product formed first,
-// so (d * mu) * coef is the unweighted (d * m) * coef whenever the weight is 1.  The mask of the carry and of the way out stays m.
-template <bool kWeighted>
-__device__ __forceinline__ void sim_objective_bwd_row(const float* pred, const float* target, const float* mask,
-                                                      const float* row_weights, int64_t weight_period, int64_t R, int C,
-                                                      const double* mean, const double* meansq, const double* eps,
-                                                      const double* in_mean, const double* in_meansq, const double* in_eps,
-                                                      const double* sums, const double* weights, int normalized, int rmse, float w,
-                                                      const float* g_pred_next, const float* g_norm_in_next, float* loss_out,
-                                                      float* chan_out, float* g_pred, float* grad_norm_pred) {
+// No guard for M == 0 or loss == 0, as in k_sim_pair_bwd: the non-finite coefficient reaches the output.  The head (coefficients) and
+// the tail (step weight, carry, way out) of a row live in objective_row.h, shared with the edge objective's backward
+// (ext/edge_objective.hip).  `row_weights` (bsms_sim_objective_bwd_w): row r's loss gradient carries mu = m * row_weights[r % period],
+// ONE fp32 product formed first, so (d * mu) * coef is the unweighted (d * m) * coef whenever the weight is 1; nullptr: mu IS m (no
+// product), the launch of bsms_sim_objective_bwd.  The mask of the carry and of the way out stays m.
+__global__ __launch_bounds__(256) void k_sim_objective_bwd(const float* pred, const float* target, const float* mask,
+                                                           const float* row_weights, int64_t weight_period, int64_t R, int C,
+                                                           int normalized, int rmse, const LossBwdArgs o) {
   const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  const double e = *eps;
+  const double* sums = static_cast<const double*>(o.sums);
+  const double e = *o.eps;
   const double MC = sums[0] * double(C);
   double sd[kMaxC], a[kMaxC];
   double Q = 0.0;
   for (int c = 0; c < C; ++c) {
-    const ObjectiveChannel ch = objective_channel(c, mean, meansq, e, sums, weights, normalized, MC);
+    const ObjectiveChannel ch = objective_channel(c, o.mean, o.meansq, e, sums, o.weights, normalized, MC);
     sd[c] = ch.sd;
     a[c] = ch.a;
-    if (r == 0 && chan_out) chan_out[c] = float(ch.term);
+    if (r == 0 && o.chan_out) o.chan_out[c] = float(ch.term);
     Q += ch.term;
   }
   const double loss = objective_loss(Q, rmse);
-  if (r == 0 && loss_out) *loss_out = float(loss);
+  if (r == 0 && o.loss_out) *o.loss_out = float(loss);
   if (r >= R) return;
   const double G = objective_scale(loss, MC, rmse);
   const float m = mask[r];
-  const float mu = kWeighted ? m * row_weights[r % weight_period] : m;
-  const bool carried = g_pred_next != nullptr && m != 0.f;
-  const double ie = g_pred_next ? *in_eps : 0.0;
+  const float mu = row_weights ? m * row_weights[r % weight_period] : m;
+  const LossBwdCarry carry = loss_bwd_carry(o, m);
   for (int c = 0; c < C; ++c) {
     const float coef = float(G * a[c]);
     const float gp = (pred[r * C + c] - target[r * C + c]) * mu * coef;
-    objective_tail(gp, w, m, carried, r, c, C, sd[c], in_mean, in_meansq, ie, g_pred_next, g_norm_in_next, g_pred, grad_norm_pred);
+    objective_tail(gp, m, carry, r, c, C, sd[c], o);
   }
 }
 
-// sim_objective_bwd_row for the robust objectives (include/bsms_hip.h: bsms_sim_robust_bwd).  `sums` = [M | S[0..C)]
+// k_sim_objective_bwd for the robust objectives (include/bsms_hip.h: bsms_sim_robust_bwd).  `sums` = [M | S[0..C)]
 // (bsms_robust_sums), loss = sum_c w_c S_c / (M C): linear in the sums, so the coefficient of a row is fl32(w_c / (M C s_c)) whatever
 // the sums hold, and only the loss-gradient term differs: psi(u) = sign(u) or clamp(u, -delta, delta) of u = double(d) / s_c takes
-// d's place.  The step weight, the carry and the way out through the de-normalisation are that function's lines, op for op.
-// `row_weights` == nullptr: mu IS m (no product), the kernel of an objective without node weights.
+// d's place.  mu and the tail are that kernel's.
 __global__ __launch_bounds__(256) void k_sim_robust_bwd(const float* pred, const float* target, const float* mask,
                                                         const float* row_weights, int64_t weight_period, int64_t R, int C,
-                                                        const double* mean, const double* meansq, const double* eps,
-                                                        const double* in_mean, const double* in_meansq, const double* in_eps,
-                                                        const double* sums, const double* weights, const double* delta,
-                                                        int normalized, int huber, float w, const float* g_pred_next,
-                                                        const float* g_norm_in_next, float* loss_out, float* chan_out, float* g_pred,
-                                                        float* grad_norm_pred) {
+                                                        const double* delta, int normalized, int huber, const LossBwdArgs o) {
   const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  const double e = *eps;
+  const double* sums = static_cast<const double*>(o.sums);
+  const double e = *o.eps;
   const double MC = sums[0] * double(C);
   double sd[kMaxC], sc[kMaxC], dl[kMaxC];
   float coef[kMaxC];
   double loss = 0.0;
   for (int c = 0; c < C; ++c) {
-    sd[c] = std_eps(mean[c], meansq[c], e);
+    sd[c] = std_eps(o.mean[c], o.meansq[c], e);
     sc[c] = normalized ? sd[c] : 1.0;
     dl[c] = huber ? delta[c] : 0.0;
-    const double wc = weights ? weights[c] : 1.0;
+    const double wc = o.weights ? o.weights[c] : 1.0;
     const double term = wc * sums[1 + c] / MC;
-    if (r == 0 && chan_out) chan_out[c] = float(term);
+    if (r == 0 && o.chan_out) o.chan_out[c] = float(term);
     loss += term;
     coef[c] = float(wc / (MC * sc[c]));
   }
-  if (r == 0 && loss_out) *loss_out = float(loss);
+  if (r == 0 && o.loss_out) *o.loss_out = float(loss);
   if (r >= R) return;
   const float m = mask[r];
   const float mu = row_weights ? m * row_weights[r % weight_period] : m;
-  const bool carried = g_pred_next != nullptr && m != 0.f;
-  const double ie = g_pred_next ? *in_eps : 0.0;
+  const LossBwdCarry carry = loss_bwd_carry(o, m);
   for (int c = 0; c < C; ++c) {
     const double u = double(pred[r * C + c] - target[r * C + c]) / sc[c];
     double psi = u;                                                     // |u| <= delta; u == 0 (sign(0) = 0); a NaN stays one
     if (huber) psi = u > dl[c] ? dl[c] : (u < -dl[c] ? -dl[c] : u);
     else if (u > 0.0) psi = 1.0;
     else if (u < 0.0) psi = -1.0;
-    float gp = float(psi) * mu * coef[c];
-    gp = w * gp;
-    if (carried) {
-      const float through_norm = float(double(g_norm_in_next[r * (C + 1) + c]) / std_eps(in_mean[c], in_meansq[c], ie));
-      const float g_state = g_pred_next[r * C + c] + through_norm;
-      gp = gp + g_state;
-    }
-    if (g_pred) g_pred[r * C + c] = gp;
-    const float gd = gp * m;
-    grad_norm_pred[r * C + c] = float(double(gd) * sd[c]);
+    objective_tail(float(psi) * mu * coef[c], m, carry, r, c, C, sd[c], o);
   }
 }
 
-__global__ __launch_bounds__(256) void k_sim_objective_bwd(const float* pred, const float* target, const float* mask, int64_t R,
-                                                           int C, const double* mean, const double* meansq, const double* eps,
-                                                           const double* in_mean, const double* in_meansq, const double* in_eps,
-                                                           const double* sums, const double* weights, int normalized, int rmse,
-                                                           float w, const float* g_pred_next, const float* g_norm_in_next,
-                                                           float* loss_out, float* chan_out, float* g_pred,
-                                                           float* grad_norm_pred) {
-  sim_objective_bwd_row<false>(pred, target, mask, nullptr, 1, R, C, mean, meansq, eps, in_mean, in_meansq, in_eps, sums, weights,
-                               normalized, rmse, w, g_pred_next, g_norm_in_next, loss_out, chan_out, g_pred, grad_norm_pred);
-}
-
-__global__ __launch_bounds__(256) void k_sim_objective_bwd_w(const float* pred, const float* target, const float* mask,
-                                                             const float* row_weights, int64_t weight_period, int64_t R, int C,
-                                                             const double* mean, const double* meansq, const double* eps,
-                                                             const double* in_mean, const double* in_meansq, const double* in_eps,
-                                                             const double* sums, const double* weights, int normalized, int rmse,
-                                                             float w, const float* g_pred_next, const float* g_norm_in_next,
-                                                             float* loss_out, float* chan_out, float* g_pred,
-                                                             float* grad_norm_pred) {
-  sim_objective_bwd_row<true>(pred, target, mask, row_weights, weight_period, R, C, mean, meansq, eps, in_mean, in_meansq, in_eps, sums,
-                              weights, normalized, rmse, w, g_pred_next, g_norm_in_next, loss_out, chan_out, g_pred, grad_norm_pred);
+// bsms_sim_objective_bwd and its `_w` form (`weighted`: a weight per row, required, with its period): one list of checks -- each
+// weighted argument directly behind the check it belongs to -- and one launch.
+int sim_objective_bwd(const char* who, bool weighted, const float* pred, const float* target, const float* mask, const float* row_weights,
+                      int64_t weight_period, int64_t R, int64_t C, int space, int kind, const LossBwdArgs& o, bsms_stream_t stream) {
+  BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "%s: R=%lld C=%lld", who, (long long)R, (long long)C);
+  if (int rc = check_space_kind(who, space, kind)) return rc;
+  BSMS_REQUIRE(pred && target && mask && (row_weights || !weighted) && o.mean && o.meansq && o.eps && o.sums && o.grad_norm_pred,
+               BSMS_E_INVALID_ARG, "%s: null argument", who);
+  BSMS_REQUIRE(!weighted || (weight_period >= 1 && weight_period <= R && R % weight_period == 0), BSMS_E_INVALID_ARG,
+               "%s: weight_period=%lld does not divide R=%lld", who, (long long)weight_period, (long long)R);
+  if (int rc = check_carry(who, o.g_pred_next, o.g_norm_in_next, o.in_mean, o.in_meansq, o.in_eps, o.g_pred)) return rc;
+  hipLaunchKernelGGL(k_sim_objective_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask,
+                     weighted ? row_weights : nullptr, weighted ? weight_period : 1, R, (int)C, int(space == BSMS_LOSS_NORMALIZED),
+                     int(kind == BSMS_LOSS_RMSE), o);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
 }
 
 }  // namespace
@@ -407,50 +345,22 @@ extern "C" int bsms_sim_objective_bwd(const float* pred, const float* target, co
                                       const double* channel_weights, int space, int kind, float w, const float* g_pred_next,
                                       const float* g_norm_in_next, float* loss_out, float* chan_out, float* g_pred,
                                       float* grad_norm_pred, bsms_stream_t stream) {
-  BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "sim_objective_bwd: R=%lld C=%lld", (long long)R, (long long)C);
-  BSMS_REQUIRE((space == BSMS_LOSS_PHYSICAL || space == BSMS_LOSS_NORMALIZED) && (kind == BSMS_LOSS_MSE || kind == BSMS_LOSS_RMSE),
-               BSMS_E_UNSUPPORTED, "sim_objective_bwd: space=%d kind=%d (each 0 or 1)", space, kind);
-  BSMS_REQUIRE(pred && target && mask && mean && meansq && std_eps_dev && sums && grad_norm_pred, BSMS_E_INVALID_ARG,
-               "sim_objective_bwd: null argument");
-  BSMS_REQUIRE((g_pred_next == nullptr) == (g_norm_in_next == nullptr), BSMS_E_INVALID_ARG,
-               "sim_objective_bwd: the carried pair (g_pred_next, g_norm_in_next) is given together or not at all");
-  BSMS_REQUIRE(!g_pred_next || (in_mean && in_meansq && in_std_eps_dev), BSMS_E_INVALID_ARG,
-               "sim_objective_bwd: a carried gradient needs the input normaliser's statistics");
-  BSMS_REQUIRE(!g_pred || (g_pred != g_pred_next), BSMS_E_INVALID_ARG, "sim_objective_bwd: g_pred aliases g_pred_next");
-  hipLaunchKernelGGL(k_sim_objective_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask, R,
-                     (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, channel_weights,
-                     int(space == BSMS_LOSS_NORMALIZED), int(kind == BSMS_LOSS_RMSE), w, g_pred_next, g_norm_in_next, loss_out,
-                     chan_out, g_pred, grad_norm_pred);
-  BSMS_LAUNCH_CHECK();
-  return BSMS_OK;
+  return sim_objective_bwd("sim_objective_bwd", false, pred, target, mask, nullptr, 1, R, C, space, kind,
+                           {mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, channel_weights, w, g_pred_next,
+                            g_norm_in_next, loss_out, chan_out, g_pred, grad_norm_pred},
+                           stream);
 }
 
-// bsms_sim_objective_bwd with a weight per row (include/bsms_hip.h): the checks of that entry in its order, each followed at once by
-// the weighted argument that belongs to it.
 extern "C" int bsms_sim_objective_bwd_w(const float* pred, const float* target, const float* mask, const float* row_weights,
                                         int64_t weight_period, int64_t R, int64_t C, const double* mean, const double* meansq,
                                         const double* std_eps_dev, const double* in_mean, const double* in_meansq,
                                         const double* in_std_eps_dev, const double* sums, const double* channel_weights, int space,
                                         int kind, float w, const float* g_pred_next, const float* g_norm_in_next, float* loss_out,
                                         float* chan_out, float* g_pred, float* grad_norm_pred, bsms_stream_t stream) {
-  BSMS_REQUIRE(R >= 1 && C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "sim_objective_bwd_w: R=%lld C=%lld", (long long)R, (long long)C);
-  BSMS_REQUIRE((space == BSMS_LOSS_PHYSICAL || space == BSMS_LOSS_NORMALIZED) && (kind == BSMS_LOSS_MSE || kind == BSMS_LOSS_RMSE),
-               BSMS_E_UNSUPPORTED, "sim_objective_bwd_w: space=%d kind=%d (each 0 or 1)", space, kind);
-  BSMS_REQUIRE(pred && target && mask && row_weights && mean && meansq && std_eps_dev && sums && grad_norm_pred, BSMS_E_INVALID_ARG,
-               "sim_objective_bwd_w: null argument");
-  BSMS_REQUIRE(weight_period >= 1 && weight_period <= R && R % weight_period == 0, BSMS_E_INVALID_ARG,
-               "sim_objective_bwd_w: weight_period=%lld does not divide R=%lld", (long long)weight_period, (long long)R);
-  BSMS_REQUIRE((g_pred_next == nullptr) == (g_norm_in_next == nullptr), BSMS_E_INVALID_ARG,
-               "sim_objective_bwd_w: the carried pair (g_pred_next, g_norm_in_next) is given together or not at all");
-  BSMS_REQUIRE(!g_pred_next || (in_mean && in_meansq && in_std_eps_dev), BSMS_E_INVALID_ARG,
-               "sim_objective_bwd_w: a carried gradient needs the input normaliser's statistics");
-  BSMS_REQUIRE(!g_pred || (g_pred != g_pred_next), BSMS_E_INVALID_ARG, "sim_objective_bwd_w: g_pred aliases g_pred_next");
-  hipLaunchKernelGGL(k_sim_objective_bwd_w, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask,
-                     row_weights, weight_period, R, (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums,
-                     channel_weights, int(space == BSMS_LOSS_NORMALIZED), int(kind == BSMS_LOSS_RMSE), w, g_pred_next, g_norm_in_next,
-                     loss_out, chan_out, g_pred, grad_norm_pred);
-  BSMS_LAUNCH_CHECK();
-  return BSMS_OK;
+  return sim_objective_bwd("sim_objective_bwd_w", true, pred, target, mask, row_weights, weight_period, R, C, space, kind,
+                           {mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, channel_weights, w, g_pred_next,
+                            g_norm_in_next, loss_out, chan_out, g_pred, grad_norm_pred},
+                           stream);
 }
 
 // The robust objectives' backward (include/bsms_hip.h): the checks of bsms_sim_objective_bwd_w in its order, with `row_weights`
@@ -470,15 +380,12 @@ extern "C" int bsms_sim_robust_bwd(const float* pred, const float* target, const
                BSMS_E_INVALID_ARG, "sim_robust_bwd: null argument");
   BSMS_REQUIRE(!row_weights || (weight_period >= 1 && weight_period <= R && R % weight_period == 0), BSMS_E_INVALID_ARG,
                "sim_robust_bwd: weight_period=%lld does not divide R=%lld", (long long)weight_period, (long long)R);
-  BSMS_REQUIRE((g_pred_next == nullptr) == (g_norm_in_next == nullptr), BSMS_E_INVALID_ARG,
-               "sim_robust_bwd: the carried pair (g_pred_next, g_norm_in_next) is given together or not at all");
-  BSMS_REQUIRE(!g_pred_next || (in_mean && in_meansq && in_std_eps_dev), BSMS_E_INVALID_ARG,
-               "sim_robust_bwd: a carried gradient needs the input normaliser's statistics");
-  BSMS_REQUIRE(!g_pred || (g_pred != g_pred_next), BSMS_E_INVALID_ARG, "sim_robust_bwd: g_pred aliases g_pred_next");
+  if (int rc = check_carry("sim_robust_bwd", g_pred_next, g_norm_in_next, in_mean, in_meansq, in_std_eps_dev, g_pred)) return rc;
+  const LossBwdArgs o{mean, meansq, std_eps_dev, in_mean, in_meansq, in_std_eps_dev, sums, channel_weights, w, g_pred_next, g_norm_in_next,
+                      loss_out, chan_out, g_pred, grad_norm_pred};
   hipLaunchKernelGGL(k_sim_robust_bwd, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, as_stream(stream), pred, target, mask,
-                     row_weights, row_weights ? weight_period : 1, R, (int)C, mean, meansq, std_eps_dev, in_mean, in_meansq,
-                     in_std_eps_dev, sums, channel_weights, delta, int(space == BSMS_LOSS_NORMALIZED), int(rkind == BSMS_ROBUST_HUBER), w,
-                     g_pred_next, g_norm_in_next, loss_out, chan_out, g_pred, grad_norm_pred);
+                     row_weights, row_weights ? weight_period : 1, R, (int)C, delta, int(space == BSMS_LOSS_NORMALIZED),
+                     int(rkind == BSMS_ROBUST_HUBER), o);
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }

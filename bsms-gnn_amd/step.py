@@ -54,6 +54,7 @@ import torch
 import torch.distributed as dist
 
 from . import _abi
+from .objective import EDGE_WEIGHTINGS, KINDS, ROBUST_KINDS, SPACES, Objective
 from .ops import BWD_FROZEN_BF16, BWD_RECOMPUTE, FWD_LEAN, PRECISIONS, _param_ptrs, _stream
 
 
@@ -153,7 +154,6 @@ class FusedStep:
         if not input_grad and not any(p.requires_grad for q in _mlps(model) for p in q.flat_params()):
             raise ValueError("FusedStep: nothing is trainable and input_grad is off: the step would compute nothing")
         self._guard_params = [q.flat_params()[0] for q in _mlps(model)]
-        from .objective import Objective
         self.objective = (Objective() if objective is None else objective).bind(model.cfg.out_dim)
         self._obj = None if self.objective.is_default else self.objective      # None: the default route, untouched
         if isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1:
@@ -209,8 +209,11 @@ class FusedStep:
                                          # launches per step instead of one); every pack, and so every result, is the same bit for bit
 
     def _world(self):
-        w = dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
-        return 2 if (w == 1 and self.collectives_at_world_one and dist.is_available() and dist.is_initialized()) else w
+        return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
+
+    def _collectives(self):
+        """The step issues its all-reduces: in a world larger than one, or (`collectives_at_world_one`) in a process group of one rank."""
+        return self._world() > 1 or (self.collectives_at_world_one and dist.is_available() and dist.is_initialized())
 
     def _unpack(self, data, consistent):
         if consistent:
@@ -445,36 +448,66 @@ class FusedStep:
                               PRECISIONS[b["prec"]], s), "bsms_bsgmp_fwd")     # (the lean forward packs per call: _pack_group)
         ck(L.bsms_mlp_fwd_ex(b["h1"].data_ptr(), R, D, D, C, H, 0, t["dec"][0][0], b["norm_pred"].data_ptr(), b["s_dec"].data_ptr(),
                              work.data_ptr(), reuse, s), "bsms_mlp_fwd(decode)")
-        if self._obj is None:
-            ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), tar.data_ptr(), R, C, p,
-                                   no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["pred"].data_ptr(),
-                                   _ptr(next_in), _ptr(ic), b["sums"].data_ptr(), work.data_ptr(), s), "bsms_sim_epilogue")
-            return
-        # another objective: no fp32 pair from the epilogue; one segment of R rows through bsms_error_sums instead (fp64, deterministic)
-        ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), None, R, C, p,
+        own = self._obj is None               # the default route: the epilogue forms the fp32 pair itself
+        ck(L.bsms_sim_epilogue(b["norm_pred"].data_ptr(), node_in.data_ptr(), mask.data_ptr(), tar.data_ptr() if own else None, R, C, p,
                                no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["pred"].data_ptr(),
-                               _ptr(next_in), _ptr(ic), None, work.data_ptr(), s), "bsms_sim_epilogue")
-        if self._obj.is_robust:               # [M | S] into the first 1 + C fields of the same row; the rest of the row is not written
-            from .objective import ROBUST_KINDS, SPACES
-            nw = b["nw"].data_ptr() if self._obj.node_weighted else None
-            ck(L.bsms_robust_sums(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), nw, 1, R, C, R, R, R, R, no._E_data.data_ptr(),
-                                  no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), _ptr(self._obj_delta), SPACES[self._obj.space],
-                                  ROBUST_KINDS[self._obj.kind], b["osums"].data_ptr(), 1 + 3 * C, b["work_obj"].data_ptr(), s),
-               "bsms_robust_sums")
+                               _ptr(next_in), _ptr(ic), b["sums"].data_ptr() if own else None, work.data_ptr(), s), "bsms_sim_epilogue")
+        self._objective_sums(b, tar, mask, B, N)
+
+    def _objective_sums(self, b, tar, mask, B, N):
+        """The sums of another objective than the default, behind the epilogue: one segment of R rows into the step's fp64 row
+        (deterministic).  Robust: [M | S] into the first 1 + C fields, the rest of the row is not written.  Node weights: mu = mask * weight
+        in the mask's place; the row [M | SE] downstream is none the wiser.  An edge term: B segments of N rows through the level-0 plan
+        (a variable-mesh batch: one, the union's), folded into the tail of the row."""
+        o = self._obj
+        if o is None:
             return
-        if self._obj.node_weighted:           # mu = mask * weight in the mask's place; the row [M | SE] downstream is none the wiser
-            ck(L.bsms_error_sums_w(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), b["nw"].data_ptr(), 1, R, C, R, R, R, R,
-                                   b["osums"].data_ptr(), b["work_obj"].data_ptr(), s), "bsms_error_sums_w")
-            return
-        ck(L.bsms_error_sums(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), 1, R, C, R, R, R, b["osums"].data_ptr(),
-                             b["work_obj"].data_ptr(), s), "bsms_error_sums")
-        if self._edge:                        # B segments of N rows through the level-0 plan (a variable-mesh batch: one, the union's)
-            from .objective import EDGE_WEIGHTINGS
-            o = self._obj
-            ck(L.bsms_edge_diff_sums(b["plan0"], 0, N, b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), b["pos"].data_ptr(), B, C, p,
-                                     EDGE_WEIGHTINGS.index(o.edge_weighting), N, N, N, N, b["esums"].data_ptr(), b["work_edge"].data_ptr(), s),
-               "bsms_edge_diff_sums")
-            ck(_abi.ext().bsms_edge_diff_fold(b["esums"].data_ptr(), B, C, b["osums"][1 + 3 * C:].data_ptr(), s), "bsms_edge_diff_fold")
+        m, L, s, ck = self.model, _abi.lib(), _stream(), _abi.check
+        C, p, R, no = m.cfg.out_dim, m.pos_dim, b["R"], m._targetNormalizer
+        rows = (b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr())
+        nw = b["nw"].data_ptr() if o.node_weighted else None
+        if o.is_robust:
+            ck(L.bsms_robust_sums(*rows, nw, 1, R, C, R, R, R, R, no._E_data.data_ptr(), no._E_data_squared.data_ptr(),
+                                  no.std_eps.data_ptr(), _ptr(self._obj_delta), SPACES[o.space], ROBUST_KINDS[o.kind], b["osums"].data_ptr(),
+                                  1 + 3 * C, b["work_obj"].data_ptr(), s), "bsms_robust_sums")
+        elif o.node_weighted:
+            ck(L.bsms_error_sums_w(*rows, nw, 1, R, C, R, R, R, R, b["osums"].data_ptr(), b["work_obj"].data_ptr(), s), "bsms_error_sums_w")
+        else:
+            ck(L.bsms_error_sums(*rows, 1, R, C, R, R, R, b["osums"].data_ptr(), b["work_obj"].data_ptr(), s), "bsms_error_sums")
+            if self._edge:
+                ck(L.bsms_edge_diff_sums(b["plan0"], 0, N, *rows, b["pos"].data_ptr(), B, C, p, EDGE_WEIGHTINGS.index(o.edge_weighting),
+                                         N, N, N, N, b["esums"].data_ptr(), b["work_edge"].data_ptr(), s), "bsms_edge_diff_sums")
+                ck(_abi.ext().bsms_edge_diff_fold(b["esums"].data_ptr(), B, C, b["osums"][1 + 3 * C:].data_ptr(), s), "bsms_edge_diff_fold")
+
+    def _loss_gradient(self, b, tar, mask, chain, B, N):
+        """The head of a backward: the loss of the step and its gradient w.r.t. the decoder's output, `g_np`, from the entry of the
+        step's objective (DESIGN.md 4.24) -- the default: bsms_sim_loss_bwd, or bsms_sim_unroll_bwd with a `chain`; robust;
+        with an edge term; squared, with or without node weights.  Without a `chain`: w = 1, nothing carried, no g_pred."""
+        m, L, s, ck = self.model, _abi.lib(), _stream(), _abi.check
+        C, p, R, o = m.cfg.out_dim, m.pos_dim, b["R"], self._obj
+        c = chain or dict(w=1.0, g_pred_next=None, g_nin_next=None, g_pred=None)
+        stats = lambda n: (n._E_data.data_ptr(), n._E_data_squared.data_ptr(), n.std_eps.data_ptr())
+        rows = (b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr())
+        out_stats, both_stats = stats(m._targetNormalizer), (*stats(m._targetNormalizer), *stats(m._inputNormalizer))
+        carried = (c["w"], _ptr(c["g_pred_next"]), _ptr(c["g_nin_next"]), b["loss"].data_ptr())
+        outs = (_ptr(c["g_pred"]), b["g_np"].data_ptr(), s)
+        if o is None and chain is None:
+            ck(L.bsms_sim_loss_bwd(*rows, R, C, *out_stats, b["sums"].data_ptr(), b["loss"].data_ptr(), b["g_np"].data_ptr(), s), "bsms_sim_loss_bwd")
+        elif o is None:
+            ck(L.bsms_sim_unroll_bwd(*rows, R, C, *both_stats, b["sums"].data_ptr(), *carried, *outs), "bsms_sim_unroll_bwd")
+        elif o.is_robust:
+            ck(L.bsms_sim_robust_bwd(*rows, b["nw"].data_ptr() if o.node_weighted else None, R, R, C, *both_stats, b["osums"].data_ptr(),
+                                     _ptr(self._obj_w), _ptr(self._obj_delta), SPACES[o.space], ROBUST_KINDS[o.kind], *carried,
+                                     b["chan"].data_ptr(), *outs), "bsms_sim_robust_bwd")
+        elif self._edge:
+            ck(_abi.ext().bsms_sim_edge_objective_bwd(b["plan0"], N, B, *rows, b["pos"].data_ptr(), C, p, EDGE_WEIGHTINGS.index(o.edge_weighting),
+                                                      *both_stats, b["osums"].data_ptr(), b["osums"][1 + 3 * C:].data_ptr(), _ptr(self._obj_w),
+                                                      SPACES[o.space], KINDS[o.kind], o.edge_weight, *carried, b["parts"].data_ptr(),
+                                                      b["chan"].data_ptr(), *outs), "bsms_sim_edge_objective_bwd")
+        else:                                         # node weights: the same call with the step's weights behind the mask: one per row, period R
+            name, nw = ("bsms_sim_objective_bwd_w", (b["nw"].data_ptr(), R)) if o.node_weighted else ("bsms_sim_objective_bwd", ())
+            ck(getattr(L, name)(*rows, *nw, R, C, *both_stats, b["osums"].data_ptr(), _ptr(self._obj_w), SPACES[o.space], KINDS[o.kind],
+                                *carried, b["chan"].data_ptr(), *outs), name)
 
     def _backward(self, b, tar, mask, ews, B, N, events=None, chain=None, tabs=None):
         """`events`: (pointer array, keep-alive) of 2L+1 hipEvent_t for bsms_bsgmp_bwd_ev, or None.
@@ -486,56 +519,11 @@ class FusedStep:
         C, p, D, H = m.cfg.out_dim, m.pos_dim, m.cfg.latent_dim, m.cfg.hidden_layer
         R, t = b["R"], ((tabs or self._tabs) if chain is None else chain["tabs"])
         work = b["work"]
-        no = m._targetNormalizer
         ck = _abi.check
         ig = b["ig"] if self._input_grad else None
         if ig is not None and chain is None:          # the single step as a chain of one: w = 1, nothing carried, g_pred kept
             chain = dict(w=1.0, tabs=t, g_pred_next=None, g_nin_next=None, g_pred=ig["g_pred"], grad_x=ig["g_nin"], first_step=1, overwrite=1)
-        if self._obj is not None and self._obj.is_robust:
-            from .objective import ROBUST_KINDS, SPACES
-            ni, o = m._inputNormalizer, self._obj
-            c = chain or dict(w=1.0, g_pred_next=None, g_nin_next=None, g_pred=None)
-            ck(L.bsms_sim_robust_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), b["nw"].data_ptr() if o.node_weighted else None,
-                                     R, R, C, no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(),
-                                     ni._E_data.data_ptr(), ni._E_data_squared.data_ptr(), ni.std_eps.data_ptr(), b["osums"].data_ptr(),
-                                     _ptr(self._obj_w), _ptr(self._obj_delta), SPACES[o.space], ROBUST_KINDS[o.kind], c["w"],
-                                     _ptr(c["g_pred_next"]), _ptr(c["g_nin_next"]), b["loss"].data_ptr(), b["chan"].data_ptr(),
-                                     _ptr(c["g_pred"]), b["g_np"].data_ptr(), s), "bsms_sim_robust_bwd")
-        elif self._obj is not None and self._edge:
-            from .objective import EDGE_WEIGHTINGS, KINDS, SPACES
-            ni, o = m._inputNormalizer, self._obj
-            c = chain or dict(w=1.0, g_pred_next=None, g_nin_next=None, g_pred=None)
-            ck(_abi.ext().bsms_sim_edge_objective_bwd(b["plan0"], N, B, b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), b["pos"].data_ptr(), C, p,
-                                             EDGE_WEIGHTINGS.index(o.edge_weighting), no._E_data.data_ptr(), no._E_data_squared.data_ptr(),
-                                             no.std_eps.data_ptr(), ni._E_data.data_ptr(), ni._E_data_squared.data_ptr(),
-                                             ni.std_eps.data_ptr(), b["osums"].data_ptr(), b["osums"][1 + 3 * C:].data_ptr(), _ptr(self._obj_w),
-                                             SPACES[o.space], KINDS[o.kind], o.edge_weight, c["w"], _ptr(c["g_pred_next"]),
-                                             _ptr(c["g_nin_next"]), b["loss"].data_ptr(), b["parts"].data_ptr(), b["chan"].data_ptr(),
-                                             _ptr(c["g_pred"]), b["g_np"].data_ptr(), s), "bsms_sim_edge_objective_bwd")
-        elif self._obj is not None:
-            from .objective import KINDS, SPACES
-            ni, o = m._inputNormalizer, self._obj
-            c = chain or dict(w=1.0, g_pred_next=None, g_nin_next=None, g_pred=None)
-            head = (b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr())
-            tail = (R, C, no._E_data.data_ptr(), no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), ni._E_data.data_ptr(),
-                    ni._E_data_squared.data_ptr(), ni.std_eps.data_ptr(), b["osums"].data_ptr(), _ptr(self._obj_w), SPACES[o.space],
-                    KINDS[o.kind], c["w"], _ptr(c["g_pred_next"]), _ptr(c["g_nin_next"]), b["loss"].data_ptr(), b["chan"].data_ptr(),
-                    _ptr(c["g_pred"]), b["g_np"].data_ptr(), s)
-            if o.node_weighted:                       # the same call with the step's weights behind the mask: one per row, period R
-                ck(L.bsms_sim_objective_bwd_w(*head, b["nw"].data_ptr(), R, *tail), "bsms_sim_objective_bwd_w")
-            else:
-                ck(L.bsms_sim_objective_bwd(*head, *tail), "bsms_sim_objective_bwd")
-        elif chain is None:
-            ck(L.bsms_sim_loss_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), R, C, no._E_data.data_ptr(),
-                                   no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), b["sums"].data_ptr(), b["loss"].data_ptr(),
-                                   b["g_np"].data_ptr(), s), "bsms_sim_loss_bwd")
-        else:
-            ni = m._inputNormalizer
-            ck(L.bsms_sim_unroll_bwd(b["pred"].data_ptr(), tar.data_ptr(), mask.data_ptr(), R, C, no._E_data.data_ptr(),
-                                     no._E_data_squared.data_ptr(), no.std_eps.data_ptr(), ni._E_data.data_ptr(),
-                                     ni._E_data_squared.data_ptr(), ni.std_eps.data_ptr(), b["sums"].data_ptr(), chain["w"],
-                                     _ptr(chain["g_pred_next"]), _ptr(chain["g_nin_next"]), b["loss"].data_ptr(),
-                                     _ptr(chain["g_pred"]), b["g_np"].data_ptr(), s), "bsms_sim_unroll_bwd")
+        self._loss_gradient(b, tar, mask, chain, B, N)
         ck(L.bsms_mlp_bwd_ex(b["h1"].data_ptr(), b["g_np"].data_ptr(), R, D, D, C, H, 0, t["dec"][0][0], b["s_dec"].data_ptr(),
                              b["work_dec"].data_ptr(), b["gh1"].data_ptr(), t["dec"][1][0], 1, s), "bsms_mlp_bwd(decode)")   # 1 = BSMS_BWD_DEFER_JOIN
         ewp, keep = _abi.ptr_array([e.data_ptr() for e in ews])
@@ -581,21 +569,21 @@ class FusedStep:
         b = self._buffers(B, N, plans, node_in.device)
         self._set_node_weights(b, node_weights, B, N)
         self._decide_packs()
-        world = self._world()
+        coll = self._collectives()
         if self.accumulate > 1:
-            return self._micro_batch(b, node_in, tar, mask, later_targets, ews, B, N, world, consistent)
+            return self._micro_batch(b, node_in, tar, mask, later_targets, ews, B, N, coll, consistent)
         if self.unroll > 1:
-            return self._unrolled(b, node_in, tar, mask, later_targets, ews, B, N, world, consistent)
+            return self._unrolled(b, node_in, tar, mask, later_targets, ews, B, N, coll, consistent)
         if self.use_graph:
-            return self._replay(b, node_in, tar, mask, ews, B, N, world)
+            return self._replay(b, node_in, tar, mask, ews, B, N, coll)
         self._forward(b, node_in, tar, mask, ews, B, N)
-        if world > 1:
+        if coll:
             dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
-        if world > 1 and self._any_live and self._overlap_now():
+        if coll and self._any_live and self._overlap_now():
             self._backward_overlapped(b, tar, mask, ews, B, N)
         else:
             self._backward(b, tar, mask, ews, B, N)
-            if world > 1 and self._any_live:
+            if coll and self._any_live:
                 dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         self._probe_end()
         return b["loss"][0].clone()       # the static buffer is overwritten by the next step: hand out a copy (4 bytes)
@@ -668,7 +656,7 @@ class FusedStep:
             raise RuntimeError(f"later_targets is on {later.device}, node_in on {node_in.device}")
         return later if (later.is_contiguous() and later.dtype == torch.float32) else later.contiguous().float()
 
-    def _unrolled(self, b, node_in, tar, mask, later, ews, B, N, world, consistent, into=None):
+    def _unrolled(self, b, node_in, tar, mask, later, ews, B, N, coll, consistent, into=None):
         """`into` (gradient accumulation): (tables, flat buffer) that receive the K-step sum instead of grads.flat, and no gradient
         all-reduce here; the steps that are folded in then go through `_tabs_scratch` / `_gscratch` as ever."""
         K, L, s = self.unroll, _abi.lib(), _stream()
@@ -683,7 +671,7 @@ class FusedStep:
             nxt = steps[k + 1]["in"] if k + 1 < K else None
             self._forward(bk, node_in if k == 0 else bk["in"], tars[k], mask, ews, B, N, next_in=nxt, ic=None if nxt is None else node_in,
                           pack=False)
-        if world > 1:
+        if coll:
             dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
         # K backwards, k = K-1 .. 0.  The first one run writes grads.flat itself, the others the scratch buffer, folded in after
         # the join: the deferred weight-gradient lanes of step k still write it (and read work / work_enc / work_dec) until then
@@ -699,18 +687,17 @@ class FusedStep:
             self._backward(bk, tars[k], mask, ews, B, N, chain=chain)          # ends with bsms_side_lanes_join
             if not last and self._any_live:
                 _abi.check(L.bsms_grad_accumulate(flat_sum.data_ptr(), self._gscratch.data_ptr(), n, 0, s), "bsms_grad_accumulate")
-        if world > 1 and self._any_live and into is None:
+        if coll and self._any_live and into is None:
             dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         return torch.dot(b["loss_all"], self._wts)
 
     # ------------------------------------------------------------------------------------------------ gradient accumulation
-    def _micro_batch(self, b, node_in, tar, mask, later, ews, B, N, world, consistent):
+    def _micro_batch(self, b, node_in, tar, mask, later, ews, B, N, coll, consistent):
         """One micro-batch of a cycle of `accumulate` (DESIGN.md 4.17).  Micro-batch 0 is the plain (or unrolled) step into grads.flat;
         micro-batch t >= 1 writes its whole gradient into the scratch flat buffer, and behind the join bsms_accum_coef forms (a, b)
         on the device from the (all-reduced) loss sums and bsms_grad_fold leaves a * grads.flat + b * scratch in grads.flat.  The host
         reads nothing back.  Data parallel: every rank folds with the same global coefficients; ONE all-reduce of the flat buffer
         after the last fold of the cycle."""
-        from .objective import KINDS, SPACES
         L, s, K = _abi.lib(), _stream(), self.unroll
         dev = node_in.device
         if self._micro >= self.accumulate:            # the (M+1)-th call starts a new cycle by itself
@@ -721,11 +708,11 @@ class FusedStep:
                              loss=torch.zeros(K, device=dev))
         if K > 1:                                     # t >= 1: the K-step sum in _gsum, the folded-in steps through _gscratch
             into = (self._tabs, self.grads.flat) if t == 0 else (self._tabs_sum, self._gsum)
-            loss = self._unrolled(b, node_in, tar, mask, later, ews, B, N, world, consistent, into=into)
+            loss = self._unrolled(b, node_in, tar, mask, later, ews, B, N, coll, consistent, into=into)
             g = self._gsum
         else:
             self._forward(b, node_in, tar, mask, ews, B, N)
-            if world > 1:
+            if coll:
                 dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
             self._backward(b, tar, mask, ews, B, N, tabs=None if t == 0 else self._tabs_scratch)       # ends with bsms_side_lanes_join
             loss, g = b["loss"][0].clone(), self._gscratch
@@ -743,7 +730,7 @@ class FusedStep:
             _abi.check(L.bsms_grad_fold(self.grads.flat.data_ptr(), g.data_ptr(), self.grads.flat.numel(), self._acc["coef"].data_ptr(), s),
                        "bsms_grad_fold")
         self._micro = t + 1
-        if self.ready and world > 1 and self._any_live:
+        if self.ready and coll and self._any_live:
             dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         return loss
 
@@ -943,7 +930,7 @@ class FusedStep:
         """[B,N,C] prediction of the last step (a static buffer: clone it to keep it)."""
         return self._buf["pred"]
 
-    def _replay(self, b, node_in, tar, mask, ews, B, N, world):
+    def _replay(self, b, node_in, tar, mask, ews, B, N, coll):
         if b["in_static"] is None:
             b["in_static"] = (torch.empty_like(node_in), torch.empty_like(tar), torch.empty_like(mask))
             self._graphs = None
@@ -967,10 +954,10 @@ class FusedStep:
             self._graphs = (gf, gb, ews)              # the graphs hold raw pointers: keep what they point at alive
         gf, gb, _ = self._graphs
         gf.replay()
-        if world > 1:
+        if coll:
             dist.all_reduce(self._loss_sums(b), op=dist.ReduceOp.SUM, group=self.group)
         gb.replay()
-        if world > 1 and self._any_live:
+        if coll and self._any_live:
             dist.all_reduce(self.grads.flat, op=dist.ReduceOp.SUM, group=self.group)
         return b["loss"][0].clone()
 
@@ -1003,7 +990,6 @@ def input_gradient(model, data, consistent=True, later_targets=None, step_weight
 
     `node_weights`: FusedStep's, for an `objective` with `node_weighted`."""
     from .dp import GradBuckets
-    from .objective import Objective
     K = 1 if later_targets is None else int(later_targets.shape[0]) + 1
     objective = Objective() if objective is None else objective
     if not isinstance(recompute, bool):
