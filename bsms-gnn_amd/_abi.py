@@ -160,6 +160,20 @@ EXT_SIGNATURES = {
 }
 
 
+# the second companion library libbsms_hip_stats.so: name -> (restype, argtypes); one entry per declaration in include/bsms_hip_stats.h
+STATS_LIB_PATH = os.path.join(_HERE, "libbsms_hip_stats.so")
+STATS_SIGNATURES = {
+    "bsms_moment_work_bytes": (c_size_t, [c_i64]),
+    "bsms_moment_sums": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
+    "bsms_moment_fold": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p]),
+}
+
+
+class MomentTraj(C.Structure):
+    """bsms_moment_traj (include/bsms_hip_stats.h)."""
+    _fields_ = [("state", c_void_p), ("type", c_void_p), ("n", c_i64), ("frame0", c_i64), ("frames", c_i64), ("type_stride", c_i64)]
+
+
 class WgradJob(C.Structure):
     """bsms_wgrad_job (include/bsms_hip.h)."""
     _fields_ = [("G", c_void_p), ("A", c_void_p), ("dW", c_void_p), ("db", c_void_p), ("R", c_i64),
@@ -213,6 +227,26 @@ def ext():
             fn.restype, fn.argtypes = res, args
         _ext = handle
     return _ext
+
+
+_stats = None
+
+
+def stats():
+    """Load the statistics library (once), behind libbsms_hip.so, which it links against.  Raises if it has not been built.  Only the
+    dataset statistics (ops.moment_sums / moment_fold) call this: a process that never asks for them never loads the library."""
+    global _stats
+    if _stats is None:
+        lib()
+        if not os.path.exists(STATS_LIB_PATH):
+            raise BsmsError(f"{STATS_LIB_PATH} not found: build it with `python bsms-gnn_amd/build.py` (or __graft_entry__.build()); "
+                            "there is no CPU/PyTorch fallback")
+        handle = C.CDLL(STATS_LIB_PATH)
+        for name, (res, args) in STATS_SIGNATURES.items():
+            fn = getattr(handle, name)  # AttributeError if the symbol is missing
+            fn.restype, fn.argtypes = res, args
+        _stats = handle
+    return _stats
 
 
 def check(rc, what):

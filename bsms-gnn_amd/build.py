@@ -10,13 +10,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libbsms_hip.so")
-EXT_LIB = os.path.join(HERE, "libbsms_hip_ext.so")      # the companion library (include/bsms_hip_ext.h): entries behind libbsms_hip.so's closed surface
-EXT_SOURCES = [os.path.join("ext", "edge_objective.hip")]
+# the companion libraries (name, sources): entries behind libbsms_hip.so's closed surface, each linked against it
+# (include/bsms_hip_ext.h, include/bsms_hip_stats.h)
+COMPANIONS = [("libbsms_hip_ext.so", [os.path.join("ext", "edge_objective.hip")]),
+              ("libbsms_hip_stats.so", [os.path.join("stats", "moments.hip")])]
+COMPANION_SOURCES = [src for _, srcs in COMPANIONS for src in srcs]
 SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "chain_d32.hip", "chain_d64.hip", "chain_d96.hip", "chain_d128.hip", "chain_d160.hip", "chain_d192.hip", "chain_d224.hip",
            "chain_d256.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "mlp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip", "batch.hip", "errsum.hip", "edgediff.hip"]
 # chain.hip: prepack + dispatch on the latent width; chain_d<D>.hip: the chain kernels of one width (templates in chain_kernels.h /
 # chain_edge.h, launchers in chain_launch.h), one translation unit each so that they compile in parallel
-HEADERS = ["common.h", "chain.h", "host_orch.h", "gmp_block.h", "chain_dev.h", "chain_kernels.h", "chain_edge.h", "chain_launch.h", "objective_row.h", "edge_gather.h", os.path.join("..", "..", "include", "bsms_hip.h"), os.path.join("..", "..", "include", "bsms_hip_ext.h")]
+HEADERS = ["common.h", "chain.h", "host_orch.h", "gmp_block.h", "chain_dev.h", "chain_kernels.h", "chain_edge.h", "chain_launch.h", "objective_row.h", "edge_gather.h", os.path.join("..", "..", "include", "bsms_hip.h"), os.path.join("..", "..", "include", "bsms_hip_ext.h"),
+           os.path.join("..", "..", "include", "bsms_hip_stats.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 if os.environ.get("BSMS_EXPERIMENTS") == "1":   # profiling / A-B builds only: BSMS_DEBUG_FLAGS, in-kernel time stamps, launch-shape knobs
     FLAGS.append("-DBSMS_EXPERIMENTS")
@@ -31,7 +35,7 @@ def _hipcc():
 
 def _digest():
     h = hashlib.sha256((" ".join(FLAGS) + os.environ.get("BSMS_CHAIN_FLAGS", "")).encode())
-    for f in SOURCES + EXT_SOURCES + HEADERS:
+    for f in SOURCES + COMPANION_SOURCES + HEADERS:
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()
@@ -41,15 +45,17 @@ def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     stamp = os.path.join(OBJ, "stamp")
     digest = _digest()
-    if not force and os.path.exists(LIB) and os.path.exists(EXT_LIB) and os.path.exists(stamp) and open(stamp).read() == digest:
+    built = os.path.exists(LIB) and all(os.path.exists(os.path.join(HERE, name)) for name, _ in COMPANIONS)
+    if not force and built and os.path.exists(stamp) and open(stamp).read() == digest:
         return LIB
     hipcc = _hipcc()
 
     def compile_one(src):
         obj = os.path.join(OBJ, os.path.basename(src).replace(".hip", ".o"))
         # no contraction: rowsum.hip rounds x*ew before the add like the reference; sim.hip keeps the fp64 normaliser roundings;
-        # batch.hip rounds g*noise before the add like the host's torch ops; errsum.hip and edgediff.hip keep separate fp64 multiplies and adds
-        extra = ["-ffp-contract=off"] if src in ("rowsum.hip", "sim.hip", "batch.hip", "errsum.hip", "edgediff.hip", *EXT_SOURCES) else []
+        # batch.hip rounds g*noise before the add like the host's torch ops; errsum.hip, edgediff.hip and the companions' sum kernels keep
+        # separate fp64 multiplies and adds
+        extra = ["-ffp-contract=off"] if src in ("rowsum.hip", "sim.hip", "batch.hip", "errsum.hip", "edgediff.hip", *COMPANION_SOURCES) else []
         if src.startswith("chain") and os.environ.get("BSMS_CHAIN_FLAGS"):   # A/B builds (chain.hip and the chain_d*.hip widths)
             extra += os.environ["BSMS_CHAIN_FLAGS"].split()
         cmd = [hipcc, *FLAGS, *extra, "-c", os.path.join(CSRC, src), "-o", obj]
@@ -60,17 +66,19 @@ def build(force=False, verbose=True):
             print(r.stderr, file=sys.stderr)
         return obj
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES) + len(EXT_SOURCES)) as ex:
-        objs = list(ex.map(compile_one, SOURCES + EXT_SOURCES))
-    objs, ext_objs = objs[:len(SOURCES)], objs[len(SOURCES):]
+    with ThreadPoolExecutor(max_workers=len(SOURCES) + len(COMPANION_SOURCES)) as ex:
+        objs = list(ex.map(compile_one, SOURCES + COMPANION_SOURCES))
+    objs, companion_objs = objs[:len(SOURCES)], objs[len(SOURCES):]
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
-    # the companion library: its own entries, everything else (plans, error text) from libbsms_hip.so next to it
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", EXT_LIB, *ext_objs, "-L" + HERE, "-lbsms_hip", "-Wl,-rpath,$ORIGIN"],
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link of the companion library failed:\n{r.stdout}\n{r.stderr}")
+    # the companion libraries: their own entries, everything else (plans, error text) from libbsms_hip.so next to them
+    for name, srcs in COMPANIONS:
+        own, companion_objs = companion_objs[:len(srcs)], companion_objs[len(srcs):]
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(HERE, name), *own, "-L" + HERE, "-lbsms_hip",
+                            "-Wl,-rpath,$ORIGIN"], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link of the companion library {name} failed:\n{r.stdout}\n{r.stderr}")
     with open(stamp, "w") as fh:
         fh.write(digest)
     if verbose:

@@ -164,6 +164,103 @@ def transform_rows(x, rows_per_sample, transforms, groups, inverse=False, out=No
     return out
 
 
+class Moments:
+    """First and second moments of what the normalisers see (the row layout of bsms_moment_sums, include/bsms_hip_stats.h):
+    `per_trajectory` fp64 [S, 4C+4] and `total` fp64 [4C+4] = [R | M | SX[C] | ST | QX[C] | QT | SD[C] | QD[C]] -- the rows, the rows
+    whose node type counts for the loss, and the sums and sums of squares of the state channels, of the node type and of the deltas
+    fl32(state[t+1] - state[t]) over every row.  The accessors below cut `total`; none of them copies or synchronises.  The tensors may
+    live on any device (the arithmetic of `normalizer_stats` is plain torch in fp64)."""
+
+    def __init__(self, per_trajectory, total, C, rows_known=None):
+        C = int(C)
+        if total.dtype != torch.float64 or tuple(total.shape) != (4 * C + 4,):
+            raise ValueError(f"Moments: total must be float64 [{4 * C + 4}], got {total.dtype} {tuple(total.shape)}")
+        if per_trajectory is not None and (per_trajectory.dtype != torch.float64 or per_trajectory.dim() != 2 or per_trajectory.shape[1] != 4 * C + 4):
+            raise ValueError(f"Moments: per_trajectory must be float64 [S, {4 * C + 4}]")
+        self.per_trajectory, self.total, self.C = per_trajectory, total, C
+        self._rows_known = rows_known        # the host's knowledge of `rows` (an int from the shapes), or None
+
+    rows = property(lambda self: self.total[0])
+    masked = property(lambda self: self.total[1])
+    sum_state = property(lambda self: self.total[2:2 + self.C])
+    sum_type = property(lambda self: self.total[2 + self.C])
+    sumsq_state = property(lambda self: self.total[3 + self.C:3 + 2 * self.C])
+    sumsq_type = property(lambda self: self.total[3 + 2 * self.C])
+    sum_delta = property(lambda self: self.total[4 + 2 * self.C:4 + 3 * self.C])
+    sumsq_delta = property(lambda self: self.total[4 + 3 * self.C:4 + 4 * self.C])
+
+    def all_reduce(self, group=None):
+        """Sum `total` over the ranks of `group`: ONE fp64 message of 4C+4 numbers, all-reduced in place as step.FusedStep reduces its
+        fp64 loss sums (gloo or RCCL).  `per_trajectory` stays this rank's.  A no-op at world size 1.  Returns self."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            dist.all_reduce(self.total, op=dist.ReduceOp.SUM, group=group)
+            if not self._rows_known:         # this rank holds no row: whether any rank does is on the device only
+                self._rows_known = None
+        return self
+
+    def _no_rows(self):
+        if self._rows_known is not None:
+            return self._rows_known == 0
+        return float(self.total[0]) == 0.0   # host tensors, or a reduced total of a rank without rows: the one read of R
+
+    def normalizer_stats(self, noise_std=None, noise_gamma=0.0):
+        """(in_mean [C+1], in_meansq [C+1], out_mean [C], out_meansq [C]), fp64 on the device of `total`: the statistics of the
+        network's inputs [state + n | type] and of its normalised targets delta - gamma n under the training noise of
+        bsms_batch_assemble -- n ~ N(0, sigma_c^2) on the M rows whose mask is 1, zero elsewhere -- in closed form:
+          in_meansq[c] = QX[c] / R + sigma_c^2 (M / R),   out_meansq[c] = QD[c] / R + gamma^2 sigma_c^2 (M / R),   the means SX / R, ST / R, SD / R
+        with sigma_c = double(fl32(noise_std[c])), every operand fp64.  `noise_std` None: the data's own moments, no noise term.
+        Nothing is read back when the row count is known from the shapes (a `TrajectoryBank.moments()` result).  ValueError without rows."""
+        if self._no_rows():
+            raise ValueError("Moments.normalizer_stats: no rows")
+        t, C = self.total, self.C
+        R = t[0]
+        in_mean = torch.cat([self.sum_state, self.sum_type.reshape(1)]) / R
+        in_meansq = torch.cat([self.sumsq_state, self.sumsq_type.reshape(1)]) / R
+        out_mean, out_meansq = self.sum_delta / R, self.sumsq_delta / R
+        if noise_std is not None:
+            sigma = np.asarray([float(v) for v in noise_std], dtype=np.float32).astype(np.float64)
+            if sigma.shape != (C,):
+                raise ValueError(f"Moments.normalizer_stats: noise_std has {sigma.size} entries for {C} channels")
+            var = torch.from_numpy(sigma * sigma).to(t.device)
+            share = self.masked / R
+            in_meansq = torch.cat([in_meansq[:C] + var * share, in_meansq[C:]])
+            gamma = float(noise_gamma)
+            out_meansq = out_meansq + (gamma * gamma) * var * share
+        return in_mean, in_meansq, out_mean, out_meansq
+
+
+def fit_normalizers(model, bank, noise="expected", indices=None, group=None, ignore_augment=False):
+    """Set both normalisers of `model` (a BSMS_Simulator on the bank's device) from the exact moments of `bank`:
+    `bank.moments(indices)`, summed over the ranks of `group`, through `Moments.normalizer_stats`.  noise="expected": with the bank's
+    training noise (cfg.noise_level, cfg.noise_gamma) in closed form -- what the reference's warm-up samples; "none": the data's own
+    moments.  The statistics are written IN PLACE (pointers held by sessions, the fused step and captured graphs stay valid):
+    _E_data / _E_data_squared by copy_, _acc_weight = rows / unit, _num_accumulations = _max_accumulations (a later accumulate=True
+    call changes nothing), synced = True.  Nothing is read back.  A bank with an `augment` is refused unless `ignore_augment`: the
+    statistics are those of the data's frame, and rotations change the per-channel moments of vector fields.  Returns the Moments."""
+    if noise not in ("expected", "none"):
+        raise ValueError(f'fit_normalizers: noise must be "expected" or "none", got {noise!r}')
+    if getattr(bank, "augment", None) is not None and not ignore_augment:
+        raise ValueError("fit_normalizers: the bank augments its training batches; the statistics would be those of the data's frame "
+                         "(pass ignore_augment=True to take them anyway)")
+    mom = bank.moments(indices).all_reduce(group)
+    if noise == "expected":
+        stats = mom.normalizer_stats([float(v) for v in bank.cfg.noise_level], float(bank.cfg.noise_gamma))
+    else:
+        stats = mom.normalizer_stats()
+    with torch.no_grad():
+        for norm, mean, meansq in ((model._inputNormalizer, stats[0], stats[1]), (model._targetNormalizer, stats[2], stats[3])):
+            if norm._E_data.device != mean.device or tuple(norm._E_data.shape) != tuple(mean.shape):
+                raise ValueError(f"fit_normalizers: {norm.name} holds {tuple(norm._E_data.shape)} on {norm._E_data.device}, the statistics are "
+                                 f"{tuple(mean.shape)} on {mean.device}")
+            norm._E_data.copy_(mean)
+            norm._E_data_squared.copy_(meansq)
+            norm._acc_weight.copy_((mom.rows / norm.unit).reshape(1))
+            norm._num_accumulations.copy_(norm._max_accumulations.reshape(1))
+            norm.synced = True
+    return mom
+
+
 class _Traj:
     __slots__ = ("state", "pos", "type", "pos_static", "type_static", "T", "N", "entry", "weights")
 
@@ -466,6 +563,23 @@ class TrajectoryBank:
     def sample(self, B, train=True, return_noise=False):
         """`batch` of the next `B` picks of the epoch order; the noise draw counts the batches."""
         return self.batch(self.next_picks(B), train=train, return_noise=return_noise)
+
+    # ------------------------------------------------------------------------------------------------ statistics
+    def moments(self, indices=None):
+        """The `Moments` of the chosen trajectories (None: all, in order) over EVERY pair of frames (t, t+1) they hold, whatever
+        `horizon` is: one bsms_moment_sums pass over the resident state and node type plus its fold, on the current stream.  Row k
+        of `per_trajectory` belongs to indices[k] and depends on that trajectory alone.  In the data's frame, without noise."""
+        from .ops import moment_fold, moment_sums
+        chosen = list(range(len(self._trajs))) if indices is None else [int(i) for i in indices]
+        table = []
+        for i in chosen:
+            tr = self._trajs[i]               # IndexError for a trajectory the bank does not hold
+            table.append((tr.state, tr.type, 0, tr.T - 1))
+        C_ = len(self._std)
+        with torch.cuda.device(self.device):
+            per = moment_sums(table, C_, list(self._valid), out=torch.empty(len(table), 4 * C_ + 4, device=self.device, dtype=torch.float64))
+            total = moment_fold(per)
+        return Moments(per, total, C_, rows_known=sum((self._trajs[i].T - 1) * self._trajs[i].N for i in chosen))
 
     # ------------------------------------------------------------------------------------------------ rollout
     def hierarchy(self, i):

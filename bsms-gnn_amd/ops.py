@@ -239,6 +239,69 @@ def edge_diff_bwd(pred, target, mask, plan, coef, *, pos=None, weighting="differ
     return grad
 
 
+# --------------------------------------------------------------------------------- dataset statistics
+def moment_sums(table, C, valid, *, out=None):
+    """Normaliser moments of resident trajectories (bsms_moment_sums of libbsms_hip_stats.so): fp64 [S, 4C+4] =
+    [R | M | SX | ST | QX | QT | SD | QD] per entry of `table`, a sequence of (state, type, frame0, frames) -- `state` a contiguous
+    float32 device [T, n, C], `type` contiguous float32 [n(, 1)] (one column for all frames) or [T, n(, 1)], and the pairs (t, t+1) for
+    t = frame0 .. frame0 + frames - 1, which must exist.  `valid`: the node-type codes that count for M.  `out`: a contiguous fp64
+    [S, 4C+4] to write into (None allocates).  One launch pair per 64 entries on the current stream; nothing is copied and nothing
+    synchronises.  All tensors live on one device."""
+    import ctypes as ct
+    C, S = int(C), len(table)
+    rows, dev = (_abi.MomentTraj * max(S, 1))(), None
+    max_rows = 0
+    for k, (state, typ, frame0, frames) in enumerate(table):
+        for what, t in (("state", state), ("type", typ)):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise _abi.BsmsError(f"moment_sums: entry {k}: {what} must be a contiguous float32 GPU tensor; there is no CPU fallback")
+            if dev is not None and t.device != dev:
+                raise _abi.BsmsError(f"moment_sums: entry {k}: {what} lives on {t.device}, the table on {dev}")
+            dev = t.device
+        if state.dim() != 3 or state.shape[2] != C:
+            raise ValueError(f"moment_sums: entry {k}: state of shape {tuple(state.shape)} is not [T, n, {C}]")
+        T, n, frame0, frames = int(state.shape[0]), int(state.shape[1]), int(frame0), int(frames)
+        if frame0 < 0 or frames < 0 or (frames > 0 and frame0 + frames + 1 > T):
+            raise ValueError(f"moment_sums: entry {k}: the pairs of frames [{frame0}, {frame0 + frames}] do not lie in {T} frames")
+        if typ.numel() == n:
+            stride = 0
+        elif typ.numel() == T * n:
+            stride = n
+        else:
+            raise ValueError(f"moment_sums: entry {k}: type of shape {tuple(typ.shape)} is neither [{n}] nor [{T}, {n}]")
+        r = rows[k]
+        r.state, r.type, r.n, r.frame0, r.frames, r.type_stride = state.data_ptr(), typ.data_ptr(), n, frame0, frames, stride
+        max_rows = max(max_rows, frames * n)
+    if dev is None:
+        dev = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+    W = 4 * C + 4
+    if out is None:
+        out = torch.empty(S, W, device=dev, dtype=torch.float64)
+    elif out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (S, W) or not out.is_contiguous():
+        raise ValueError(f"moment_sums: out must be a contiguous float64 [{S}, {W}] on {dev}")
+    codes = (ct.c_float * max(len(valid), 1))(*[float(v) for v in valid])
+    L = _abi.stats()
+    with torch.cuda.device(dev):
+        work = _workspace(dev, L.bsms_moment_work_bytes(max_rows))
+        _abi.check(L.bsms_moment_sums(ct.addressof(rows), S, C, ct.addressof(codes), len(valid), out.data_ptr(), work.data_ptr(), _stream()),
+                   "bsms_moment_sums")
+    return out
+
+
+def moment_fold(sums, *, out=None):
+    """The rows of a float64 device [S, W] added in ascending order (bsms_moment_fold): fp64 [W].  One launch, no atomics."""
+    if not torch.is_tensor(sums) or not sums.is_cuda or sums.dtype != torch.float64 or sums.dim() != 2 or not sums.is_contiguous():
+        raise _abi.BsmsError("moment_fold: sums must be a contiguous float64 GPU tensor [S, W]; there is no CPU fallback")
+    S, W = int(sums.shape[0]), int(sums.shape[1])
+    if out is None:
+        out = torch.empty(W, device=sums.device, dtype=torch.float64)
+    elif out.dtype != torch.float64 or out.device != sums.device or tuple(out.shape) != (W,) or not out.is_contiguous():
+        raise ValueError(f"moment_fold: out must be a contiguous float64 [{W}] on {sums.device}")
+    with torch.cuda.device(sums.device):
+        _abi.check(_abi.stats().bsms_moment_fold(sums.data_ptr() if S else None, S, W, out.data_ptr(), _stream()), "bsms_moment_fold")
+    return out
+
+
 # --------------------------------------------------------------------------------- tensor prims
 class _SegmentSum(torch.autograd.Function):
     @staticmethod

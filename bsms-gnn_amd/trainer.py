@@ -374,6 +374,7 @@ class Trainer:
         _check_host_threads()
         self._synced = False
         self._norm_base = None     # statistics every rank already shares (restore followed by warm-up)
+        self._fitted = False       # fit_normalizers has set the statistics: no warm-up iterations, no merge
 
     def move_to_device(self, data):
         """trainer/trainer.py:143 semantics (nested lists -> device), except that INDEX tensors (edge lists, kept ids)
@@ -417,7 +418,20 @@ class Trainer:
         return data
 
     def _warming_up(self):
-        return self.train_step < self.model_cfg.accumulation_steps
+        return not self._fitted and self.train_step < self.model_cfg.accumulation_steps
+
+    def fit_normalizers(self, bank, noise="expected", indices=None, ignore_augment=False):
+        """Set the normalisers from the exact moments of `bank` (databank.fit_normalizers) instead of sampling them
+        over model_cfg.accumulation_steps warm-up iterations: every resident pair of frames of the chosen trajectories, the training
+        noise in closed form (noise="expected") or left out ("none"), summed over the ranks of the trainer's process group, so every
+        rank holds identical statistics and no merge follows.  The trainer is then fitted: `iter` trains from its next call on,
+        whatever `train_step` is.  The statistics travel in the model's state_dict as ever, so `save` / `restore` carry them; a
+        trainer that restores such a checkpoint with train_step < accumulation_steps calls this again, or is configured with
+        accumulation_steps = 0, to skip the warm-up.  Returns the Moments."""
+        from .databank import fit_normalizers
+        mom = fit_normalizers(self.model, bank, noise=noise, indices=indices, group=self.dp.group, ignore_augment=ignore_augment)
+        self._fitted, self._synced, self._norm_base = True, True, None
+        return mom
 
     def ema_model(self):
         """The model with the averaged weights (opt_cfg.ema_decay > 0): FusedAdamW.ema_model of the live one, built once.  Its
