@@ -12,6 +12,7 @@ from .databank import Augment, Moments, TrajectoryBank, epoch_picks, fit_normali
 from .dp import DataParallel, GradBuckets, global_masked_rmse  # noqa: F401
 from .hierarchy import BistrideMultiLayerGraph, lumped_node_measure, to_flat_edge  # noqa: F401
 from .rollout import RolloutErrors, rank_slice, rollout_bank, rollout_batch, rollout_dataset, rollout_errors, rollout_one_traj, rollout_rmse  # noqa: F401
+from .sample import MeshSampler, rollout_frames, write_png  # noqa: F401
 from .step import FusedStep, input_gradient  # noqa: F401
 from .trainer import DevicePrefetcher, FusedAdamW, Trainer, WarmupCosineDecay, param_groups, segment_table  # noqa: F401
 

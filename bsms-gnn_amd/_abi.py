@@ -169,6 +169,18 @@ STATS_SIGNATURES = {
 }
 
 
+# the third companion library libbsms_hip_sample.so: name -> (restype, argtypes); one entry per declaration in include/bsms_hip_sample.h
+SAMPLE_LIB_PATH = os.path.join(_HERE, "libbsms_hip_sample.so")
+SAMPLE_SIGNATURES = {
+    "bsms_raster_work_bytes": (c_size_t, []),
+    "bsms_raster_owner": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, C.c_double, C.c_double, C.c_double, C.c_double, c_i64,
+                                  c_void_p, c_void_p, c_void_p]),
+    "bsms_point_owner": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p]),
+    "bsms_field_gather": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_i64, C.c_double, C.c_double,
+                                  C.c_double, C.c_double, c_void_p, c_i64, c_i64, c_i64, c_i64, C.c_float, c_void_p, c_void_p]),
+}
+
+
 class MomentTraj(C.Structure):
     """bsms_moment_traj (include/bsms_hip_stats.h)."""
     _fields_ = [("state", c_void_p), ("type", c_void_p), ("n", c_i64), ("frame0", c_i64), ("frames", c_i64), ("type_stride", c_i64)]
@@ -247,6 +259,26 @@ def stats():
             fn.restype, fn.argtypes = res, args
         _stats = handle
     return _stats
+
+
+_sample = None
+
+
+def sample():
+    """Load the sampling library (once), behind libbsms_hip.so, which it links against.  Raises if it has not been built.  Only the
+    mesh sampler (sample.MeshSampler) calls this: a process that never samples a field never loads the library."""
+    global _sample
+    if _sample is None:
+        lib()
+        if not os.path.exists(SAMPLE_LIB_PATH):
+            raise BsmsError(f"{SAMPLE_LIB_PATH} not found: build it with `python bsms-gnn_amd/build.py` (or __graft_entry__.build()); "
+                            "there is no CPU/PyTorch fallback")
+        handle = C.CDLL(SAMPLE_LIB_PATH)
+        for name, (res, args) in SAMPLE_SIGNATURES.items():
+            fn = getattr(handle, name)  # AttributeError if the symbol is missing
+            fn.restype, fn.argtypes = res, args
+        _sample = handle
+    return _sample
 
 
 def check(rc, what):

@@ -262,7 +262,7 @@ def fit_normalizers(model, bank, noise="expected", indices=None, group=None, ign
 
 
 class _Traj:
-    __slots__ = ("state", "pos", "type", "pos_static", "type_static", "T", "N", "entry", "weights")
+    __slots__ = ("state", "pos", "type", "pos_static", "type_static", "T", "N", "entry", "weights", "cells")
 
 
 class TrajectoryBank:
@@ -419,6 +419,11 @@ class TrajectoryBank:
         tr.pos = self._put(pos[0] if tr.pos_static else pos)
         tr.type = self._put(typ[0] if tr.type_static else typ)
         tr.weights = None if measure is None else self._put(measure)
+        cells = fields.get("cells")                   # host: what `sampler` triangulates (nothing is uploaded for it).  An OWNED int32 copy
+        if cells is not None:                         # of frame 0 -- a view would keep the [T, n_cells, k] array of `fields` alive
+            cells = np.asarray(cells)
+            cells = np.array(cells[0] if cells.ndim == 3 else cells, dtype=np.int32, copy=True)
+        tr.cells = cells
         self._trajs.append(tr)
         return len(self._trajs) - 1
 
@@ -506,6 +511,15 @@ class TrajectoryBank:
             raise ValueError("TrajectoryBank.node_weights: no picks")
         w = [self._trajs[int(si)].weights for si, _ in picks]
         return torch.stack(w) if self.cfg.consist_mesh else torch.cat(w)
+
+    def sampler(self, i):
+        """A `sample.MeshSampler` on the mesh of trajectory `i`: its stored `cells` and its frame-0 positions.  Built
+        on every call (the sampler caches its owner images: keep it)."""
+        tr = self._trajs[int(i)]
+        if tr.cells is None:
+            raise ValueError('TrajectoryBank.sampler: needs the trajectory\'s "cells" (cfg.field_names)')
+        from .sample import MeshSampler
+        return MeshSampler(tr.pos if tr.pos_static else tr.pos[0], tr.cells, self.cfg.mesh_type, device=self.device)
 
     def batch(self, picks, train=True, draw=None, return_noise=False, horizon=None, transforms=None, return_transforms=False,
               return_weights=False):

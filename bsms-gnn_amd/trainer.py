@@ -452,6 +452,26 @@ class Trainer:
         """`ema=True` (here, in get_loss and in get_error): the averaged weights (`ema_model()`) instead of the live ones."""
         return self._model_forward(self.move_to_device(data), ema)
 
+    def eval_panels(self, data, sampler, width, height, sample=0, ema=False, bounds=None, fill=float("nan")):
+        """The panels of the reference's eval_plot (src/utils/train_utils.py:60-101) on the device: float32 [C, 4, H, W] -- per
+        channel the input state, the label, the prediction and prediction - label of batch entry `sample`, each rasterised on
+        `sampler`'s mesh (sample.MeshSampler) in ONE gather launch.  A variable-mesh batch is one sample of sum N
+        rows, so `sampler` then spans the union and `sample` is 0.  `ema` as in `get_pred`."""
+        data = self.move_to_device(data)
+        with torch.no_grad():
+            pred = self.get_pred(data, ema)
+            tar, _ = self.get_label_mask(data)
+            node_in = data[0] if self.model_cfg.consistent_mesh else data[0].x
+            C = pred.shape[-1]
+            if self.model_cfg.consistent_mesh:
+                pred, tar, node_in = pred[sample], tar[sample], node_in[sample]
+            elif sample != 0:
+                raise IndexError(f"eval_panels: a variable-mesh batch is one sample, got sample={sample}")
+            else:
+                pred = pred.reshape(-1, C)
+            sets = torch.stack([node_in[..., :C], tar, pred, pred - tar])         # [4, N, C]: the one (small) copy on the way
+            return sampler.rasterize(sets, width, height, bounds, fill).permute(1, 0, 2, 3)
+
     def get_loss(self, data, ema=False, node_weights=None):
         """The training objective on `data` (autograd).  `node_weights`: as `iter` takes them, with model_cfg.loss_node_weights."""
         node_weights = self.objective.check_node_weights(node_weights)
