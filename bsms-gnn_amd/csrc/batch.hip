@@ -15,7 +15,6 @@ using namespace bsms;
 
 namespace {
 
-constexpr int kMaxC = 8;             // state channels (sim.hip keeps the same bound)
 constexpr int kMaxValid = 4;         // node-type codes that count for the loss
 constexpr int kBatchSamples = 64;    // samples per launch: the table is a kernel argument (64 * 48 B + header < 4 KB)
 constexpr int kRowsPerBlock = 256;

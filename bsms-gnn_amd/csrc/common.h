@@ -66,6 +66,7 @@ int side_mark_chain(SideLane* a, SideLane* b, int slot);   // b's mark covers a'
 // join leaves the flag set; the next bsms_side_lanes_join then waits for that (recorded) event once more, which is harmless.
 int side_wait_open_mark(SideLane* lane, int slot, hipStream_t main);
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+constexpr int kMaxC = 8;   // state / field channels of a row, in every library: what the kernels hold in registers per row
 
 // Per-DEVICE launch state: hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the device that is current
 // when it is called, and the CU count is a property of that device -- a process driving several devices (not the one-process-per-GPU

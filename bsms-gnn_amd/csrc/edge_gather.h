@@ -10,7 +10,6 @@
 namespace bsms {
 namespace edge {
 
-constexpr int kMaxC = 8;                                // state channels (errsum.hip keeps the same bound)
 constexpr int kMaxP = 3;                                // position columns
 constexpr int kBwdThreads = 256;                        // rows per block of the backward
 
@@ -125,18 +124,6 @@ __device__ __forceinline__ void edge_gather(const EdgeArgs& a, const float* __re
     }
   }
 }
-
-#define BSMS_EDGE_BY_C(C_, CALL)  \
-  switch (C_) {                   \
-    case 1: CALL(1); break;       \
-    case 2: CALL(2); break;       \
-    case 3: CALL(3); break;       \
-    case 4: CALL(4); break;       \
-    case 5: CALL(5); break;       \
-    case 6: CALL(6); break;       \
-    case 7: CALL(7); break;       \
-    default: CALL(8); break;      \
-  }
 
 }  // namespace edge
 }  // namespace bsms

@@ -6,9 +6,8 @@
 //   ME = sum mu_e    DE[c] = sum mu_e omega_e (d_ic - d_jc)^2    TE[c] = sum mu_e omega_e (t_ic - t_jc)^2,   d = fl32(pred - target)
 // d takes the ONE fp32 rounding of bsms_error_sums; every product and sum after it is fp64.
 // Deterministic, no atomics.  Sums: row r owns its INCOMING edges (the plan's dst-sorted CSR, stable in the caller's edge order) and
-// adds them one after the other; the rows are reduced like those of errsum.hip -- pieces of kPieceRows rows counted from the
-// segment's own first row, one row per thread, a fixed shuffle tree per wave, the sixteen waves in order, and k_edge_finish adds
-// the pieces in index order.  A segment's row therefore depends on its own rows and edges only: not on S, the
+// adds them one after the other; the rows are reduced by the piece sum of piece_sum.h -- pieces of kPieceRows rows,
+// one row per thread, sixteen waves.  A segment's row therefore depends on its own rows and edges only: not on S, the
 // strides, its neighbours in the launch, or on whether the plan is the mesh's own or a block-diagonal union around it.
 // Backward: thread r owns grad[s, r, :]; per element ONE fp64 accumulator, incoming edges in CSR order, then outgoing edges in
 // transpose order, times 2 * coef[s, c] in fp64, ONE rounding to fp32.
@@ -17,8 +16,8 @@
 // independent.
 // The gather loop of the backward is `edge_gather` (edge_gather.h): ext/edge_objective.hip runs the same copy.
 // Compiled with -ffp-contract=off (build.py): the sums keep the roundings of separate fp64 multiplies and adds.
-#include "common.h"
 #include "edge_gather.h"
+#include "piece_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -34,9 +33,8 @@ constexpr int64_t kMaxBlocksPerLaunch = int64_t(1) << 21;   // 2^31 threads: bel
 template <int C, bool kQuot>
 __global__ __launch_bounds__(kPieceRows) void k_edge_pieces(const EdgeArgs a, double* __restrict__ partials) {
   constexpr int ncol = 1 + 2 * C, U = Batch<C>::kSums;
-  __shared__ double red[kPieceRows / 64][ncol];
-  const int64_t blk = a.blk0 + int64_t(blockIdx.x);
-  const int64_t s = blk / a.pieces, piece = blk - s * a.pieces;
+  const psum::Split at = psum::split(a.blk0, a.pieces);
+  const int64_t s = at.seg, piece = at.piece;
   const float* pred = a.pred + s * a.pred_stride * C;
   const float* target = a.target + s * a.target_stride * C;
   const float* mask = a.mask + s * a.mask_stride;
@@ -79,46 +77,15 @@ __global__ __launch_bounds__(kPieceRows) void k_edge_pieces(const EdgeArgs a, do
       }
     }
   }
-  // fixed trees: lanes of a wave by shuffle, then the sixteen waves in order
-  const int lane = int(threadIdx.x) & 63, wave = int(threadIdx.x) >> 6;
-#pragma unroll
-  for (int k = 0; k < ncol; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (int(threadIdx.x) < ncol) {
-    const int k = int(threadIdx.x);
-    double v = red[0][k];
-#pragma unroll
-    for (int w = 1; w < kPieceRows / 64; ++w) v += red[w][k];
-    partials[blk * ncol + k] = v;
-  }
-}
-
-// sums[s, col] = the pieces of segment s added in index order (zero pieces: zeros); one thread per output element
-__global__ __launch_bounds__(256) void k_edge_finish(const double* __restrict__ partials, int64_t S, int64_t pieces, int ncol,
-                                                    double* __restrict__ sums) {
-  const int64_t i = int64_t(blockIdx.x) * 256 + int(threadIdx.x);
-  if (i >= S * ncol) return;
-  const int64_t s = i / ncol;
-  const int col = int(i - s * ncol);
-  const double* p = partials + s * pieces * ncol + col;
-  double v = 0.0;
-#pragma unroll 8
-  for (int64_t k = 0; k < pieces; ++k) v += p[k * ncol];
-  sums[i] = v;
+  psum::block_sum<kPieceRows>(acc, psum::Dense<ncol>(), partials + at.blk * ncol);
 }
 
 // grad[s, r, c] = fl32(2 coef[s, c] * (sum over incoming, then outgoing edges of mu omega (d_rc - d_other,c))); one thread per row
 template <int C, bool kQuot>
 __global__ __launch_bounds__(kBwdThreads) void k_edge_bwd(const EdgeArgs a, const double* __restrict__ coef, int accumulate,
                                                          float* __restrict__ grad, int64_t grad_stride) {
-  const int64_t blk = a.blk0 + int64_t(blockIdx.x);
-  const int64_t s = blk / a.pieces;
-  const int64_t r = (blk - s * a.pieces) * kBwdThreads + int(threadIdx.x);
+  const psum::Split at = psum::split(a.blk0, a.pieces);
+  const int64_t s = at.seg, r = at.piece * kBwdThreads + int(threadIdx.x);
   if (r >= a.seg_rows) return;
   const float* pred = a.pred + s * a.pred_stride * C;
   const float* target = a.target + s * a.target_stride * C;
@@ -204,16 +171,12 @@ extern "C" int bsms_edge_diff_sums(const bsms_plan_t* plan, int64_t row0, int64_
   hipStream_t s = as_stream(stream);
   double* partials = reinterpret_cast<double*>(work);
   const int64_t blocks = S * a.pieces;
-  for (int64_t first = 0; first < blocks; first += kMaxBlocksPerLaunch) {
+  const int rc = psum::for_block_slices(blocks, kMaxBlocksPerLaunch, [&](int64_t first, unsigned nb) {
     a.blk0 = first;
-    const unsigned nb = unsigned(std::min(kMaxBlocksPerLaunch, blocks - first));
-#define BSMS_EDGE_CALL(C_) launch_pieces<C_>(weighting == BSMS_EDGE_QUOTIENT, nb, s, a, partials)
-    BSMS_EDGE_BY_C(int(C), BSMS_EDGE_CALL)
-#undef BSMS_EDGE_CALL
-    BSMS_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_edge_finish, dim3(unsigned(ceil_div(S * ncol, 256))), dim3(256), 0, s, (const double*)partials, S, a.pieces,
-                     ncol, sums);
+    psum::by_channels(int(C), [&](auto c) { launch_pieces<decltype(c)::value>(weighting == BSMS_EDGE_QUOTIENT, nb, s, a, partials); });
+  });
+  if (rc) return rc;
+  psum::launch_finish(partials, S, a.pieces, ncol, ncol, sums, s);
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
@@ -234,13 +197,10 @@ extern "C" int bsms_edge_diff_bwd(const bsms_plan_t* plan, int64_t row0, int64_t
   hipStream_t s = as_stream(stream);
   a.pieces = ceil_div(seg_rows, kBwdThreads);            // blocks per segment: one thread per row
   const int64_t blocks = S * a.pieces;
-  for (int64_t first = 0; first < blocks; first += kMaxBlocksPerLaunch) {
+  return psum::for_block_slices(blocks, kMaxBlocksPerLaunch, [&](int64_t first, unsigned nb) {
     a.blk0 = first;
-    const unsigned nb = unsigned(std::min(kMaxBlocksPerLaunch, blocks - first));
-#define BSMS_EDGE_CALL(C_) launch_bwd<C_>(weighting == BSMS_EDGE_QUOTIENT, nb, s, a, coef, accumulate, grad, grad_stride)
-    BSMS_EDGE_BY_C(int(C), BSMS_EDGE_CALL)
-#undef BSMS_EDGE_CALL
-    BSMS_LAUNCH_CHECK();
-  }
-  return BSMS_OK;
+    psum::by_channels(int(C), [&](auto c) {
+      launch_bwd<decltype(c)::value>(weighting == BSMS_EDGE_QUOTIENT, nb, s, a, coef, accumulate, grad, grad_stride);
+    });
+  });
 }

@@ -3,15 +3,14 @@
 // mask there.  Per segment s (a sample of a batch, or a time step of a rolled-out trajectory) over its seg_rows rows:
 //   M = sum m    SE[c] = sum m * d_c^2    AE[c] = sum m * |d_c|    TT[c] = sum m * target_c^2,   d = fl32(pred - target)
 // d takes the ONE fp32 rounding of the reference's subtraction; every product and sum after it is fp64.
-// Deterministic, no atomics: a segment is cut into pieces of kPieceRows rows counted from ITS first row; k_error_pieces reduces a
-// piece (per thread: its rows in ascending order; per wave: a fixed shuffle tree; per block: the four waves in order) and
-// k_error_finish adds the pieces of a segment in index order.  A segment's sums therefore depend on its own rows only -- not on
-// S, on the strides, or on what else is in the launch.
+// Deterministic, no atomics: the piece sum of piece_sum.h over pieces of kPieceRows rows, a thread adding its rows
+// in ascending order.  A segment's sums therefore depend on its own rows only -- not on S, on the strides, or on what else is in
+// the launch.  What is this file's: what a row adds (SumErrors / SumRobust), the argument checks and the entries.
 // bsms_error_sums_w (node-weighted training objectives) is the same code with mu = double(m) * double(weight) in m's place.
 // bsms_robust_sums (robust training objectives) is the same code again with another POLICY for what a row adds: one
 // column S[c] = sum mu * rho(d_c / s_c) per channel in place of the three of the evaluation (SumErrors / SumRobust below).
 // Compiled with -ffp-contract=off (build.py): the sums keep the roundings of separate fp64 multiplies and adds.
-#include "common.h"
+#include "piece_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -19,7 +18,6 @@ using namespace bsms;
 
 namespace {
 
-constexpr int kMaxC = 8;                                // state channels (sim.hip and batch.hip keep the same bound)
 constexpr int kMaxCols = 1 + 3 * kMaxC;                 // M | SE | AE | TT
 constexpr int kThreads = 256;                           // four waves of 64
 constexpr int kRowsPerThread = 4;
@@ -67,17 +65,25 @@ struct SumRobust {                                      // M | S, S[c] = sum mu 
   }
 };
 
+// The accumulators of a thread are M and kGroups blocks of kMaxC channels; the output columns are M and kGroups blocks of C.
+template <int kGroups>
+struct ChannelCols {
+  int C;
+  __device__ __forceinline__ bool live(int k) const { return k == 0 || (k - 1) % kMaxC < C; }
+  __device__ __forceinline__ int ncol() const { return 1 + kGroups * C; }
+  __device__ __forceinline__ int slot(int col) const { return col == 0 ? 0 : 1 + ((col - 1) / C) * kMaxC + (col - 1) % C; }
+};
+
 // One piece of one segment.  kWeighted (bsms_error_sums_w): the row's mask is multiplied by its weight in fp64 before anything
 // else sees it -- with a unit weight the product IS the mask, so every later operation is the unweighted kernel's.
 template <bool kWeighted, class Policy>
 __device__ __forceinline__ void error_piece(const ErrArgs& a, const float* __restrict__ row_weights, int64_t weight_stride,
                                             double* __restrict__ partials, Policy pol) {
   constexpr int kCols = 1 + Policy::kGroups * kMaxC;    // accumulators of a thread: M, then kGroups blocks of kMaxC channels
-  __shared__ double red[kThreads / 64][kCols];
-  const int C = a.C, ncol = 1 + Policy::kGroups * C;
+  const int C = a.C;
   pol.prepare(C);
-  const int64_t blk = a.blk0 + int64_t(blockIdx.x);
-  const int64_t s = blk / a.pieces, piece = blk - s * a.pieces;
+  const psum::Split at = psum::split(a.blk0, a.pieces);
+  const int64_t s = at.seg, piece = at.piece;
   const float* pred = a.pred + s * a.pred_stride * C;
   const float* target = a.target + s * a.target_stride * C;
   const float* mask = a.mask + s * a.mask_stride;
@@ -103,27 +109,8 @@ __device__ __forceinline__ void error_piece(const ErrArgs& a, const float* __res
       }
     }
   }
-  // fixed trees: lanes of a wave by shuffle, then the four waves in order
-  const int lane = int(threadIdx.x) & 63, wave = int(threadIdx.x) >> 6;
-#pragma unroll
-  for (int k = 0; k < kCols; ++k) {
-    const int c = (k - 1) % kMaxC;                      // channel of column k (k >= 1)
-    if (k == 0 || c < C) {
-      double v = acc[k];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-      if (lane == 0) red[wave][k] = v;
-    }
-  }
-  __syncthreads();
-  if (int(threadIdx.x) < ncol) {
-    const int col = int(threadIdx.x);                   // output column: 0 | 1 + c | 1 + C + c | 1 + 2C + c (the groups of the policy)
-    const int k = col == 0 ? 0 : 1 + ((col - 1) / C) * kMaxC + (col - 1) % C;
-    double v = red[0][k];
-#pragma unroll
-    for (int w = 1; w < kThreads / 64; ++w) v += red[w][k];
-    partials[blk * ncol + col] = v;
-  }
+  const ChannelCols<Policy::kGroups> cols{C};
+  psum::block_sum<kThreads>(acc, cols, partials + at.blk * cols.ncol());
 }
 
 __global__ __launch_bounds__(kThreads) void k_error_pieces(const ErrArgs a, double* __restrict__ partials) {
@@ -142,21 +129,6 @@ __global__ __launch_bounds__(kThreads) void k_robust_pieces(const ErrArgs a, con
 __global__ __launch_bounds__(kThreads) void k_robust_pieces_w(const ErrArgs a, const SumRobust pol, const float* __restrict__ row_weights,
                                                               int64_t weight_stride, double* __restrict__ partials) {
   error_piece<true>(a, row_weights, weight_stride, partials, pol);
-}
-
-// sums[s, col] = the pieces of segment s added in index order (zero pieces: zeros); one thread per output element.  Rows of `sums`
-// are sums_stride doubles apart (>= ncol; what lies between the rows is not written).
-__global__ __launch_bounds__(kThreads) void k_error_finish(const double* __restrict__ partials, int64_t S, int64_t pieces, int ncol,
-                                                          int64_t sums_stride, double* __restrict__ sums) {
-  const int64_t i = int64_t(blockIdx.x) * kThreads + int(threadIdx.x);
-  if (i >= S * ncol) return;
-  const int64_t s = i / ncol;
-  const int col = int(i - s * ncol);
-  const double* p = partials + s * pieces * ncol + col;
-  double v = 0.0;
-#pragma unroll 8
-  for (int64_t k = 0; k < pieces; ++k) v += p[k * ncol];
-  sums[s * sums_stride + col] = v;
 }
 
 inline int64_t pieces_of(int64_t seg_rows) { return ceil_div(seg_rows, kPieceRows); }
@@ -201,17 +173,15 @@ int error_sums_impl(const char* who, bool weighted, const float* pred, const flo
   a.pred_stride = pred_stride; a.target_stride = target_stride; a.mask_stride = mask_stride;
   a.C = int(C);
   const int64_t blocks = S * pieces;     // < 2^20 * 2^21 at the documented limits: no overflow
-  for (int64_t first = 0; first < blocks; first += kMaxBlocksPerLaunch) {
+  const int rc = psum::for_block_slices(blocks, kMaxBlocksPerLaunch, [&](int64_t first, unsigned nb) {
     a.blk0 = first;
-    const unsigned nb = unsigned(std::min(kMaxBlocksPerLaunch, blocks - first));
     if (robust && weighted) hipLaunchKernelGGL(k_robust_pieces_w, dim3(nb), dim3(kThreads), 0, s, a, *robust, row_weights, weight_stride, partials);
     else if (robust) hipLaunchKernelGGL(k_robust_pieces, dim3(nb), dim3(kThreads), 0, s, a, *robust, partials);
     else if (weighted) hipLaunchKernelGGL(k_error_pieces_w, dim3(nb), dim3(kThreads), 0, s, a, row_weights, weight_stride, partials);
     else hipLaunchKernelGGL(k_error_pieces, dim3(nb), dim3(kThreads), 0, s, a, partials);
-    BSMS_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_error_finish, dim3(unsigned(ceil_div(S * ncol, kThreads))), dim3(kThreads), 0, s, (const double*)partials, S, pieces,
-                     ncol, sums_stride, sums);
+  });
+  if (rc) return rc;
+  psum::launch_finish(partials, S, pieces, ncol, sums_stride, sums, s);
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
@@ -233,7 +203,7 @@ extern "C" int bsms_error_sums_w(const float* pred, const float* target, const f
                          weight_stride, sums, work, stream);
 }
 
-// The per-channel sums of the robust training objectives (include/bsms_hip.h): the pieces, trees and finish of
+// The per-channel sums of the robust training objectives (include/bsms_hip.h): the pieces, block sum and finish of
 // bsms_error_sums with S[c] = sum mu * rho(double(d_c) / s_c) as the one column per channel.
 extern "C" int bsms_robust_sums(const float* pred, const float* target, const float* mask, const float* row_weights, int64_t S,
                                 int64_t seg_rows, int64_t C, int64_t pred_stride, int64_t target_stride, int64_t mask_stride,

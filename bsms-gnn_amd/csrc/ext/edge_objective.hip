@@ -1,14 +1,14 @@
 // The objective with an edge-difference term (include/bsms_hip_ext.h: bsms_edge_diff_fold, bsms_sim_edge_objective_bwd),
 // built into the companion library libbsms_hip_ext.so: the surface of libbsms_hip.so is closed (its entries are pinned one by one),
 // so entries that come later live here, on the same plans, error reporting and device code.
-// The fold adds the segments' rows in index order, one thread per column.  The backward is the row of k_sim_objective_bwd
+// The fold is the row fold of piece_sum.h over the columns [ME | DE] of the segments' rows.  The backward is the row of k_sim_objective_bwd
 // (sim.hip; objective_row.h: the one head and the one tail) with the adjoint's gather (edge_gather.h: the one copy k_edge_bwd runs too) added to the loss
 // gradient in front of the step weight.  Compiled with -ffp-contract=off (build.py).
 #include <cmath>
 
-#include "../common.h"
 #include "../edge_gather.h"
 #include "../objective_row.h"
+#include "../piece_sum.h"
 #include "../../../include/bsms_hip_ext.h"
 
 #pragma clang fp contract(off)
@@ -85,16 +85,6 @@ __global__ __launch_bounds__(kBwdThreads) void k_edge_objective_bwd(const EdgeAr
   }
 }
 
-// out[0] = sum_s ME_s, out[1 + c] = sum_s DE_s[c]: the segments in ascending order, one thread per column
-__global__ __launch_bounds__(64) void k_edge_fold(const double* __restrict__ sums, int64_t S, int C, double* __restrict__ out) {
-  const int col = int(threadIdx.x);
-  if (col > C) return;
-  const int64_t ncol = 1 + 2 * C;
-  double v = 0.0;
-  for (int64_t s = 0; s < S; ++s) v += sums[s * ncol + col];
-  out[col] = v;
-}
-
 template <int C>
 void launch_objective_bwd(bool quot, unsigned nb, hipStream_t s, const EdgeArgs& a, const EdgeObjArgs& o) {
   if (quot) hipLaunchKernelGGL((k_edge_objective_bwd<C, true>), dim3(nb), dim3(kBwdThreads), 0, s, a, o);
@@ -107,7 +97,7 @@ extern "C" int bsms_edge_diff_fold(const double* sums, int64_t S, int64_t C, dou
   BSMS_REQUIRE(C >= 1 && C <= kMaxC, BSMS_E_UNSUPPORTED, "edge_diff_fold: C=%lld (C in 1..8)", (long long)C);
   BSMS_REQUIRE(S >= 0, BSMS_E_INVALID_ARG, "edge_diff_fold: S=%lld", (long long)S);
   BSMS_REQUIRE(out && (sums || S == 0), BSMS_E_INVALID_ARG, "edge_diff_fold: null argument");
-  hipLaunchKernelGGL(k_edge_fold, dim3(1), dim3(64), 0, as_stream(stream), sums, S, int(C), out);
+  psum::launch_fold(sums, S, 1 + C, 1 + 2 * C, out, as_stream(stream));     // out[0] = sum_s ME_s, out[1 + c] = sum_s DE_s[c]
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
@@ -150,9 +140,7 @@ extern "C" int bsms_sim_edge_objective_bwd(const bsms_plan_t* plan, int64_t seg_
   o.normalized = int(space == BSMS_LOSS_NORMALIZED); o.rmse = int(kind == BSMS_LOSS_RMSE);
   const unsigned nb = unsigned(ceil_div(o.R, kBwdThreads));
   hipStream_t s = as_stream(stream);
-#define BSMS_EDGE_CALL(C_) launch_objective_bwd<C_>(quot, nb, s, a, o)
-  BSMS_EDGE_BY_C(int(C), BSMS_EDGE_CALL)
-#undef BSMS_EDGE_CALL
+  psum::by_channels(int(C), [&](auto c) { launch_objective_bwd<decltype(c)::value>(quot, nb, s, a, o); });
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }

@@ -17,7 +17,6 @@ using namespace bsms;
 
 namespace {
 
-constexpr int kMaxC = 8;                                // channels of a field set (sim.hip, errsum.hip and moments.hip keep the same bound)
 constexpr int kThreads = 256;                           // four waves of 64
 constexpr int kGroup = 8;                               // lanes that hold one triangle in k_raster_tris (a power of two below 64)
 constexpr int kSmallBox = 64;                           // pixels a group walks at most (the measured default: DESIGN.md 4.26)

@@ -16,8 +16,6 @@ using namespace bsms;
 
 namespace {
 
-constexpr int kMaxC = 8;   // state / target channels handled in registers
-
 // node_in [R, C+p+1] = [state(C) | mesh_pos(p) | node_type(1)]  ->  norm_in [R, C+1] = normalised [state | type], pos [R,p]
 __global__ __launch_bounds__(256) void k_sim_prologue(const float* node_in, int64_t R, int C, int p, const double* mean,
                                                       const double* meansq, const double* eps, float* norm_in, float* pos) {

@@ -5,12 +5,11 @@
 // A memory-bound streaming reduction.  A frame is a flat array of E = n * C floats (rows of 12 bytes when C = 3, frames that start
 // at any multiple of 4 bytes): a thread owns kElems elements kThreads apart -- every load of a wave is one contiguous run of 256
 // bytes, whatever n * C is -- and walks the frames of its chunk through a ring of kRing frames in registers (two being summed, the
-// others in flight), so every state element is read once (a chunk re-reads its first frame).  Deterministic, no atomics: k_moment_pieces
-// reduces a piece (slab x frame chunk) by fixed trees, k_moment_finish adds the pieces of an entry in index order.
+// others in flight), so every state element is read once (a chunk re-reads its first frame).  Deterministic, no atomics: the piece
+// sum of piece_sum.h with a piece = slab x frame chunk; k_moment_finish is table-driven (R comes from the shapes)
+// and adds the pieces of an entry with the shared in-order add, bsms_moment_fold is the shared row fold.
 // Compiled with -ffp-contract=off (build.py): the sums keep the roundings of separate fp64 multiplies and adds.
-#include <algorithm>
-
-#include "../common.h"
+#include "../piece_sum.h"
 #include "../../../include/bsms_hip_stats.h"
 
 #pragma clang fp contract(off)
@@ -19,7 +18,6 @@ using namespace bsms;
 
 namespace {
 
-constexpr int kMaxC = 8;                                // state channels (sim.hip, batch.hip and errsum.hip keep the same bound)
 constexpr int kMaxValid = 4;                            // node-type codes that count for the mask (batch.hip)
 constexpr int kMaxW = 4 * kMaxC + 4;                    // columns of a row of `sums`
 constexpr int kThreads = 256;                           // four waves of 64
@@ -66,7 +64,6 @@ __device__ __forceinline__ void type_terms(float ty, const MomentArgs& a, double
 template <int C>
 __global__ __launch_bounds__(kThreads) void k_moment_pieces(const MomentArgs a, double* __restrict__ partials) {
   constexpr int kCols = 4 * C + 3;
-  __shared__ double red[kThreads / 64][kCols];
   const int64_t blk = a.blk_off + int64_t(blockIdx.x);
   // which entry does this block belong to: block-uniform search over at most 64 entries of the argument table
   int lo = 0, hi = a.n_entries - 1;
@@ -163,23 +160,7 @@ __global__ __launch_bounds__(kThreads) void k_moment_pieces(const MomentArgs a, 
       acc[3 + 3 * C + c] += mine ? qd[q] : 0.0;
     }
   }
-  // fixed trees: lanes of a wave by shuffle, then the four waves in order
-  const int lane = int(threadIdx.x) & 63, wave = int(threadIdx.x) >> 6;
-#pragma unroll
-  for (int k = 0; k < kCols; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (int(threadIdx.x) < kCols) {
-    const int k = int(threadIdx.x);
-    double v = red[0][k];
-#pragma unroll
-    for (int w = 1; w < kThreads / 64; ++w) v += red[w][k];
-    partials[blk * kCols + k] = v;
-  }
+  psum::block_sum<kThreads>(acc, psum::Dense<kCols>(), partials + blk * kCols);
 }
 
 // row of entry k of the launch: R from the shapes, every other column the entry's pieces in index order; one block per entry
@@ -190,42 +171,8 @@ __global__ __launch_bounds__(64) void k_moment_finish(const MomentArgs a, int C,
   if (col >= W) return;
   const int64_t E = en.n * C;
   const int64_t pieces = (en.n == 0 || en.frames == 0) ? 0 : ((E + kSlab - 1) / kSlab) * ((en.frames + kFrameChunk - 1) / kFrameChunk);
-  double v = 0.0;
-  if (col == 0) {
-    v = double(en.frames * en.n);
-  } else {
-#pragma unroll 8
-    for (int64_t p = 0; p < pieces; ++p) v += partials[(en.blk0 + p) * cols + (col - 1)];   // loads ahead, adds in order
-  }
-  sums[int64_t(blockIdx.x) * W + col] = v;
-}
-
-// out[col] = sum_s sums[s, col]: the rows in ascending order, one thread per column
-__global__ __launch_bounds__(64) void k_moment_fold(const double* __restrict__ sums, int64_t S, int64_t W, double* __restrict__ out) {
-  const int64_t col = int64_t(blockIdx.x) * 64 + int(threadIdx.x);
-  if (col >= W) return;
-  double v = 0.0;
-#pragma unroll 8
-  for (int64_t s = 0; s < S; ++s) v += sums[s * W + col];         // loads ahead, adds in order
-  out[col] = v;
-}
-
-template <int C>
-void launch_pieces(unsigned nb, hipStream_t s, const MomentArgs& a, double* partials) {
-  hipLaunchKernelGGL((k_moment_pieces<C>), dim3(nb), dim3(kThreads), 0, s, a, partials);
-}
-
-void launch_pieces_by_c(int C, unsigned nb, hipStream_t s, const MomentArgs& a, double* partials) {
-  switch (C) {
-    case 1: launch_pieces<1>(nb, s, a, partials); break;
-    case 2: launch_pieces<2>(nb, s, a, partials); break;
-    case 3: launch_pieces<3>(nb, s, a, partials); break;
-    case 4: launch_pieces<4>(nb, s, a, partials); break;
-    case 5: launch_pieces<5>(nb, s, a, partials); break;
-    case 6: launch_pieces<6>(nb, s, a, partials); break;
-    case 7: launch_pieces<7>(nb, s, a, partials); break;
-    default: launch_pieces<8>(nb, s, a, partials); break;
-  }
+  sums[int64_t(blockIdx.x) * W + col] =
+      col == 0 ? double(en.frames * en.n) : psum::add_in_order(partials + en.blk0 * cols + (col - 1), pieces, cols);
 }
 
 }  // namespace
@@ -284,11 +231,13 @@ extern "C" int bsms_moment_sums(const bsms_moment_traj* trajs, int64_t S, int64_
       a.e[k].blk0 = blocks;
     }
     a.n_entries = cnt;
-    for (int64_t b0 = 0; b0 < blocks; b0 += kMaxBlocksPerLaunch) {
+    const int rc = psum::for_block_slices(blocks, kMaxBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
       a.blk_off = b0;
-      launch_pieces_by_c(int(C), unsigned(std::min(kMaxBlocksPerLaunch, blocks - b0)), s, a, partials);
-      BSMS_LAUNCH_CHECK();
-    }
+      psum::by_channels(int(C), [&](auto c) {
+        hipLaunchKernelGGL((k_moment_pieces<decltype(c)::value>), dim3(nb), dim3(kThreads), 0, s, a, partials);
+      });
+    });
+    if (rc) return rc;
     a.blk_off = 0;
     hipLaunchKernelGGL(k_moment_finish, dim3(unsigned(cnt)), dim3(64), 0, s, a, int(C), partials, sums + first * W);
     BSMS_LAUNCH_CHECK();
@@ -301,7 +250,7 @@ extern "C" int bsms_moment_fold(const double* sums, int64_t S, int64_t W, double
   BSMS_REQUIRE(W >= 1 && W <= 65536, BSMS_E_UNSUPPORTED, "moment_fold: W=%lld (W in 1..65536)", (long long)W);
   BSMS_REQUIRE(S >= 0, BSMS_E_INVALID_ARG, "moment_fold: S=%lld", (long long)S);
   BSMS_REQUIRE(out && (sums || S == 0), BSMS_E_INVALID_ARG, "moment_fold: null argument");
-  hipLaunchKernelGGL(k_moment_fold, dim3(unsigned(ceil_div(W, 64))), dim3(64), 0, as_stream(stream), sums, S, W, out);
+  psum::launch_fold(sums, S, W, W, out, as_stream(stream));
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
