@@ -121,8 +121,13 @@ Work carve_work(void* base, const Shape& s, bool recompute = false) {
 constexpr int kBwdFlags = BSMS_BWD_DEFER_JOIN | BSMS_BWD_RECOMPUTE | BSMS_BWD_FROZEN_BF16;   // (the last changes no size)
 constexpr int kFwdReuse = 1 | 2 | BSMS_FWD_LEAN;
 
-int make_shape(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int H, int precision, Shape* s, const char* who) {
+// `block_who`: the name under which a block call of this entry reports a bad block shape (the depth is refused here, in its words)
+int make_shape(const bsms_plan_t* const* plans, int L, int64_t B, int64_t D, int64_t p, int H, int precision, Shape* s, const char* who,
+               const char* block_who = nullptr) {
   BSMS_REQUIRE(plans != nullptr && L >= 0 && L <= kMaxLevels, BSMS_E_INVALID_ARG, "%s: unet_depth %d (0..%d)", who, L, kMaxLevels);
+  // (before anything is carved: the blocks' layouts index per-stage arrays of kMaxStages entries, and a size query over a depth no
+  // block accepts must answer 0, as those of a single block do, not the size of the level inputs alone)
+  BSMS_REQUIRE(H >= 1 && H < kMaxStages, BSMS_E_UNSUPPORTED, "%s: hidden=%d (1..%d)", block_who ? block_who : who, H, kMaxStages - 1);
   s->L = L; s->B = B; s->D = D; s->p = p; s->H = H; s->prec = precision; s->plans = plans;
   for (int i = 0; i <= L; ++i) {
     BSMS_REQUIRE(plans[i] != nullptr, BSMS_E_INVALID_ARG, "%s: plan of level %d is null", who, i);
@@ -210,7 +215,7 @@ extern "C" int bsms_bsgmp_fwd_p(const bsms_plan_t* const* plans, const float* co
   const bool lean = reuse & BSMS_FWD_LEAN;
   BSMS_REQUIRE(!lean || saved, BSMS_E_INVALID_ARG, "bsgmp_fwd: BSMS_FWD_LEAN needs `saved` (bsms_bsgmp_saved_bytes_ex)");
   Shape s;
-  int rc = make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_fwd");
+  int rc = make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_fwd", "gmp_fwd");
   if (rc) return rc;
   BSMS_REQUIRE(h && pos && params && out && work && (ew || L == 0), BSMS_E_INVALID_ARG, "bsgmp_fwd: null argument");
   hipStream_t st = as_stream(stream);
@@ -420,7 +425,7 @@ int bsgmp_bwd_impl(const bsms_plan_t* const* plans, const float* const* ew, int 
   const bool recompute = flags & BSMS_BWD_RECOMPUTE;
   BSMS_REQUIRE(!recompute || saved, BSMS_E_INVALID_ARG, "bsgmp_bwd: BSMS_BWD_RECOMPUTE needs the lean `saved` of the forward");
   Shape s;
-  int rc = make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_bwd");
+  int rc = make_shape(plans, L, B, D, p, hidden, precision, &s, "bsgmp_bwd", "gmp_bwd");
   if (rc) return rc;
   BSMS_REQUIRE(h && pos && grad_out && params && saved && work && grad_h && (ew || L == 0), BSMS_E_INVALID_ARG,
                "bsgmp_bwd: null argument");

@@ -224,6 +224,18 @@ size_t wgrad_work_bytes(int D, int njobs);
 int launch_wgrad(int D, const WgradJob* jobs, int njobs, void* work, hipStream_t s, unsigned skip_mask);
 static_assert(kMaxWgradJobs <= 32, "launch_wgrad: one bit per job");
 
+// The depth envelope, hidden = 1 .. kMaxStages - 1 (GmpShape::check, check_mlp), against every fixed-size table that grows with it
+// (DESIGN.md 4.28).  The counts are those of the code that fills the tables: gmp.hip block_pack_table / GmpBwd::lane0_wgrads,
+// mlp.hip mlp_pack_table / bsms_mlp_bwd_ex, chain_launch.h (the loader sequences).
+constexpr int kMaxHidden = kMaxStages - 1;
+constexpr int gmp_block_packs(int H) { return 9 + 4 * H; }       // a training block: 5 of the first edge Linear, 4 of the first node Linear, 2 per D x D Linear of either MLP
+constexpr int mlp_packs(int H) { return 1 + 2 * (H + 1); }       // a training MLP: the narrow transpose, 2 per Linear
+constexpr int gmp_block_wgrad_jobs(int H) { return 2 * H + 2; }  // lane 0: H edge Linears, H node Linears, the two halves of the first node Linear
+static_assert(gmp_block_packs(kMaxHidden) <= kMaxPack && mlp_packs(kMaxHidden) <= kMaxPack, "PackTable::d holds the packs of the deepest block");
+static_assert(gmp_block_wgrad_jobs(kMaxHidden) <= kMaxWgradJobs && kMaxHidden + 1 <= kMaxWgradJobs, "one wgrad launch holds the jobs of the deepest block");
+static_assert(kBoundSlots == 4 * 8 && kMaxHidden + 1 <= 8, "bound slots: four groups of 8, hidden + 1 entries used in each ([16 + H], [24 + H] are the last)");
+static_assert(kMaxHidden + 2 <= kMaxStages + 2, "wseq: the node chains stream hidden + 2 packs (IN_ROWS2 forward, F_HEADS2 backward)");
+
 // small-side weight gradients: out[s*os + f*of] = sum_r G[r][f] * S[r][s],  s < S (<= 8)
 struct SmallWgradArgs {
   const float* G;  // [R,D]

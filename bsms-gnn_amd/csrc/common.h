@@ -132,6 +132,9 @@ int gmp_pos_grad(const bsms_plan* plan, const void* gE0, bool g_bf16, const floa
                  int64_t D, int64_t p, int64_t pos_bstride, float* grad_pos, bool accumulate, float* scratch, hipStream_t s);
 // out [R,K] = G [R,D] . W[:, 0:K] (W [D,K] row-major): the input gradient of an MLP whose first Linear is narrow (K <= 8)
 int narrow_input_grad(const float* G, int64_t R, int64_t D, const float* W, int K, float* out, hipStream_t s);
+// posgrad.hip: db = column sums of the LayerNorm backward of dy, in fp32 (D = 128 / 256); `part`: ln_bias_grad_work_floats(D) floats of scratch
+size_t ln_bias_grad_work_floats(int64_t D);
+int ln_bias_grad(const float* dy, const float* yln, const float* rstd, int64_t R, int64_t D, float* part, float* db, hipStream_t s);
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 // bsms_plan_concat (plan.hip: host side; rowsum.hip: the kernel -- plan.hip is also compiled as plain C++ for the sanitizer build):

@@ -468,7 +468,14 @@ struct GmpBwd {
       if (!bfn) for (int k = 0; k <= H; ++k) a.gmax[k] = sv.bound + size_t(24 + k) * kBoundWidth;
       else a.gmax[H] = sv.bound + size_t(24 + H) * kBoundWidth;   // BSMS_BF16_NODES: only gN[0] (fp32) feeds an fp32 weight-gradient job
     }
-    return launch_chain_bwd((int)D, G_ROWS_LN, F_HEADS2, a, s);
+    const int rc = launch_chain_bwd((int)D, G_ROWS_LN, F_HEADS2, a, s);
+    if (rc || !bfn || !nlive) return rc;
+    // BSMS_BF16_NODES: gN[H] is stored as bf16 rows for the weight-gradient products, and the last node Linear's bias gradient used to
+    // be the column sum of those rounded rows: 2^-9 of the fp32 sum at any depth.  It is summed from the unrounded LayerNorm backward
+    // instead (posgrad.hip: ln_bias_grad; lane0_wgrads gives that job no db).  On the caller's stream, in front of the forks: grad_out
+    // belongs to the caller, who may rewrite it while the lanes still run, and the split-K area is this block's own until lane 0 starts.
+    BSMS_REQUIRE(ln_bias_grad_work_floats(D) * sizeof(float) <= wgrad_work_bytes((int)D, 0), BSMS_E_SHAPE, "gmp_bwd: bias-gradient partials exceed the split-K area");
+    return ln_bias_grad(grad_out, sv.n_yln, sv.n_rstd, B * N, D, reinterpret_cast<float*>(wk.wg), gn[2 * H + 1], s);
   }
 
   // edge MLP backward (gradient of the aggregation = gather by target)
@@ -532,7 +539,7 @@ struct GmpBwd {
       if (!elive) skip |= 1u << (nj - 1);
     }
     for (int l = 1; l <= H; ++l) {   // node Linears 1..H: bf16 tensors in BSMS_BF16_NODES
-      jobs[nj++] = job(wk.gN[l], sv.n_act[l - 1], GN(2 * l), GN(2 * l + 1), B * N, (int)D, 0, nbd(24 + (H - l), 2), nbd(8 + l, 2));
+      jobs[nj++] = job(wk.gN[l], sv.n_act[l - 1], GN(2 * l), (bfn && l == H) ? nullptr : GN(2 * l + 1), B * N, (int)D, 0, nbd(24 + (H - l), 2), nbd(8 + l, 2));   // (bfn, l == H: node_chain)
       jobs[nj - 1].bf16 = bfn;
       if (!nlive) skip |= 1u << (nj - 1);
     }

@@ -238,4 +238,105 @@ int narrow_input_grad(const float* G, int64_t R, int64_t D, const float* W, int 
   }
 }
 
+// Bias gradient of a Linear whose output goes through LayerNorm (no affine), from fp32: db[f] = sum_r g[r][f] with the LayerNorm
+// backward g[r] = rstd_r (dy[r] - mean(dy[r]) - yln[r] mean(dy[r] yln[r])).  BSMS_BF16_NODES stores that gradient as bf16 rows for the
+// weight-gradient products; a column sum of the rounded rows sits 2^-9 from the fp32 one at any depth (the roundings do not
+// average out against a sum that cancels), so the bias takes this sum of the unrounded rows instead (gmp.hip: GmpBwd::node_chain).
+// Two launches in a fixed order, no atomics: run-to-run bit-identical.  Streams dy and yln once (HBM-bound: R * D * 8 bytes).
+namespace {
+constexpr int kLnBiasMaxBlocks = 128;   // partial rows: the second launch adds them in 128 / 8 (D = 128) or 128 / 4 dependent steps
+
+struct LnBiasArgs {
+  const float *dy, *yln, *rstd;   // [R, D], [R, D], [R]
+  int64_t R;
+  float* part;                    // [gridDim.x, D] one partial row per workgroup
+  float* db;                      // [D]
+  int nblk;
+};
+
+template <int LPR>   // lanes per row = D / 4 (32 or 64): a wave takes 64 / LPR rows per pass
+__global__ __launch_bounds__(256) void k_ln_bias_part(LnBiasArgs a) {
+  constexpr int RPW = 64 / LPR, D = 4 * LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane / LPR, l = lane % LPR;
+  const int64_t step = int64_t(gridDim.x) * 4 * RPW;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int64_t r0 = (int64_t(blockIdx.x) * 4 + wave) * RPW; r0 < a.R; r0 += step) {   // r0 is uniform over the wave: every lane reaches the shuffles
+    const int64_t r = r0 + sub;
+    float4 g = make_float4(0.f, 0.f, 0.f, 0.f), y = g;
+    float rs = 0.f;
+    if (r < a.R) {
+      g = *reinterpret_cast<const float4*>(a.dy + r * D + 4 * l);
+      y = *reinterpret_cast<const float4*>(a.yln + r * D + 4 * l);
+      rs = a.rstd[r];
+    }
+    float s1 = (g.x + g.y) + (g.z + g.w), s2 = (g.x * y.x + g.y * y.y) + (g.z * y.z + g.w * y.w);
+#pragma unroll
+    for (int m = LPR / 2; m >= 1; m >>= 1) {
+      s1 += __shfl_xor(s1, m, LPR);
+      s2 += __shfl_xor(s2, m, LPR);
+    }
+    s1 *= 1.f / D;
+    s2 *= 1.f / D;
+    acc.x += rs * (g.x - s1 - y.x * s2);
+    acc.y += rs * (g.y - s1 - y.y * s2);
+    acc.z += rs * (g.z - s1 - y.z * s2);
+    acc.w += rs * (g.w - s1 - y.w * s2);
+  }
+  __shared__ float4 sh[256];
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x < LPR) {   // waves, then row slots, in order
+    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int w = 0; w < 4; ++w)
+      for (int q = 0; q < RPW; ++q) {
+        const float4 v = sh[w * 64 + q * LPR + threadIdx.x];
+        t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
+      }
+    *reinterpret_cast<float4*>(a.part + int64_t(blockIdx.x) * D + 4 * threadIdx.x) = t;
+  }
+}
+
+template <int LPR>   // 256 / LPR groups of threads take the partial rows in turn, then the groups are added in order
+__global__ __launch_bounds__(256) void k_ln_bias_sum(LnBiasArgs a) {
+  constexpr int G = 256 / LPR, D = 4 * LPR;
+  const int q = threadIdx.x / LPR, l = threadIdx.x % LPR;
+  float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+  for (int b = q; b < a.nblk; b += G) {
+    const float4 v = *reinterpret_cast<const float4*>(a.part + int64_t(b) * D + 4 * l);
+    t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
+  }
+  __shared__ float4 sh[256];
+  sh[threadIdx.x] = t;
+  __syncthreads();
+  if (threadIdx.x < LPR) {
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int g = 0; g < G; ++g) {
+      const float4 v = sh[g * LPR + threadIdx.x];
+      r.x += v.x; r.y += v.y; r.z += v.z; r.w += v.w;
+    }
+    float* const out = a.db + 4 * threadIdx.x;   // (scalar stores: a bias gradient may sit at any 4-byte offset of a flat buffer)
+    out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
+  }
+}
+}  // namespace
+
+size_t ln_bias_grad_work_floats(int64_t D) { return size_t(kLnBiasMaxBlocks) * size_t(D); }
+
+int ln_bias_grad(const float* dy, const float* yln, const float* rstd, int64_t R, int64_t D, float* part, float* db, hipStream_t s) {
+  BSMS_REQUIRE(D == 128 || D == 256, BSMS_E_UNSUPPORTED, "ln_bias_grad: D=%lld (128 / 256: the widths of the bf16 precisions)", (long long)D);
+  BSMS_REQUIRE(dy && yln && rstd && part && db && R >= 0, BSMS_E_INVALID_ARG, "ln_bias_grad: null argument");
+  LnBiasArgs a{};
+  a.dy = dy; a.yln = yln; a.rstd = rstd; a.R = R; a.part = part; a.db = db;
+  const int rows_per_wg = D == 128 ? 8 : 4;
+  a.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(R, rows_per_wg), kLnBiasMaxBlocks));
+  if (D == 128) hipLaunchKernelGGL((k_ln_bias_part<32>), dim3(a.nblk), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((k_ln_bias_part<64>), dim3(a.nblk), dim3(256), 0, s, a);
+  BSMS_LAUNCH_CHECK();
+  if (D == 128) hipLaunchKernelGGL((k_ln_bias_sum<32>), dim3(1), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((k_ln_bias_sum<64>), dim3(1), dim3(256), 0, s, a);
+  BSMS_LAUNCH_CHECK();
+  return BSMS_OK;
+}
+
 }  // namespace bsms

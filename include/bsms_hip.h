@@ -49,6 +49,8 @@
  *     order: seq.0.weight, seq.0.bias, seq.2.weight, seq.2.bias, ...  Weights are [out,in] row-major
  *     exactly as torch.nn.Linear stores them.  `grads` arrays have the same order and shapes and
  *     are OVERWRITTEN (not accumulated).
+ *   - `hidden`: 1 <= hidden <= 7 in every entry that takes one.  Outside that range the calls return
+ *     BSMS_E_UNSUPPORTED before any launch and every size query -- a block's, an MLP's, the U-Net's -- returns 0.
  */
 #ifndef BSMS_HIP_H
 #define BSMS_HIP_H
@@ -78,7 +80,8 @@ typedef enum {
  *   the hidden activations rounded to bf16 as they enter a Linear, weights rounded once per call; fp32 accumulation,
  *   bias, ReLU, LayerNorm), its hidden activations are saved as bf16 and its layer gradients gN[1..H] are stored as bf16
  *   (one-product weight-gradient jobs); the block's input / output rows [B,N,D], the residual and skip additions, the
- *   projections, gN[0] and the weight gradient of the first node Linear (operands x, aggr in fp32) stay fp32. */
+ *   projections, gN[0] and the weight gradient of the first node Linear (operands x, aggr in fp32) stay fp32, and so does the
+ *   bias gradient of the LAST node Linear: the column sum of the unrounded LayerNorm backward, not of the rows of gN[H]. */
 typedef enum { BSMS_F32 = 0, BSMS_BF16 = 1, BSMS_BF16_NODES = 2 } bsms_precision;
 
 typedef struct bsms_plan bsms_plan_t; /* one mesh level: dst-sorted CSR + src-sorted transpose */

@@ -110,7 +110,8 @@ def all_live(k, i):
     return True
 
 
-UNET_SHAPES = {"d128_h3": (128, 3), "d128_h2": (128, 2), "d256_h3": (256, 3)}     # the fused kernels; the bf16 ring kernels (twice)
+UNET_SHAPES = {"d128_h3": (128, 3), "d128_h2": (128, 2), "d256_h3": (256, 3),     # the fused kernels; the bf16 ring kernels (twice)
+               "d128_h5": (128, 5)}                                               # ... and above the fused depth
 
 
 @pytest.mark.parametrize("prec", list(PREC))

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import pick_seed, rel_err
+from conftest import KinkMargin, pick_seed, rel_err
 from oracle import bsms_oracle as ro
 
 pytestmark = pytest.mark.gpu
@@ -69,10 +69,14 @@ def run_mine(mine, x, g, pos, cot, x_grad=True, pos_grad=True):
 
 # ------------------------------------------------------------------------------------------------------------ GMP
 @pytest.mark.parametrize("shared", [False, True], ids=["pos3d", "pos2d_shared"])
-@pytest.mark.parametrize("D,p,H", [(128, 2, 3), (64, 3, 3), (256, 3, 2), (64, 7, 2), (32, 1, 2)])
+@pytest.mark.parametrize("D,p,H", [(128, 2, 3), (64, 3, 3), (256, 3, 2), (64, 7, 2), (32, 1, 2), (32, 2, 7)])
 def test_gmp_pos_grad_matches_oracle(eng, D, p, H, shared):
     B = 3
-    g, (ref, _, x, pos, cot) = gmp_case(D, p, H, B, shared)
+    g, (ref, run, x, pos, cot) = gmp_case(D, p, H, B, shared)
+    if H > 3:   # the deepest block (tests/test_hip_depth.py): many more ReLU inputs, and pick_seed hands back its best try when no seed keeps the margin
+        with KinkMargin(ref) as km, torch.no_grad():
+            run()
+        assert km.min > 1.5e-6, km.min
     y = ref(x, g, pos)
     (y * cot).sum().backward()
     mine = load_sd(eng.GMP(D, H, p), ref.state_dict())

@@ -185,6 +185,9 @@ CASES = [  # depth, D, H, shared pos, precision
     (2, 128, 3, False, "bf16"),    # the fused edge backward: e_Ps / e_Pd / e_wr in the blob
     (2, 128, 3, True, "bf16_nodes"),
     (1, 128, 2, False, "bf16"),    # bf16 without the fused edge backward (hidden = 2)
+    (2, 32, 7, False, "f32"),      # the deepest block: blobs, pack table and weight-gradient table at their largest
+    (1, 128, 5, True, "f32"),
+    (1, 128, 5, False, "bf16"),    # bf16 on the generic ring kernels, above the fused depth
 ]
 
 
