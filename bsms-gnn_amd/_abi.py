@@ -181,9 +181,29 @@ SAMPLE_SIGNATURES = {
 }
 
 
+# the fourth companion library libbsms_hip_query.so: name -> (restype, argtypes); one entry per declaration in include/bsms_hip_query.h
+QUERY_LIB_PATH = os.path.join(_HERE, "libbsms_hip_query.so")
+QUERY_SIGNATURES = {
+    "bsms_chain_launch_query": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+}
+
+
 class MomentTraj(C.Structure):
     """bsms_moment_traj (include/bsms_hip_stats.h)."""
     _fields_ = [("state", c_void_p), ("type", c_void_p), ("n", c_i64), ("frame0", c_i64), ("frames", c_i64), ("type_stride", c_i64)]
+
+
+class ChainLaunchKey(C.Structure):
+    """bsms_chain_launch_key (include/bsms_hip_query.h)."""
+    _fields_ = [("R", c_i64), ("nstage", c_int), ("nseq", c_int), ("bf16", c_int), ("store_mode", c_int), ("timing", c_int),
+                ("resid", c_int), ("act_stores", c_int), ("glast", c_int), ("gstores", c_int), ("masks", c_int)]
+
+
+class ChainLaunchInfo(C.Structure):
+    """bsms_chain_launch_info (include/bsms_hip_query.h)."""
+    _fields_ = [("family", c_int), ("rb", c_int), ("save", c_int), ("store", c_int), ("lone", c_int), ("bf16", c_int), ("timing", c_int),
+                ("cw", c_int), ("nload", c_int), ("nring", c_int), ("ntiles", c_int), ("grid", c_i64), ("threads", c_i64), ("lds", c_i64),
+                ("lds_max", c_i64), ("name", C.c_char * 48)]
 
 
 class WgradJob(C.Structure):
@@ -279,6 +299,26 @@ def sample():
             fn.restype, fn.argtypes = res, args
         _sample = handle
     return _sample
+
+
+_query = None
+
+
+def query():
+    """Load the query library (once), behind libbsms_hip.so, which it links against.  Raises if it has not been built.  For tests and
+    tools: nothing on the product path calls this."""
+    global _query
+    if _query is None:
+        lib()
+        if not os.path.exists(QUERY_LIB_PATH):
+            raise BsmsError(f"{QUERY_LIB_PATH} not found: build it with `python bsms-gnn_amd/build.py` (or __graft_entry__.build()); "
+                            "there is no CPU/PyTorch fallback")
+        handle = C.CDLL(QUERY_LIB_PATH)
+        for name, (res, args) in QUERY_SIGNATURES.items():
+            fn = getattr(handle, name)  # AttributeError if the symbol is missing
+            fn.restype, fn.argtypes = res, args
+        _query = handle
+    return _query
 
 
 def check(rc, what):

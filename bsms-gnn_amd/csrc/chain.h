@@ -33,6 +33,9 @@
 // chunk; compute waves read their A fragments with conflict-free lane-linear ds_read_b128.
 // (The bf16 PRECISION of the edge MLP -- bsms_precision -- keeps one bf16 plane per weight and its bias in chunk 0.)
 #pragma once
+#include <type_traits>
+
+#include "../../include/bsms_hip_query.h"
 #include "common.h"
 
 namespace bsms {
@@ -69,7 +72,7 @@ enum GradFirst { F_NONE = 0, F_HEADS1 = 1, F_HEADS2 = 2 };
 
 struct ChainFwdArgs {
   int64_t R;  // rows
-  int ntiles; // filled by the launcher: ceil(R / kTileRows); workgroups stride over tiles (persistent)
+  int ntiles; // filled by the launcher: ceil(R / (16 RB cw)), the tiles of this launch's cw compute waves x RB row blocks (ChainLaunch); workgroups stride over tiles (persistent)
   // ---- input stage
   const float* x;    // IN_ROWS/IN_ROWS2: [R,D]; IN_SMALL: [R,K0]
   const float* x2;   // IN_ROWS2: second source [R,D]
@@ -195,11 +198,43 @@ int pack_group_open(bsms_pack_group_t* group, const char* who, PackGroup** g);
 
 int launch_chain_fwd(int D, int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s);
 int launch_chain_bwd(int D, int gin_mode, int first_mode, const ChainBwdArgs& a, hipStream_t s);
+// The choice of a chain launch as data (chain_launch.h: plan_fwd / plan_bwd decide, the launch path and bsms_chain_launch_query read).
+// The key: what the choice reads from ChainFwdArgs / ChainBwdArgs, and nothing else (bsms_hip_query.h spells out the fields).
+using ChainLaunchKey = ::bsms_chain_launch_key;
+enum ChainStores { CHAIN_STORES_NONE = 0, CHAIN_STORES_ALL = 1, CHAIN_STORES_MIXED = 2 };   // a set of nullable store pointers
+enum ChainFamily { CHAIN_FS = 0, CHAIN_EDGE = 1, CHAIN_RING = 2, CHAIN_UNBUILT = 3 };   // k_fs_* / k_edge_* / k_chain_*; UNBUILT: refused, never launched
+struct ChainLaunch {
+  int family;                    // ChainFamily
+  int rb;                        // EDGE: row blocks per wave (1 / 2)
+  bool save, store;              // EDGE: the SAVE build of the forward / the STORE build of the backward
+  bool lone, bf16, timing;       // EDGE / RING: the single-round build; RING: the bf16 and the TIMING builds
+  int cw, nload, nring, ntiles;  // compute waves, loader waves, ring slots, tiles of 16 rb cw rows
+  unsigned grid, threads;
+  size_t lds, lds_max;           // dynamic LDS of this launch and the most any launch of the kernel asks for (launch_dyn_lds)
+  const char *what, *build;      // launcher and variant in the error text (launch_dyn_lds)
+};
 // the chain kernels of one width, NB = D / 16 = 2, 4, ... 16: defined in chain_launch.h, instantiated by one translation unit each (chain_d*.hip)
 template <int NB>
 int launch_chain_fwd_nb(int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s);
 template <int NB>
 int launch_chain_bwd_nb(int gin_mode, int first_mode, const ChainBwdArgs& a, hipStream_t s);
+template <int NB>
+int chain_launch_query_nb(int backward, int mode_a, int mode_b, const ChainLaunchKey& k, int cus, ChainLaunch* out);
+// the dispatch on the latent width: f(NB as an integral constant), one translation unit per width (chain_d32.hip ... chain_d256.hip)
+template <class F>
+int with_width(int D, F&& f) {
+  switch (D) {
+    case 32: return f(std::integral_constant<int, 2>{});
+    case 64: return f(std::integral_constant<int, 4>{});
+    case 96: return f(std::integral_constant<int, 6>{});
+    case 128: return f(std::integral_constant<int, 8>{});
+    case 160: return f(std::integral_constant<int, 10>{});
+    case 192: return f(std::integral_constant<int, 12>{});
+    case 224: return f(std::integral_constant<int, 14>{});
+    case 256: return f(std::integral_constant<int, 16>{});
+  }
+  BSMS_FAIL(BSMS_E_UNSUPPORTED, "latent width D=%d not supported (a multiple of 32, 32..256)", D);
+}
 
 // weight gradients ------------------------------------------------------------------------------
 struct WgradJob {

@@ -202,32 +202,12 @@ int launch_prepack_group(PackGroup& g, hipStream_t s) {
 
 int launch_chain_fwd(int D, int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s) {
   if (a.R == 0) return BSMS_OK;
-  switch (D) {   // one translation unit per width: chain_d32.hip ... chain_d256.hip
-    case 32: return launch_chain_fwd_nb<2>(in_mode, out_mode, a, s);
-    case 64: return launch_chain_fwd_nb<4>(in_mode, out_mode, a, s);
-    case 96: return launch_chain_fwd_nb<6>(in_mode, out_mode, a, s);
-    case 128: return launch_chain_fwd_nb<8>(in_mode, out_mode, a, s);
-    case 160: return launch_chain_fwd_nb<10>(in_mode, out_mode, a, s);
-    case 192: return launch_chain_fwd_nb<12>(in_mode, out_mode, a, s);
-    case 224: return launch_chain_fwd_nb<14>(in_mode, out_mode, a, s);
-    case 256: return launch_chain_fwd_nb<16>(in_mode, out_mode, a, s);
-  }
-  BSMS_FAIL(BSMS_E_UNSUPPORTED, "latent width D=%d not supported (a multiple of 32, 32..256)", D);
+  return with_width(D, [&](auto nb) { return launch_chain_fwd_nb<decltype(nb)::value>(in_mode, out_mode, a, s); });
 }
 
 int launch_chain_bwd(int D, int gin, int first, const ChainBwdArgs& a, hipStream_t s) {
   if (a.R == 0) return BSMS_OK;
-  switch (D) {
-    case 32: return launch_chain_bwd_nb<2>(gin, first, a, s);
-    case 64: return launch_chain_bwd_nb<4>(gin, first, a, s);
-    case 96: return launch_chain_bwd_nb<6>(gin, first, a, s);
-    case 128: return launch_chain_bwd_nb<8>(gin, first, a, s);
-    case 160: return launch_chain_bwd_nb<10>(gin, first, a, s);
-    case 192: return launch_chain_bwd_nb<12>(gin, first, a, s);
-    case 224: return launch_chain_bwd_nb<14>(gin, first, a, s);
-    case 256: return launch_chain_bwd_nb<16>(gin, first, a, s);
-  }
-  BSMS_FAIL(BSMS_E_UNSUPPORTED, "latent width D=%d not supported (a multiple of 32, 32..256)", D);
+  return with_width(D, [&](auto nb) { return launch_chain_bwd_nb<decltype(nb)::value>(gin, first, a, s); });
 }
 
 }  // namespace bsms

@@ -5,6 +5,7 @@
 namespace bsms {
 template int launch_chain_fwd_nb<8>(int, int, const ChainFwdArgs&, hipStream_t);
 template int launch_chain_bwd_nb<8>(int, int, const ChainBwdArgs&, hipStream_t);
+template int chain_launch_query_nb<8>(int, int, int, const ChainLaunchKey&, int, ChainLaunch*);
 }  // namespace bsms
 
 // experiments only (not in bsms_hip.h): what residency does the runtime compute for the D = 128 edge chains?

@@ -5,4 +5,5 @@
 namespace bsms {
 template int launch_chain_fwd_nb<12>(int, int, const ChainFwdArgs&, hipStream_t);
 template int launch_chain_bwd_nb<12>(int, int, const ChainBwdArgs&, hipStream_t);
+template int chain_launch_query_nb<12>(int, int, int, const ChainLaunchKey&, int, ChainLaunch*);
 }  // namespace bsms

@@ -1,8 +1,12 @@
-// Host side of the chain kernels: launch shapes, the choice of the kernel variant, and the two entry points of a width,
-// launch_chain_fwd_nb<NB> / launch_chain_bwd_nb<NB> (chain.h), which chain_d*.hip instantiates explicitly.
+// Host side of the chain kernels.  The choice of a launch is DATA: plan_fwd / plan_bwd map a ChainLaunchKey (what the choice reads
+// from the arguments) and a CU count to a ChainLaunch (family, variant, shape) without touching the device; launch_fwd_t /
+// launch_bwd_t build the key, call them and run ONE switch from the record to the instantiation; chain_launch_query_nb answers
+// bsms_chain_launch_query from the same two functions.  The entry points of a width, launch_chain_fwd_nb<NB> /
+// launch_chain_bwd_nb<NB> / chain_launch_query_nb<NB> (chain.h), are instantiated explicitly by chain_d*.hip.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "chain_edge.h"
 #include "chain_kernels.h"
@@ -18,6 +22,12 @@ namespace {
 // (profiles/width_rates.txt: resource table).
 template <int NB>
 constexpr int resident_per_cu() { return NB <= 4 ? 4 : NB == 8 ? 2 : 1; }
+// the same for the edge kernels with `rb` row blocks per wave (chain_edge.h)
+template <int NB>
+constexpr int edge_resident(int rb) { return rb == 2 ? EdgeTile<NB, 2>::resident : EdgeTile<NB, 1>::resident; }
+
+// THE one-round predicate: `tiles` fit one round of `room` workgroups (room = the CU count: at most one workgroup per CU)
+inline bool one_round(int64_t tiles, int64_t room) { return tiles <= room; }
 
 // Compute waves per workgroup of a generic chain launch: 4 (64-row tiles), or up to 7 when that makes the launch fit ONE
 // round of resident workgroups.  A workgroup streams the whole weight set once per tile (~23 us for the node MLP: the
@@ -25,18 +35,11 @@ constexpr int resident_per_cu() { return NB <= 4 ? 4 : NB == 8 ? 2 : 1; }
 // airfoil step (41 864 rows = 655 tiles of 64 on 512 slots) run as 437 tiles of 96 rows instead.  The SPI accounts a
 // 5-wave workgroup like an 8-wave one anyway (resident_per_cu), so the extra waves use slots that were empty.
 template <int NB>
-int chain_compute_waves(int64_t R) {
-  const int cus = device_cu_count();
+int chain_compute_waves(int64_t R, int cus) {
   const int64_t slots = int64_t(cus) * resident_per_cu<NB>();
-  if (resident_per_cu<NB>() >= 4 || ceil_div(R, kTileRows) <= slots) return kComputeWaves;   // D = 32 / 64: always 4
+  if (resident_per_cu<NB>() >= 4 || one_round(ceil_div(R, kTileRows), slots)) return kComputeWaves;   // D = 32 / 64: always 4
   const int64_t need = ceil_div(R, slots * 16);   // waves per workgroup for one round
   return need <= 7 ? (int)need : kComputeWaves;
-}
-
-template <int NB>
-unsigned persistent_grid(int64_t ntiles) {
-  const int cus = device_cu_count();
-  return (unsigned)std::min<int64_t>(ntiles, int64_t(cus) * resident_per_cu<NB>());
 }
 
 // Launch shape knobs.  Production values are the defaults; experiment builds read them from the environment for
@@ -78,16 +81,16 @@ int edge_compute_waves() {
 // cylinder level 0 (90 112 rows, 512 slots) runs 2 rounds with 7, 6 waves and 3 with 5, 4 -- 6 waves win by the shorter
 // tile (same-box sweep: 4 / 5 / 6 / 7 waves = 400.1 / 392.6 / 404.4 / 397.2 steps/s, exactly this model's order).  The
 // slope t1 / t0 = 0.53 per wave with one row block per wave comes from the airfoil sweep (7 against 4 waves: +2.5 %).
-template <int NB, int RB>
-int pick_edge_waves(int64_t R) {
+template <int NB>
+int pick_edge_waves(int64_t R, int rb, int cus) {
   const int fixed = edge_compute_waves<NB>();
 #ifdef BSMS_EXPERIMENTS
   if (getenv(NB >= 16 ? "BSMS_EDGE_CW16" : "BSMS_EDGE_CW") || getenv("BSMS_EDGE_CW_FIXED")) return fixed;
 #endif
-  const double slope = (NB >= 16 ? 0.25 : 0.53) * RB;
-  const int64_t slots = int64_t(device_cu_count()) * EdgeTile<NB, RB>::resident;
+  const double slope = (NB >= 16 ? 0.25 : 0.53) * rb;
+  const int64_t slots = int64_t(cus) * edge_resident<NB>(rb);
   auto cost_of = [&](int cw) {
-    const int64_t tiles = ceil_div(R, int64_t(16) * RB * cw);
+    const int64_t tiles = ceil_div(R, int64_t(16) * rb * cw);
     const int64_t per = ceil_div(tiles, std::min<int64_t>(tiles, slots));
     return double(per) * (1.0 + slope * cw);
   };
@@ -109,112 +112,231 @@ inline int chain_loader_waves() {
   return nl;
 }
 
-// Weight stream of a launch: loader waves and ring depth (Ring).  A launch that fits ONE round of workgroups (at most
-// one workgroup per CU: the coarse mesh levels, most node-level launches) has the CU's whole LDS and nothing to overlap
-// its chunk latency with: deep ring (up to 6 slots = 5 chunks in flight) fed by two loader waves.  Anything larger keeps
-// 3 slots so that two workgroups share a CU.  Limits: compute + loader waves <= 8; (nr - 2) x pieces per loader <= 63
-// (vmcnt field); ring + side tables <= 160 KB.
-template <int NB, int PL = kPL>
-int max_ring() { return (int)std::min<size_t>(6, (size_t(160) * 1024 - Ring<NB, PL>::PRE_FLOATS * sizeof(float)) / (Ring<NB, PL>::CHF * sizeof(float))); }
-template <int NB, int PL = kPL>
-void pick_stream(int64_t ntiles, int cw, int nload_default, int& nload, int& nring) {
-  static const int deep = knob("BSMS_RING_DEEP", 6), lone_nl = knob("BSMS_LONE_NL", 2), shared = knob("BSMS_RING", 3);
-  nload = std::max(1, std::min(nload_default, 8 - cw));
-  nring = std::min(shared, max_ring<NB, PL>());
-  if (ntiles <= device_cu_count()) {
-    nload = std::max(nload, std::min(lone_nl, 8 - cw));
-    nring = std::min(deep, max_ring<NB, PL>());
-  }
-  const int mine = (Ring<NB, PL>::PER + nload - 1) / nload;
-  while (nring > 3 && (nring - 2) * mine > 63) --nring;
-}
-
-template <int NB>
-size_t ring_lds_max() { return Ring<NB>::lds_bytes(max_ring<NB>()); }
-
-template <int NB, int RB, int SAVE>
-int launch_edge_fwd_t(ChainFwdArgs& a, hipStream_t s) {
-  const int cw = pick_edge_waves<NB, RB>(a.R);
-  a.ntiles = (int)ceil_div(a.R, 16 * RB * cw);
-  pick_stream<NB>(a.ntiles, cw, edge_loader_waves<NB>(), a.nload, a.nring);
-  const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, int64_t(device_cu_count()) * EdgeTile<NB, RB>::resident);
-  const unsigned threads = (cw + a.nload) * 64;
-  const size_t lds = Ring<NB>::lds_bytes(a.nring);
-  static const int lone = knob("BSMS_EDGE_LONE", 1);
-  if (lone && a.ntiles <= device_cu_count() && !a.timing)   // one round of workgroups: the variant that passes the chunk barrier early (stage_rb<LONE>)
-    return launch_dyn_lds<k_edge_fwd<NB, RB, SAVE, true>>("edge_fwd", "single-round build", grid, threads, lds, ring_lds_max<NB>(), a, s);
-  return launch_dyn_lds<k_edge_fwd<NB, RB, SAVE>>("edge_fwd", nullptr, grid, threads, lds, ring_lds_max<NB>(), a, s);
-}
-
-// the software-pipelined edge kernels take the production configuration only; anything else stays on k_chain_fwd
-template <int NB>
-bool launch_edge_fwd(ChainFwdArgs& a, hipStream_t s, int& rc) {
-  if (a.bf16 || a.nstage < 1 || a.store_mode != 1 || a.resid || a.resid2 || edge_rb_mode() == 0 || a.R >= (int64_t(1) << 31)) return false;
-  const bool save = a.store_in != nullptr;
-  for (int l = 0; l + 1 < a.nstage; ++l)
-    if ((a.store[l] != nullptr) != save) return false;
-  constexpr int RBIG = NB == 8 ? 2 : 1;
-  // Measured per level (profiles/r02_edge_levels.md): with several tiles per workgroup two workgroups per CU of one row
-  // block per wave win the forward (the random row gathers of one hide under the other's MFMA stages); a launch that
-  // fits one round of workgroups is faster with two row blocks per wave, and so is the whole backward (its loads are
-  // sequential or local).  Below half a round of 128-row tiles the narrow tile keeps more CUs busy.
-  const int64_t cus = device_cu_count(), rows1 = 16 * edge_compute_waves<NB>();   // rows of a tile with one row block per wave
-  bool big = RBIG == 2 && a.R >= cus * rows1 && ceil_div(a.R, rows1) <= cus * EdgeTile<NB, 1>::resident;
-  if (edge_rb_mode() > 0) big = RBIG == 2 && edge_rb_mode() == 2;
-  if (big) rc = save ? launch_edge_fwd_t<NB, RBIG, 1>(a, s) : launch_edge_fwd_t<NB, RBIG, 0>(a, s);
-  else rc = save ? launch_edge_fwd_t<NB, 1, 1>(a, s) : launch_edge_fwd_t<NB, 1, 0>(a, s);
-  return true;
-}
-
-template <int NB, int RB, bool STORE>
-int launch_edge_bwd_t(ChainBwdArgs& a, hipStream_t s) {
-  const int cw = pick_edge_waves<NB, RB>(a.R);
-  a.ntiles = (int)ceil_div(a.R, 16 * RB * cw);
-  pick_stream<NB>(a.ntiles, cw, edge_loader_waves<NB>(), a.nload, a.nring);
-  const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, int64_t(device_cu_count()) * EdgeTile<NB, RB>::resident);
-  const unsigned threads = (cw + a.nload) * 64;
-  const size_t lds = Ring<NB>::lds_bytes(a.nring);
-  static const int lone = knob("BSMS_EDGE_LONE", 1);
-  if (lone && a.ntiles <= device_cu_count())   // see launch_edge_fwd_t
-    return launch_dyn_lds<k_edge_bwd<NB, RB, true, STORE>>("edge_bwd", STORE ? "single-round build" : "single-round no-store build", grid, threads, lds, ring_lds_max<NB>(), a, s);
-  return launch_dyn_lds<k_edge_bwd<NB, RB, false, STORE>>("edge_bwd", STORE ? nullptr : "no-store build", grid, threads, lds, ring_lds_max<NB>(), a, s);
-}
-
-template <int NB>
-bool launch_edge_bwd(ChainBwdArgs& a, hipStream_t s, int& rc) {
-  if (a.bf16 || a.nstage < 1 || a.store_mode != 1 || edge_rb_mode() == 0 || a.R >= (int64_t(1) << 31)) return false;
-  // the layer gradients gstore[0 .. nstage-1]: all kept, or none (a frozen edge MLP: the no-store build; tile, ring and single-round
-  // choices are the storing launch's).  The last gradient, gstore[nstage], always has a reader.
-  if (!a.gstore[a.nstage]) return false;
-  const bool store = a.gstore[0] != nullptr;
-  for (int k = 0; k < a.nstage; ++k)
-    if ((a.gstore[k] != nullptr) != store || !a.mask[k]) return false;
-  constexpr int RBIG = NB == 8 ? 2 : 1;
-  bool big = RBIG == 2 && a.R >= int64_t(device_cu_count()) * 16 * edge_compute_waves<NB>();   // see launch_edge_fwd
-  if (edge_rb_mode() > 0) big = RBIG == 2 && edge_rb_mode() == 2;
-  if (store) rc = big ? launch_edge_bwd_t<NB, RBIG, true>(a, s) : launch_edge_bwd_t<NB, 1, true>(a, s);
-  else rc = big ? launch_edge_bwd_t<NB, RBIG, false>(a, s) : launch_edge_bwd_t<NB, 1, false>(a, s);
-  return true;
-}
-
 // Compute waves per workgroup of the bf16 edge chains (generic kernels, 16 rows per wave).  Round 4, same-box with the
 // experiment build (profiles/r04_bfcw.sh): 7 waves against 4 -- airfoil batch 8 bf16 222.4 -> 230.1, bf16_nodes 231.5 -> 241.5,
 // surface B=2 bf16 105.2 -> 110.9 / bf16_nodes 111.6 -> 118.0 steps/s (a workgroup streams the weights once per tile: 112 rows
 // per pass instead of 64); a launch that fits one round of 64-row tiles keeps 4 (batch 1: 614 against 597 steps/s with 7).
 template <int NB>
-int bf_edge_waves(int64_t R) {
+int bf_edge_waves(int64_t R, int cus) {
   static const int forced = knob("BSMS_BFEDGE_CW", 0);
   if (forced > 0) return forced;
-  return R > int64_t(device_cu_count()) * resident_per_cu<NB>() * 16 * kComputeWaves ? 7 : kComputeWaves;
+  return R > int64_t(cus) * resident_per_cu<NB>() * 16 * kComputeWaves ? 7 : kComputeWaves;
 }
 
-// Which kernel runs a forward chain, first match wins:
-//   1. the pipelined edge kernel (launch_edge_fwd: NB = 8 / 16, fp32 edge MLP in its production configuration);
-//   2. the feature-split kernel (NB = 8, fp32, at most kFsMaxRows rows);
-//   3. the TIMING variant when the caller asks for stamps (NB = 8 edge chain; experiment builds: also the single-round node chain);
-//   4. the bf16 variant (edge and node MLPs at NB = 8 / 16; bf16 anywhere else is an error);
-//   5. the single-round (LONE) variant, NB >= 8, when the launch fits one workgroup per CU or is the [x, x2] Linear below;
-//   6. the ring kernel.
+template <int NB, int PL = kPL>
+int max_ring() { return (int)std::min<size_t>(6, (size_t(160) * 1024 - Ring<NB, PL>::PRE_FLOATS * sizeof(float)) / (Ring<NB, PL>::CHF * sizeof(float))); }
+template <int NB>
+size_t ring_lds_max() { return Ring<NB>::lds_bytes(max_ring<NB>()); }
+
+// THE launch shape of the edge and ring kernels: `cw` compute waves of `rows_per_wave` rows make a tile; persistent workgroups,
+// `resident` per CU, stride over the tiles (`per_cu`: exactly one per CU, whatever the tile count -- the [x, x2] Linear of plan_fwd).
+// Weight stream: loader waves and ring depth (Ring<NB, PL>; PL = 1: the one-plane chunks of the bf16 precision, whose ring may be
+// deeper than the fp32 one at the same D and is sized as what it is).  A launch that fits ONE round of workgroups (at most one
+// workgroup per CU: the coarse mesh levels, most node-level launches) has the CU's whole LDS and nothing to overlap its chunk
+// latency with: deep ring (up to 6 slots = 5 chunks in flight) fed by two loader waves.  Anything larger keeps 3 slots so that two
+// workgroups share a CU.  Limits: compute + loader waves <= 8; (nr - 2) x pieces per loader <= 63 (vmcnt field); ring + side
+// tables <= 160 KB.
+template <int NB, int PL>
+void launch_shape(ChainLaunch& l, int64_t R, int rows_per_wave, int cw, int nload_default, int resident, bool per_cu, int cus) {
+  static const int deep = knob("BSMS_RING_DEEP", 6), lone_nl = knob("BSMS_LONE_NL", 2), shared = knob("BSMS_RING", 3);
+  l.cw = cw;
+  l.ntiles = (int)ceil_div(R, rows_per_wave * cw);
+  l.nload = std::max(1, std::min(nload_default, 8 - cw));
+  l.nring = std::min(shared, max_ring<NB, PL>());
+  if (per_cu || one_round(l.ntiles, cus)) {
+    l.nload = std::max(l.nload, std::min(lone_nl, 8 - cw));
+    l.nring = std::min(deep, max_ring<NB, PL>());
+  }
+  const int mine = (Ring<NB, PL>::PER + l.nload - 1) / l.nload;
+  while (l.nring > 3 && (l.nring - 2) * mine > 63) --l.nring;
+  l.grid = (unsigned)std::min<int64_t>(l.ntiles, int64_t(cus) * (per_cu ? 1 : resident));
+  l.threads = (cw + l.nload) * 64;
+  l.lds = Ring<NB, PL>::lds_bytes(l.nring);
+  l.lds_max = ring_lds_max<NB>();
+}
+// ... of the generic ring kernels (16 rows per wave)
+template <int NB>
+void ring_shape(ChainLaunch& l, const ChainLaunchKey& k, int cw, bool per_cu, int cus) {
+  l.family = CHAIN_RING;
+  if (k.bf16) launch_shape<NB, 1>(l, k.R, 16, cw, chain_loader_waves(), resident_per_cu<NB>(), per_cu, cus);
+  else launch_shape<NB, kPL>(l, k.R, 16, cw, chain_loader_waves(), resident_per_cu<NB>(), per_cu, cus);
+}
+// ... of the software-pipelined edge kernels (`rb` row blocks of 16 rows per wave)
+template <int NB>
+void edge_shape(ChainLaunch& l, const ChainLaunchKey& k, int rb, int cus) {
+  l.family = CHAIN_EDGE;
+  l.rb = rb;
+  launch_shape<NB, kPL>(l, k.R, 16 * rb, pick_edge_waves<NB>(k.R, rb, cus), edge_loader_waves<NB>(), edge_resident<NB>(rb), false, cus);
+}
+inline void fs_shape(ChainLaunch& l, const ChainLaunchKey& k) {   // the feature-split kernels: one workgroup of 4 waves per 16 rows, static LDS
+  l.family = CHAIN_FS;
+  l.cw = 4;
+  l.ntiles = (int)ceil_div(k.R, 16);
+  l.grid = (unsigned)l.ntiles;
+  l.threads = 256;
+}
+
+// Which variants are built (each is a large unrolled kernel: only the combinations the path uses): plan_* set a flag, and the launch
+// path names the instantiation, under the same condition
+constexpr bool has_edge_kernels(int NB) { return NB == 8 || NB == 16; }
+constexpr int edge_rb_max(int NB) { return NB == 8 ? 2 : 1; }   // two row blocks per wave are built at D = 128 only
+constexpr bool has_lone(int NB) { return NB >= 8; }             // D = 96 has no single-round build: its single-round launches stay on the ring kernel
+constexpr bool has_fs_fwd(int NB, int IN) { return NB == 8 && (IN == IN_ROWS || IN == IN_ROWS2 || IN == IN_SMALL); }
+constexpr bool has_fs_bwd(int NB, int GIN) { return NB == 8 && (GIN == G_ROWS_LN || GIN == G_SMALL); }
+constexpr bool has_timing(int NB, int IN) { return NB == 8 && IN == IN_EDGE; }   // the only production instantiation with stamps
+constexpr bool has_bf16_fwd(int NB, int IN, int OUT) { return (NB == 8 || NB == 16) && (IN == IN_EDGE || IN == IN_ROWS2) && OUT == OUT_LN; }   // edge MLP (BSMS_BF16), node MLP (BSMS_BF16_NODES)
+constexpr bool has_bf16_bwd(int NB, int GIN, int FIRST) { return (NB == 8 || NB == 16) && ((GIN == G_EDGE_LN && FIRST == F_NONE) || (GIN == G_ROWS_LN && FIRST == F_HEADS2)); }
+
+inline ChainLaunchKey key_of(const ChainFwdArgs& a) {   // (after wseq / nseq are built)
+  ChainLaunchKey k{};
+  k.R = a.R; k.nstage = a.nstage; k.nseq = a.nseq; k.bf16 = a.bf16 != 0; k.store_mode = a.store_mode; k.timing = a.timing != nullptr;
+  k.resid = a.resid || a.resid2;
+  int set = a.store_in != nullptr, all = 1;
+  for (int l = 0; l + 1 < std::min(a.nstage, kMaxStages); ++l, ++all) set += a.store[l] != nullptr;
+  k.act_stores = set == 0 ? CHAIN_STORES_NONE : set == all ? CHAIN_STORES_ALL : CHAIN_STORES_MIXED;
+  return k;
+}
+inline ChainLaunchKey key_of(const ChainBwdArgs& a) {
+  ChainLaunchKey k{};
+  k.R = a.R; k.nstage = a.nstage; k.nseq = a.nseq; k.bf16 = a.bf16 != 0; k.store_mode = a.store_mode;
+  const int n = std::max(0, std::min(a.nstage, kMaxStages));   // (the entries bound nstage; the key never reads past the tables)
+  k.glast = a.gstore[n] != nullptr;
+  int set = 0;
+  k.masks = 1;
+  for (int q = 0; q < n; ++q) { set += a.gstore[q] != nullptr; k.masks &= a.mask[q] != nullptr; }
+  k.gstores = set == 0 ? CHAIN_STORES_NONE : set == n ? CHAIN_STORES_ALL : CHAIN_STORES_MIXED;
+  return k;
+}
+
+// Which kernel runs a forward chain, first match wins.
+template <int NB, int IN, int OUT>
+ChainLaunch plan_fwd(const ChainLaunchKey& k, int cus) {
+  ChainLaunch l{};
+  l.what = "chain_fwd";
+  // 1. the pipelined edge kernel: NB = 8 / 16, the fp32 edge MLP in its production configuration only (activation stores all kept
+  //    or none); anything else stays on k_chain_fwd
+  if constexpr (has_edge_kernels(NB) && IN == IN_EDGE && OUT == OUT_LN) {
+    if (!k.bf16 && k.nstage >= 1 && k.store_mode == 1 && !k.resid && edge_rb_mode() != 0 && k.R < (int64_t(1) << 31) &&
+        k.act_stores != CHAIN_STORES_MIXED) {
+      // Measured per level (profiles/r02_edge_levels.md): with several tiles per workgroup two workgroups per CU of one row
+      // block per wave win the forward (the random row gathers of one hide under the other's MFMA stages); a launch that
+      // fits one round of workgroups is faster with two row blocks per wave, and so is the whole backward (its loads are
+      // sequential or local).  Below half a round of 128-row tiles the narrow tile keeps more CUs busy.
+      const int64_t rows1 = 16 * edge_compute_waves<NB>();   // rows of a tile with one row block per wave
+      bool big = edge_rb_max(NB) == 2 && k.R >= cus * rows1 && one_round(ceil_div(k.R, rows1), int64_t(cus) * edge_resident<NB>(1));
+      if (edge_rb_mode() > 0) big = edge_rb_max(NB) == 2 && edge_rb_mode() == 2;
+      l.what = "edge_fwd";
+      edge_shape<NB>(l, k, big ? 2 : 1, cus);
+      l.save = k.act_stores == CHAIN_STORES_ALL;
+      static const int lone = knob("BSMS_EDGE_LONE", 1);
+      l.lone = lone && one_round(l.ntiles, cus) && !k.timing;   // one round of workgroups: the variant that passes the chunk barrier early (stage_rb<LONE>)
+      l.build = l.lone ? "single-round build" : nullptr;
+      return l;
+    }
+  }
+  // 2. the feature-split kernel: NB = 8, fp32, small launches (at most kFsMaxRows rows)
+  if constexpr (has_fs_fwd(NB, IN)) {
+    static const int fs_rows = knob("BSMS_FS_ROWS", kFsMaxRows);
+    if (!k.bf16 && k.R <= fs_rows && k.nseq >= 1 && k.nseq <= kMaxStages + 1) { fs_shape(l, k); return l; }
+  }
+  // ---- the ring kernel and its variants
+  int cw = (IN == IN_EDGE) ? bf_edge_waves<NB>(k.R, cus) : chain_compute_waves<NB>(k.R, cus);
+  // One Linear over [x, x2] added into y (the input gradient through the two edge projections, gmp.hip): three more dependent row
+  // loads per tile than a plain chain and only two packs of MFMAs to hide them under.  The single-round build keeps x2 in registers
+  // (one round trip instead of three) -- so this launch always takes it, one 7-wave workgroup per CU striding over the tiles
+  // (round 6, profiles/r06_rows2.txt; fp32 OUT_PLAIN: it reaches rule 5 below).
+  bool rows2_lone = false;
+  if constexpr (NB == 8 && IN == IN_ROWS2 && OUT == OUT_PLAIN) {
+    static const int on = knob("BSMS_ROWS2_LONE", 1);
+    rows2_lone = on && !k.bf16 && k.nstage == 1 && !one_round(ceil_div(k.R, 16 * cw), cus);
+    if (rows2_lone) cw = 7;
+  }
+  ring_shape<NB>(l, k, cw, rows2_lone, cus);
+  // 3. the TIMING variant when the caller asks for stamps: the NB = 8 edge chain ...
+  if constexpr (has_timing(NB, IN)) {
+    if (k.timing) { l.timing = true; l.build = "timing build"; return l; }
+  }
+#ifdef BSMS_EXPERIMENTS
+  if constexpr (NB == 8 && IN == IN_ROWS2 && OUT == OUT_LN) {   // ... experiment builds: phase stamps of a single-round node chain (profiles/lone_timeline.py)
+    if (k.timing && one_round(l.ntiles, cus)) { l.timing = l.lone = true; l.build = "timing build"; return l; }
+  }
+#endif
+  // 4. the bf16 variant: edge MLP (BSMS_BF16) and node MLP (BSMS_BF16_NODES) at NB = 8 / 16; bf16 anywhere else is an error
+  if (k.bf16) {
+    if constexpr (has_bf16_fwd(NB, IN, OUT)) { l.bf16 = true; l.build = "bf16 build"; }
+    else l.family = CHAIN_UNBUILT;   // the launch path and the query refuse it (chain_refuse)
+    return l;
+  }
+  // 5. the single-round (LONE) variant, NB >= 8, when the launch fits one workgroup per CU (a single wave per SIMD: the variant that
+  //    prefetches its fragments, mfma_stage) or is the [x, x2] Linear above
+  if constexpr (has_lone(NB)) {
+    if (one_round(l.ntiles, cus) || rows2_lone) { l.lone = true; l.build = "single-round build"; return l; }
+  }
+  return l;   // 6. the ring kernel
+}
+
+// Which kernel runs a backward chain, first match wins.
+template <int NB, int GIN, int FIRST>
+ChainLaunch plan_bwd(const ChainLaunchKey& k, int cus) {
+  ChainLaunch l{};
+  l.what = "chain_bwd";
+  // 1. the feature-split kernel: NB = 8, fp32, small launches (at most kFsMaxRowsBwd rows)
+  if constexpr (has_fs_bwd(NB, GIN)) {
+    static const int fs_rows = knob("BSMS_FS_ROWS_BWD", kFsMaxRowsBwd);
+    if (!k.bf16 && k.R <= fs_rows && k.nseq >= 1) { fs_shape(l, k); return l; }
+  }
+  // 2. the pipelined edge kernel: NB = 8 / 16, the fp32 edge MLP in its production configuration.  The layer gradients
+  //    gstore[0 .. nstage-1]: all kept, or none (a frozen edge MLP: the no-store build; tile, ring and single-round choices are the
+  //    storing launch's).  The last gradient, gstore[nstage], always has a reader.
+  if constexpr (has_edge_kernels(NB) && GIN == G_EDGE_LN && FIRST == F_NONE) {
+    if (!k.bf16 && k.nstage >= 1 && k.store_mode == 1 && edge_rb_mode() != 0 && k.R < (int64_t(1) << 31) && k.glast &&
+        k.gstores != CHAIN_STORES_MIXED && k.masks) {
+      bool big = edge_rb_max(NB) == 2 && k.R >= int64_t(cus) * 16 * edge_compute_waves<NB>();   // see plan_fwd
+      if (edge_rb_mode() > 0) big = edge_rb_max(NB) == 2 && edge_rb_mode() == 2;
+      l.what = "edge_bwd";
+      edge_shape<NB>(l, k, big ? 2 : 1, cus);
+      l.store = k.gstores == CHAIN_STORES_ALL;
+      static const int lone = knob("BSMS_EDGE_LONE", 1);
+      l.lone = lone && one_round(l.ntiles, cus);   // see plan_fwd
+      l.build = l.lone ? (l.store ? "single-round build" : "single-round no-store build") : (l.store ? nullptr : "no-store build");
+      return l;
+    }
+  }
+  // ---- the ring kernel and its variants
+  ring_shape<NB>(l, k, (GIN == G_EDGE_LN) ? bf_edge_waves<NB>(k.R, cus) : chain_compute_waves<NB>(k.R, cus), false, cus);
+  // 3. the bf16 variant: edge MLP; node MLP of BSMS_BF16_NODES; NB = 8 / 16; bf16 anywhere else is an error
+  if (k.bf16) {
+    if constexpr (has_bf16_bwd(NB, GIN, FIRST)) { l.bf16 = true; l.build = GIN == G_EDGE_LN ? "bf16 build" : "bf16 node build"; }
+    else l.family = CHAIN_UNBUILT;
+    return l;
+  }
+  // 4. the single-round (LONE) variant, NB >= 8, when the launch fits one workgroup per CU (see plan_fwd)
+  if constexpr (has_lone(NB)) {
+    if (one_round(l.ntiles, cus)) { l.lone = true; l.build = "single-round build"; return l; }
+  }
+  return l;   // 5. the ring kernel
+}
+
+inline int chain_refuse(const ChainLaunch& l) {
+  BSMS_FAIL(BSMS_E_UNSUPPORTED, "%s: bf16 precision is built for the edge and node MLPs at D = 128 / 256 only", l.what);
+}
+
+// From the record to the instantiation
+#define BSMS_RUN(...) return launch_dyn_lds<__VA_ARGS__>(l.what, l.build, l.grid, l.threads, l.lds, l.lds_max, a, s)
+template <int NB, int RB>
+int run_edge(const ChainLaunch& l, const ChainFwdArgs& a, hipStream_t s) {
+  if (l.save && l.lone) BSMS_RUN(k_edge_fwd<NB, RB, 1, true>);
+  if (l.save) BSMS_RUN(k_edge_fwd<NB, RB, 1>);
+  if (l.lone) BSMS_RUN(k_edge_fwd<NB, RB, 0, true>);
+  BSMS_RUN(k_edge_fwd<NB, RB, 0>);
+}
+template <int NB, int RB>
+int run_edge(const ChainLaunch& l, const ChainBwdArgs& a, hipStream_t s) {
+  if (l.store && l.lone) BSMS_RUN(k_edge_bwd<NB, RB, true, true>);
+  if (l.store) BSMS_RUN(k_edge_bwd<NB, RB, false, true>);
+  if (l.lone) BSMS_RUN(k_edge_bwd<NB, RB, true, false>);
+  BSMS_RUN(k_edge_bwd<NB, RB, false, false>);
+}
 template <int NB, int IN, int OUT>
 int launch_fwd_t(const ChainFwdArgs& a0, hipStream_t s) {
   ChainFwdArgs a = a0;
@@ -223,67 +345,71 @@ int launch_fwd_t(const ChainFwdArgs& a0, hipStream_t s) {
     a.wseq[a.nseq++] = a.wp[l];
     if (IN == IN_ROWS2 && l == 0) a.wseq[a.nseq++] = a.wp0b;
   }
-  if constexpr ((NB == 8 || NB == 16) && IN == IN_EDGE && OUT == OUT_LN) {
-    int rc = BSMS_OK;
-    if (launch_edge_fwd<NB>(a, s, rc)) return rc;
-  }
-  if constexpr (NB == 8 && (IN == IN_ROWS || IN == IN_ROWS2 || IN == IN_SMALL)) {   // small launches
-    static const int fs_rows = knob("BSMS_FS_ROWS", kFsMaxRows);
-    if (!a.bf16 && a.R <= fs_rows && a.nseq >= 1 && a.nseq <= kMaxStages + 1) {
-      hipLaunchKernelGGL((k_fs_fwd<IN, OUT>), dim3((unsigned)ceil_div(a.R, 16)), dim3(256), 0, s, a);
+  const ChainLaunch l = plan_fwd<NB, IN, OUT>(key_of(a), device_cu_count());
+  a.ntiles = l.ntiles; a.nload = l.nload; a.nring = l.nring;
+  if (l.family == CHAIN_UNBUILT) return chain_refuse(l);
+  if constexpr (has_fs_fwd(NB, IN)) {
+    if (l.family == CHAIN_FS) {
+      hipLaunchKernelGGL((k_fs_fwd<IN, OUT>), dim3(l.grid), dim3(l.threads), 0, s, a);
       BSMS_LAUNCH_CHECK();
       return BSMS_OK;
     }
   }
-  // ---- launch shape of the ring kernel and its variants
-  int cw = (IN == IN_EDGE) ? bf_edge_waves<NB>(a.R) : chain_compute_waves<NB>(a.R);
-  a.ntiles = (int)ceil_div(a.R, 16 * cw);
-  // One Linear over [x, x2] added into y (the input gradient through the two edge projections, gmp.hip): three more dependent row
-  // loads per tile than a plain chain and only two packs of MFMAs to hide them under.  The single-round build keeps x2 in registers
-  // (one round trip instead of three) -- so this launch always takes it, one 7-wave workgroup per CU striding over the tiles
-  // (round 6, profiles/r06_rows2.txt).
-  bool rows2_lone = false;
-  if constexpr (NB == 8 && IN == IN_ROWS2 && OUT == OUT_PLAIN) {
-    static const int on = knob("BSMS_ROWS2_LONE", 1);
-    if (on && !a.bf16 && a.nstage == 1 && a.ntiles > device_cu_count()) {
-      rows2_lone = true;
-      cw = 7;
-      a.ntiles = (int)ceil_div(a.R, 16 * cw);
-    }
+  if constexpr (has_edge_kernels(NB) && IN == IN_EDGE && OUT == OUT_LN) {
+    if (l.family == CHAIN_EDGE) return l.rb == 2 ? run_edge<NB, edge_rb_max(NB)>(l, a, s) : run_edge<NB, 1>(l, a, s);
   }
-  const int64_t stream_tiles = rows2_lone ? std::min<int64_t>(a.ntiles, device_cu_count()) : a.ntiles;   // ring depth / loaders of a one-workgroup-per-CU launch
-  if (a.bf16) pick_stream<NB, 1>(stream_tiles, cw, chain_loader_waves(), a.nload, a.nring);
-  else pick_stream<NB>(stream_tiles, cw, chain_loader_waves(), a.nload, a.nring);
-  const unsigned grid = rows2_lone ? (unsigned)stream_tiles : persistent_grid<NB>(a.ntiles);   // (rows2_lone: fp32 OUT_PLAIN, always the LONE variant)
-  const unsigned threads = (cw + a.nload) * 64;
-  // the bf16 precision's chunks are one plane: its ring may be deeper than the fp32 one at the same D, size it as what it is
-  const size_t lds = a.bf16 ? Ring<NB, 1>::lds_bytes(a.nring) : Ring<NB>::lds_bytes(a.nring), lds_max = ring_lds_max<NB>();
-  // ---- the variant
-  if constexpr (NB == 8 && IN == IN_EDGE) {   // the only production instantiation with stamps
-    if (a.timing) return launch_dyn_lds<k_chain_fwd<NB, IN, OUT, true>>("chain_fwd", "timing build", grid, threads, lds, lds_max, a, s);
+  if constexpr (has_timing(NB, IN)) {
+    if (l.timing) BSMS_RUN(k_chain_fwd<NB, IN, OUT, true>);
   }
 #ifdef BSMS_EXPERIMENTS
-  if constexpr (NB == 8 && IN == IN_ROWS2 && OUT == OUT_LN) {   // phase stamps of a single-round node chain (profiles/lone_timeline.py)
-    if (a.timing && a.ntiles <= device_cu_count())
-      return launch_dyn_lds<k_chain_fwd<NB, IN, OUT, true, false, true>>("chain_fwd", "timing build", grid, threads, lds, lds_max, a, s);
+  if constexpr (NB == 8 && IN == IN_ROWS2 && OUT == OUT_LN) {
+    if (l.timing) BSMS_RUN(k_chain_fwd<NB, IN, OUT, true, false, true>);
   }
 #endif
-  if constexpr ((NB == 8 || NB == 16) && (IN == IN_EDGE || IN == IN_ROWS2) && OUT == OUT_LN) {   // the bf16 arithmetic: edge MLP (BSMS_BF16), node MLP (BSMS_BF16_NODES)
-    if (a.bf16) return launch_dyn_lds<k_chain_fwd<NB, IN, OUT, false, true>>("chain_fwd", "bf16 build", grid, threads, lds, lds_max, a, s);
+  if constexpr (has_bf16_fwd(NB, IN, OUT)) {
+    if (l.bf16) BSMS_RUN(k_chain_fwd<NB, IN, OUT, false, true>);
   }
-  BSMS_REQUIRE(!a.bf16, BSMS_E_UNSUPPORTED, "chain_fwd: bf16 precision is built for the edge and node MLPs at D = 128 / 256 only");
-  // (D = 96 has no single-round build: its single-round launches stay on the ring kernel, which saves a set of instantiations)
-  if constexpr (NB >= 8) {   // one round of workgroups = a single wave per SIMD: the variant that prefetches its fragments (mfma_stage)
-    if (a.ntiles <= device_cu_count() || rows2_lone)
-      return launch_dyn_lds<k_chain_fwd<NB, IN, OUT, false, false, true>>("chain_fwd", "single-round build", grid, threads, lds, lds_max, a, s);
+  if constexpr (has_lone(NB)) {
+    if (l.lone) BSMS_RUN(k_chain_fwd<NB, IN, OUT, false, false, true>);
   }
-  return launch_dyn_lds<k_chain_fwd<NB, IN, OUT>>("chain_fwd", nullptr, grid, threads, lds, lds_max, a, s);
+  BSMS_RUN(k_chain_fwd<NB, IN, OUT>);
 }
-// Only the combinations the path uses are instantiated (each is a large unrolled kernel).
-template <int NB>
-int launch_fwd_n(int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s) {
+
+template <int NB, int GIN, int FIRST>
+int launch_bwd_t(const ChainBwdArgs& a0, hipStream_t s) {
+  ChainBwdArgs a = a0;
+  a.nseq = 0;
+  for (int k = 0; k < a.nstage; ++k) a.wseq[a.nseq++] = a.wpt[k];
+  if (FIRST != F_NONE) a.wseq[a.nseq++] = a.wh0;
+  if (FIRST == F_HEADS2) a.wseq[a.nseq++] = a.wh1;
+  const ChainLaunch l = plan_bwd<NB, GIN, FIRST>(key_of(a), device_cu_count());
+  a.ntiles = l.ntiles; a.nload = l.nload; a.nring = l.nring;
+  if (l.family == CHAIN_UNBUILT) return chain_refuse(l);
+  if constexpr (has_fs_bwd(NB, GIN)) {
+    if (l.family == CHAIN_FS) {
+      hipLaunchKernelGGL((k_fs_bwd<GIN, FIRST>), dim3(l.grid), dim3(l.threads), 0, s, a);
+      BSMS_LAUNCH_CHECK();
+      return BSMS_OK;
+    }
+  }
+  if constexpr (has_edge_kernels(NB) && GIN == G_EDGE_LN && FIRST == F_NONE) {
+    if (l.family == CHAIN_EDGE) return l.rb == 2 ? run_edge<NB, edge_rb_max(NB)>(l, a, s) : run_edge<NB, 1>(l, a, s);
+  }
+  if constexpr (has_bf16_bwd(NB, GIN, FIRST)) {
+    if (l.bf16) BSMS_RUN(k_chain_bwd<NB, GIN, FIRST, true>);
+  }
+  if constexpr (has_lone(NB)) {
+    if (l.lone) BSMS_RUN(k_chain_bwd<NB, GIN, FIRST, false, true>);
+  }
+  BSMS_RUN(k_chain_bwd<NB, GIN, FIRST>);
+}
+#undef BSMS_RUN
+
+// The mode pairs that are built: f(in, out) / f(gin, first) gets them as integral constants
+template <class F>
+int with_fwd_modes(int in_mode, int out_mode, F&& f) {
 #define BSMS_FWD(I, O) \
-  if (in_mode == I && out_mode == O) return launch_fwd_t<NB, I, O>(a, s)
+  if (in_mode == I && out_mode == O) return f(std::integral_constant<int, I>{}, std::integral_constant<int, O>{})
   BSMS_FWD(IN_ROWS, OUT_PLAIN);   // x W^T
   BSMS_FWD(IN_ROWS, OUT_PLAIN2);  // the two node pre-projections of the edge MLP
   BSMS_FWD(IN_ROWS2, OUT_PLAIN);  // its input gradient
@@ -295,56 +421,10 @@ int launch_fwd_n(int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s
 #undef BSMS_FWD
   BSMS_FAIL(BSMS_E_UNSUPPORTED, "chain_fwd: in/out mode (%d,%d) not built", in_mode, out_mode);
 }
-
-// Which kernel runs a backward chain, first match wins:
-//   1. the feature-split kernel (NB = 8, fp32, at most kFsMaxRowsBwd rows);
-//   2. the pipelined edge kernel (launch_edge_bwd: NB = 8 / 16, fp32 edge MLP in its production configuration; its no-store
-//      build when the layer gradients gstore[0 .. nstage-1] are all null);
-//   3. the bf16 variant (edge MLP; node MLP of BSMS_BF16_NODES; NB = 8 / 16; bf16 anywhere else is an error);
-//   4. the single-round (LONE) variant, NB >= 8, when the launch fits one workgroup per CU;
-//   5. the ring kernel.
-template <int NB, int GIN, int FIRST>
-int launch_bwd_t(const ChainBwdArgs& a0, hipStream_t s) {
-  ChainBwdArgs a = a0;
-  a.nseq = 0;
-  for (int k = 0; k < a.nstage; ++k) a.wseq[a.nseq++] = a.wpt[k];
-  if (FIRST != F_NONE) a.wseq[a.nseq++] = a.wh0;
-  if (FIRST == F_HEADS2) a.wseq[a.nseq++] = a.wh1;
-  if constexpr (NB == 8 && (GIN == G_ROWS_LN || GIN == G_SMALL)) {   // small launches (see launch_fwd_t)
-    static const int fs_rows = knob("BSMS_FS_ROWS_BWD", kFsMaxRowsBwd);
-    if (!a.bf16 && a.R <= fs_rows && a.nseq >= 1) {
-      hipLaunchKernelGGL((k_fs_bwd<GIN, FIRST>), dim3((unsigned)ceil_div(a.R, 16)), dim3(256), 0, s, a);
-      BSMS_LAUNCH_CHECK();
-      return BSMS_OK;
-    }
-  }
-  if constexpr ((NB == 8 || NB == 16) && GIN == G_EDGE_LN && FIRST == F_NONE) {
-    int rc = BSMS_OK;
-    if (launch_edge_bwd<NB>(a, s, rc)) return rc;
-  }
-  // ---- launch shape of the ring kernel and its variants
-  const int cw = (GIN == G_EDGE_LN) ? bf_edge_waves<NB>(a.R) : chain_compute_waves<NB>(a.R);
-  a.ntiles = (int)ceil_div(a.R, 16 * cw);
-  if (a.bf16) pick_stream<NB, 1>(a.ntiles, cw, chain_loader_waves(), a.nload, a.nring);
-  else pick_stream<NB>(a.ntiles, cw, chain_loader_waves(), a.nload, a.nring);
-  const unsigned grid = persistent_grid<NB>(a.ntiles), threads = (cw + a.nload) * 64;
-  const size_t lds = a.bf16 ? Ring<NB, 1>::lds_bytes(a.nring) : Ring<NB>::lds_bytes(a.nring), lds_max = ring_lds_max<NB>();   // see launch_fwd_t
-  // ---- the variant
-  constexpr bool kEdgeMlp = GIN == G_EDGE_LN && FIRST == F_NONE, kNodeMlp = GIN == G_ROWS_LN && FIRST == F_HEADS2;
-  if constexpr ((NB == 8 || NB == 16) && (kEdgeMlp || kNodeMlp)) {
-    if (a.bf16) return launch_dyn_lds<k_chain_bwd<NB, GIN, FIRST, true>>("chain_bwd", kEdgeMlp ? "bf16 build" : "bf16 node build", grid, threads, lds, lds_max, a, s);
-  }
-  BSMS_REQUIRE(!a.bf16, BSMS_E_UNSUPPORTED, "chain_bwd: bf16 precision is built for the edge and node MLPs at D = 128 / 256 only");
-  if constexpr (NB >= 8) {   // see launch_fwd_t
-    if (a.ntiles <= device_cu_count())
-      return launch_dyn_lds<k_chain_bwd<NB, GIN, FIRST, false, true>>("chain_bwd", "single-round build", grid, threads, lds, lds_max, a, s);
-  }
-  return launch_dyn_lds<k_chain_bwd<NB, GIN, FIRST>>("chain_bwd", nullptr, grid, threads, lds, lds_max, a, s);
-}
-template <int NB>
-int launch_bwd_n(int gin, int first, const ChainBwdArgs& a, hipStream_t s) {
-#define BSMS_BWD(G, F) \
-  if (gin == G && first == F) return launch_bwd_t<NB, G, F>(a, s)
+template <class F>
+int with_bwd_modes(int gin, int first, F&& f) {
+#define BSMS_BWD(G, F_) \
+  if (gin == G && first == F_) return f(std::integral_constant<int, G>{}, std::integral_constant<int, F_>{})
   BSMS_BWD(G_ROWS_LN, F_HEADS2);  // node MLP
   BSMS_BWD(G_EDGE_LN, F_NONE);    // edge MLP
   BSMS_BWD(G_ROWS_LN, F_NONE);    // encoder
@@ -358,7 +438,17 @@ int launch_bwd_n(int gin, int first, const ChainBwdArgs& a, hipStream_t s) {
 
 namespace bsms {
 template <int NB>
-int launch_chain_fwd_nb(int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s) { return launch_fwd_n<NB>(in_mode, out_mode, a, s); }
+int launch_chain_fwd_nb(int in_mode, int out_mode, const ChainFwdArgs& a, hipStream_t s) {
+  return with_fwd_modes(in_mode, out_mode, [&](auto i, auto o) { return launch_fwd_t<NB, decltype(i)::value, decltype(o)::value>(a, s); });
+}
 template <int NB>
-int launch_chain_bwd_nb(int gin, int first, const ChainBwdArgs& a, hipStream_t s) { return launch_bwd_n<NB>(gin, first, a, s); }
+int launch_chain_bwd_nb(int gin, int first, const ChainBwdArgs& a, hipStream_t s) {
+  return with_bwd_modes(gin, first, [&](auto g, auto f) { return launch_bwd_t<NB, decltype(g)::value, decltype(f)::value>(a, s); });
+}
+template <int NB>
+int chain_launch_query_nb(int backward, int mode_a, int mode_b, const ChainLaunchKey& k, int cus, ChainLaunch* out) {
+  const int rc = backward ? with_bwd_modes(mode_a, mode_b, [&](auto g, auto f) { *out = plan_bwd<NB, decltype(g)::value, decltype(f)::value>(k, cus); return int(BSMS_OK); })
+                          : with_fwd_modes(mode_a, mode_b, [&](auto i, auto o) { *out = plan_fwd<NB, decltype(i)::value, decltype(o)::value>(k, cus); return int(BSMS_OK); });
+  return rc || out->family != CHAIN_UNBUILT ? rc : chain_refuse(*out);
+}
 }  // namespace bsms

@@ -40,6 +40,12 @@ def test_bf16_forward_matches_the_documented_arithmetic(eng, graphs):
         mine = mine.cuda()
         mine.precision = "bf16"
         h, pos = torch.randn(2, 300, D), graphs.t("del300/pos").float().unsqueeze(0).repeat(2, 1, 1)
+        if D == 256:                                    # ... as chosen on this device: one round, six slots where the two-plane ring has four
+            from test_chain_launch_host import launch_info
+            cus = torch.cuda.get_device_properties(0).multi_processor_count
+            for l in range(depth + 1):
+                i, f = launch_info(D, 0, "edge bf16", 2 * es[l].shape[1]), launch_info(D, 0, "edge plain stores", 2 * es[l].shape[1])
+                assert (i.text, i.nring, f.text, f.nring) == ("chain_fwd bf16", 6, "chain_fwd lone", 4) and i.ntiles <= cus and i.nload == 2, l
         with torch.no_grad():
             want32 = ref(h, ids[:depth], es[: depth + 1], pos)
             want = emulate(ref)(h, ids[:depth], es[: depth + 1], pos)

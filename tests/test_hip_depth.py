@@ -213,8 +213,12 @@ def test_feature_split_kernels_equal_the_ring_kernels_mlp_at_hidden_7(eng):
     """test_hip_parity.py::test_feature_split_kernels_equal_the_ring_kernels, its MLP half, at hidden = 7: 3000 rows (feature-split forward
     and backward) against the first 3000 of 30000 (ring kernels).  Forward and input gradient bit for bit; the forwards being equal, so are
     the ReLU masks, and the weight gradients differ by their split-K summation order alone: 2e-6 as there."""
+    from test_chain_launch_host import launch_info
     torch.manual_seed(21)
     D, H, small, big = 128, 7, 3000, 30000
+    for kind in ("encoder", "mlp", "decoder"):       # the launches named above are the ones chosen on this device
+        assert [launch_info(D, 0, kind + " training", r, H).text for r in (small, big)] == ["fs_fwd", "chain_fwd"], kind
+        assert [launch_info(D, 1, kind, r, H).text for r in (small, big)] == ["fs_bwd", "chain_bwd"], kind
     for in_dim, out_dim, ln in ((3, D, True), (D, D, True), (D, 3, False)):
         mlp = eng.MLP(in_dim, D, out_dim, H, ln).cuda()
         x = torch.randn(big, in_dim, device="cuda")
@@ -238,15 +242,26 @@ def test_feature_split_kernels_equal_the_ring_kernels_mlp_at_hidden_7(eng):
 
 
 def test_gmp_launch_regimes_are_bit_equal_at_hidden_7(eng):
-    """A GMP block of n = 3000, e = 18000 at hidden = 7: one sample (18000 edge rows: the single-round edge kernels; 3000 node rows:
+    """A GMP block of n = 3000, e = 18000 at hidden = 7: one sample (18000 edge rows: the edge kernels with one row block per wave, 282
+    tiles of 4 waves -- one round of resident workgroups, but more than one per CU, so not the single-round build; 3000 node rows:
     feature-split both ways) against the same sample repeated 2, 3 and 6 times -- 36000 and 54000 edge rows (two row blocks per wave, the
     bottom and the top of that window; 6000 node rows: feature-split forward, single-round ring backward; 9000: single-round ring both
     ways), 108000 (several rounds; 18000 node rows: the ring kernel).  Forward and input gradient of every copy of the sample bit for bit
     across all four; weight gradients / B within 2e-6 (equal forwards, equal ReLU masks: split-K order only; measured worst 1.2e-6, so
     the three-way fallback against fp64 was not needed)."""
+    from test_chain_launch_host import launch_info
     from test_hip_parity import random_graph as parity_graph
     torch.manual_seed(21)
     D, H, n, e = 128, 7, 3000, 18000
+    # the launches named above are the ones chosen on this device: B -> (edge forward, edge backward, node forward, node backward)
+    named = {1: ("edge_fwd rb1 save", "edge_bwd rb1 store", "fs_fwd", "fs_bwd"),
+             2: ("edge_fwd rb2 save lone", "edge_bwd rb2 store lone", "fs_fwd", "chain_bwd lone"),
+             3: ("edge_fwd rb2 save lone", "edge_bwd rb2 store lone", "chain_fwd lone", "chain_bwd lone"),
+             6: ("edge_fwd rb1 save", "edge_bwd rb2 store", "chain_fwd", "chain_bwd")}
+    for B, want in named.items():
+        got = (launch_info(D, 0, "edge training", B * e, H), launch_info(D, 1, "edge", B * e, H),
+               launch_info(D, 0, "node training", B * n, H), launch_info(D, 1, "node", B * n, H))
+        assert tuple(i.text for i in got) == want, (B, [i.text for i in got])
     g = dev(parity_graph(n, e, 5))
     gmp = eng.GMP(D, H, 2).cuda()
     x6, pos6 = torch.randn(6, n, D, device="cuda"), torch.rand(6, n, 2, device="cuda")

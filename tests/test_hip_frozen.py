@@ -22,7 +22,7 @@ from test_hip_unroll import _cuda, later_targets, make_oracle
 
 pytestmark = pytest.mark.gpu
 OK, E_INVALID_ARG, E_UNSUPPORTED = 0, -1, -3
-FS_ROWS = 3072                    # chain.h: kFsMaxRowsBwd, the feature-split backward's row limit (D = 128)
+FS_ROWS = 3072                    # chain_kernels.h: kFsMaxRowsBwd, the feature-split backward's row limit (D = 128)
 
 
 @pytest.fixture(scope="module")
@@ -110,7 +110,7 @@ def check_freeze_patterns(c):
 
 
 # name -> (D, nodes, B): the kernel family every backward chain of the block takes, and the row counts that select it
-# (chain_launch.h: launch_bwd_t / launch_edge_bwd; a 7-wave edge tile has 112 rows, 224 with two row blocks per wave)
+# (chain_launch.h: plan_bwd; a 7-wave edge tile has 112 rows, 224 with two row blocks per wave)
 GMP_SHAPES = {
     # node MLP: k_fs_bwd (B N <= 3072); edge MLP: k_edge_bwd<8,1,LONE>, one round of 112-row tiles (B E <= 3072 here)
     "fs_d128": (128, 200, 2),
@@ -119,7 +119,8 @@ GMP_SHAPES = {
     "ring_d96": (96, 700, 2),
     # D = 160: node and edge MLP on k_chain_bwd's single-round (LONE) build (tiles <= CUs)
     "lone_ring_d160": (160, 700, 2),
-    # edge MLP: k_edge_bwd<8,1,LONE> (3072 < B E < CUs x 112); node MLP: k_chain_bwd LONE (B N > 3072)
+    # edge MLP: k_edge_bwd<8,1> (3072 < B E < CUs x 112: pick_edge_waves takes 4 waves, more tiles than CUs, so not the LONE build
+    # that fs_d128 reaches -- the shape keeps its historical name); node MLP: k_chain_bwd LONE (B N > 3072)
     "edge_lone_d128": (128, 1100, 3),
     # edge MLP: k_edge_bwd<8,2>, more than one round of 224-row tiles (B E > CUs x 224)
     "edge_rb2_multi_d128": (128, 2600, 4),
@@ -150,6 +151,17 @@ def test_gmp_block_freeze_patterns(eng, name):
         assert re > cus * 112
     else:
         assert re > cus * 224
+    # the kernels GMP_SHAPES names are the ones chosen on this device: (edge MLP, its no-store launch when frozen, node MLP)
+    from test_chain_launch_host import launch_info
+    named = {"fs_d128": ("edge_bwd rb1 store lone", "edge_bwd rb1 lone", "fs_bwd"),
+             "ring_d64": ("chain_bwd",) * 3, "ring_d96": ("chain_bwd",) * 3, "lone_ring_d160": ("chain_bwd lone",) * 3,
+             "edge_lone_d128": ("edge_bwd rb1 store", "edge_bwd rb1", "chain_bwd lone"),
+             "edge_rb2_multi_d128": ("edge_bwd rb2 store", "edge_bwd rb2", None),
+             "edge_rb2_lone_d128": ("edge_bwd rb2 store lone", "edge_bwd rb2 lone", None),
+             "edge_d256": ("edge_bwd rb1 store lone", "edge_bwd rb1 lone", None),
+             "edge_multi_d256": ("edge_bwd rb1 store", "edge_bwd rb1", None)}[name]
+    got = tuple(launch_info(D, 1, tag, rows).text for tag, rows in (("edge", re), ("edge frozen", re), ("node", rn)))
+    assert all(w is None or w == g for w, g in zip(named, got)), (name, got)
     check_freeze_patterns(c)
 
 

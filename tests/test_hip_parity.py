@@ -606,8 +606,14 @@ def test_feature_split_kernels_equal_the_ring_kernels(eng):
     launch must equal a small launch of the same rows BIT FOR BIT: forward (training and inference), input gradient; the
     weight gradients of the two paths agree to round-off.  MLP shapes of the path (encoder, decoder, D -> D with
     LayerNorm) and a whole GMP block at batch 1 against the same sample inside a batch of 6."""
+    from test_chain_launch_host import launch_info
     torch.manual_seed(21)
     D, small, big = 128, 3000, 30000      # 3000 rows: feature-split forward (<= 6144) AND backward (<= 3072)
+    for kind in ("encoder", "mlp", "decoder"):       # the launches named above are the ones chosen on this device
+        for tag in (kind + " training", kind + " inference"):
+            assert launch_info(D, 0, tag, small).text == "fs_fwd" and launch_info(D, 0, tag, big).text == "chain_fwd", tag
+        for tag in (kind, kind + " frozen"):
+            assert launch_info(D, 1, tag, small).text == "fs_bwd" and launch_info(D, 1, tag, big).text == "chain_bwd", tag
     for in_dim, out_dim, ln in ((3, D, True), (D, D, True), (D, 3, False)):
         mlp = eng.MLP(in_dim, D, out_dim, 3, ln).cuda()
         x = torch.randn(big, in_dim, device="cuda")
@@ -629,6 +635,11 @@ def test_feature_split_kernels_equal_the_ring_kernels(eng):
             assert rel_err(q.grad, gs[k]) < 2e-6, (in_dim, out_dim, k)            # weight gradients: other split-K slabs, round-off only
     # a GMP block: node-level chains of B = 1 (3000 rows) are feature-split, of B = 6 (18000 rows) ring kernels
     n, e = 3000, 18000
+    for rows, fwd, bwd in ((n, "fs_fwd", "fs_bwd"), (6 * n, "chain_fwd", "chain_bwd")):
+        assert [launch_info(D, 0, t, rows).text for t in ("projections", "node training", "node inference")] == [fwd] * 3
+        assert launch_info(D, 1, "node", rows).text == bwd
+        # (beyond the feature-split limit the [x, x2] Linear always takes the ring kernel's single-round build)
+        assert launch_info(D, 0, "input gradient of the projections", rows).text == (fwd if rows == n else "chain_fwd lone")
     g = random_graph(n, e, 5)
     gmp = eng.GMP(D, 3, 2).cuda()
     x6, pos6 = torch.randn(6, n, D, device="cuda"), torch.rand(6, n, 2, device="cuda")
@@ -735,8 +746,8 @@ def test_gmp_magnitude_range_zero_input_and_many_rows(eng):
 @pytest.mark.parametrize("n,e,B", [(40, 90, 1), (300, 2300, 3), (900, 7000, 5), (2000, 16000, 4), (1200, 9000, 7)])
 def test_gmp_launch_shapes(eng, n, e, B):
     """The chain launchers pick tile shapes by row count: 16-row blocks per wave (one or two), 4-7 compute waves, one or
-    several rounds of workgroups, the single-round kernel variants, 3-6 ring slots, 1-2 loader waves (chain.hip:
-    pick_stream, launch_edge_fwd / _bwd, chain_compute_waves).  Edge-row counts from 90 to 64 000 at D = 128 walk through
+    several rounds of workgroups, the single-round kernel variants, 3-6 ring slots, 1-2 loader waves (chain_launch.h:
+    plan_fwd / plan_bwd, launch_shape, pick_edge_waves, chain_compute_waves).  Edge-row counts from 90 to 64 000 at D = 128 walk through
     all of them (35 000 rows: two row blocks per wave in the forward; 63 000 / 64 000: several rounds).
     Forward: three-way against fp64 (<= 3x the fp32 oracle's distance).  Gradients: at these sizes a few of the 10^6-10^7
     ReLU inputs lie within 1e-8 of zero (checked: 1.1e-8 for the second case), so any two fp32 arithmetics disagree on a
