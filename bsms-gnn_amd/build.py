@@ -21,7 +21,7 @@ SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "chain_d32.hip", "chain_d64.hi
            "chain_d256.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "mlp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip", "batch.hip", "errsum.hip", "edgediff.hip"]
 # chain.hip: prepack + dispatch on the latent width; chain_d<D>.hip: the chain kernels of one width (templates in chain_kernels.h /
 # chain_edge.h, launchers in chain_launch.h), one translation unit each so that they compile in parallel
-HEADERS = ["common.h", "chain.h", "host_orch.h", "gmp_block.h", "chain_dev.h", "chain_kernels.h", "chain_edge.h", "chain_launch.h", "objective_row.h", "edge_gather.h", "piece_sum.h", os.path.join("..", "..", "include", "bsms_hip.h"), os.path.join("..", "..", "include", "bsms_hip_ext.h"),
+HEADERS = ["common.h", "chain.h", "host_orch.h", "gmp_block.h", "chain_dev.h", "chain_kernels.h", "chain_edge.h", "chain_launch.h", "edge_res.h", "objective_row.h", "edge_gather.h", "piece_sum.h", os.path.join("..", "..", "include", "bsms_hip.h"), os.path.join("..", "..", "include", "bsms_hip_ext.h"),
            os.path.join("..", "..", "include", "bsms_hip_stats.h"), os.path.join("..", "..", "include", "bsms_hip_sample.h"), os.path.join("..", "..", "include", "bsms_hip_query.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 if os.environ.get("BSMS_EXPERIMENTS") == "1":   # profiling / A-B builds only: BSMS_DEBUG_FLAGS, in-kernel time stamps, launch-shape knobs

@@ -14,18 +14,10 @@
 // Arithmetic and its order are those of k_chain_fwd<8, IN_EDGE, OUT_LN, BF> (chain.hip): same operand roundings, the K
 // chunks of every accumulator in the order 0..3 starting from the bias, the same LayerNorm expression -- the results are
 // bit-identical (profiles/r05_efwd_ab.txt).
-#include "chain.h"
-
-using namespace bsms;
+#pragma clang fp contract(off)   // chain_dev.h: every fused multiply-add of the arithmetic is an explicit fmaf()
+#include "edge_res.h"
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 constexpr int D = 128, NB = 8;
 constexpr int W_BYTES = D * D * 2;            // one weight matrix as bf16 fragments: [c][t][lane] 16 bytes (= the pack bodies)
@@ -38,51 +30,6 @@ constexpr int LDS_BYTES = OFF_SIDE + (4 * D + 3 * D) * 4;
 constexpr int WAVES = EFWD_WAVES;
 static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 
-__device__ __forceinline__ unsigned pk_bf16(float lo, float hi) {   // v_cvt_pk_bf16_f32: round to nearest even
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// LDS-DMA: 64 lanes x 16 bytes from per-lane global addresses to LDS [lds_dst, +1 KB) in lane order (chain.hip: glds16)
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ float group_sum(float s) {  // sum over the 4 lane groups holding one row
-  s += __shfl_xor(s, 16, 64);
-  s += __shfl_xor(s, 32, 64);
-  return s;
-}
-__device__ __forceinline__ void load_rows(f32x4 (&v)[NB], const float* row, int g) {
-#pragma unroll
-  for (int t = 0; t < NB; ++t) v[t] = *reinterpret_cast<const f32x4*>(row + 16 * t + 4 * g);
-}
-__device__ __forceinline__ void axpy_features(f32x4 (&v)[NB], const float* vec, float scale, int g) {
-#pragma unroll
-  for (int t = 0; t < NB; ++t) {
-    const float4 w = *reinterpret_cast<const float4*>(vec + 16 * t + 4 * g);
-    v[t][0] = fmaf(scale, w.x, v[t][0]);
-    v[t][1] = fmaf(scale, w.y, v[t][1]);
-    v[t][2] = fmaf(scale, w.z, v[t][2]);
-    v[t][3] = fmaf(scale, w.w, v[t][3]);
-  }
-}
-// relu, then the bf16 rounding that makes the B operand of the next Linear (chain.hip: relu_into + round_block)
-__device__ __forceinline__ void relu_pack(u32x4 (&bb)[4], const f32x4 (&acc)[NB]) {
-  // round first, then clamp the PAIR with one packed signed-integer max: a bf16 with its sign bit set (a negative value or
-  // -0) is a negative int16, so max(., 0) is +0, and a non-negative one is left alone -- the bits of pk_bf16(max(x, 0), max(y, 0))
-  // for every non-NaN input (rounding keeps the sign), in two operations per pair instead of three
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const unsigned w = pk_bf16(acc[2 * c + (v >> 1)][2 * (v & 1)], acc[2 * c + (v >> 1)][2 * (v & 1) + 1]);
-      asm("v_pk_max_i16 %0, %1, 0" : "=v"(bb[c][v]) : "v"(w));
-    }
-}
 // acc = bias + W x: every accumulator takes its K chunks in the order 0..3 (chain.hip: mfma_stage_bf)
 __device__ __forceinline__ void stage(f32x4 (&acc)[NB], const u32x4 (&bb)[4], const char* W, const float* bias, int lane) {
   const int g = lane >> 4;
@@ -96,17 +43,6 @@ __device__ __forceinline__ void stage(f32x4 (&acc)[NB], const u32x4 (&bb)[4], co
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int t = 0; t < NB; ++t) acc[t] = mma(frag[(c * NB + t) * 64], bb[c], acc[t]);
-}
-
-// row of the [B, E] edge tensor -> (batch, edge) without a 64-bit division (chain.hip: edge_ref; rows < 2^31, launcher)
-struct EdgeRef { int b, q; };
-__device__ __forceinline__ EdgeRef edge_ref(unsigned row, unsigned E, float rcpE) {
-  int b = int(float(row) * rcpE);
-  int q = int(row) - b * int(E);
-  if (q < 0) { q += int(E); --b; }
-  if (q >= int(E)) { q -= int(E); ++b; }
-  if (unsigned(q) >= E) { b = int(row / E); q = int(row - unsigned(b) * E); }   // estimate off by more than one (tiny E, huge B): exact
-  return EdgeRef{b, q};
 }
 
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVES / 4, WAVES / 4))) void k_edge_fwd_res(EdgeFwdResArgs a) {
@@ -139,7 +75,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
   struct Where { int b, i, j; };
   auto locate = [&](int tile) {
     const int64_t row64 = int64_t(tile) * 16 + (lane & 15);
-    const EdgeRef e = edge_ref(unsigned(row64 < a.R ? row64 : 0), unsigned(a.E), rcpE);   // a lane past the end reads row 0
+    const EdgeRef e = edge_ref_exact(unsigned(row64 < a.R ? row64 : 0), unsigned(a.E), rcpE);   // a lane past the end reads row 0
     return Where{e.b, a.src[e.q], a.dst[e.q]};
   };
   int tile = int(blockIdx.x) * WAVES + wave;
@@ -197,10 +133,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     relu_pack(bb, acc);
     stage(acc, bb, lds + 2 * W_BYTES, bias + 2 * D, lane);
     // ---- LayerNorm(elementwise_affine=False), eps 1e-5  (ops/basic.py:18; chain.hip: k_chain_fwd OUT_LN)
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < NB; ++t) s += (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]);
-    const float mean = group_sum(s) * (1.f / D);
+    const float mean = row_sum(acc) * (1.f / D);
     float ss = 0.f;
 #pragma unroll
     for (int t = 0; t < NB; ++t)
@@ -210,7 +143,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         ss = fmaf(acc[t][r], acc[t][r], ss);
       }
     ss = group_sum(ss);
-    const float rstd = 1.f / sqrtf(ss * (1.f / D) + 1e-5f);
+    const float rstd = 1.f / sqrtf(fmaf(ss, 1.f / D, 1e-5f));   // ss / D + eps: the product with 2^-7 is exact, fused or not
     if (!live) continue;
     u32x2* yp = reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(a.y) + row * D + 4 * g);
 #pragma unroll
