@@ -188,6 +188,20 @@ QUERY_SIGNATURES = {
 }
 
 
+# the fifth companion library libbsms_hip_diffop.so: name -> (restype, argtypes); one entry per declaration in include/bsms_hip_diffop.h
+DIFFOP_LIB_PATH = os.path.join(_HERE, "libbsms_hip_diffop.so")
+DIFFOP_SIGNATURES = {
+    "bsms_cell_gradient": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_i64, C.c_float, c_void_p, c_void_p]),
+    "bsms_node_gradient": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_i64,
+                                   C.c_float, c_i64, c_void_p, c_void_p]),
+    "bsms_cell_gradient_work_bytes": (c_size_t, [c_i64, c_i64]),
+    "bsms_cell_gradient_sums": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64,
+                                        c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
+    "bsms_cell_gradient_bwd": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64,
+                                       c_i64, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
+}
+
+
 class MomentTraj(C.Structure):
     """bsms_moment_traj (include/bsms_hip_stats.h)."""
     _fields_ = [("state", c_void_p), ("type", c_void_p), ("n", c_i64), ("frame0", c_i64), ("frames", c_i64), ("type_stride", c_i64)]
@@ -319,6 +333,26 @@ def query():
             fn.restype, fn.argtypes = res, args
         _query = handle
     return _query
+
+
+_diffop = None
+
+
+def diffop():
+    """Load the differential-operator library (once), behind libbsms_hip.so, which it links against.  Raises if it has not been built.
+    Only the mesh gradients (diffop.MeshGradient) call this: a process that never differentiates a field never loads the library."""
+    global _diffop
+    if _diffop is None:
+        lib()
+        if not os.path.exists(DIFFOP_LIB_PATH):
+            raise BsmsError(f"{DIFFOP_LIB_PATH} not found: build it with `python bsms-gnn_amd/build.py` (or __graft_entry__.build()); "
+                            "there is no CPU/PyTorch fallback")
+        handle = C.CDLL(DIFFOP_LIB_PATH)
+        for name, (res, args) in DIFFOP_SIGNATURES.items():
+            fn = getattr(handle, name)  # AttributeError if the symbol is missing
+            fn.restype, fn.argtypes = res, args
+        _diffop = handle
+    return _diffop
 
 
 def check(rc, what):

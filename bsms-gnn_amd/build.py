@@ -11,18 +11,20 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libbsms_hip.so")
 # the companion libraries (name, sources): entries behind libbsms_hip.so's closed surface, each linked against it
-# (include/bsms_hip_ext.h, include/bsms_hip_stats.h, include/bsms_hip_sample.h, include/bsms_hip_query.h)
+# (include/bsms_hip_ext.h, include/bsms_hip_stats.h, include/bsms_hip_sample.h, include/bsms_hip_query.h, include/bsms_hip_diffop.h)
 COMPANIONS = [("libbsms_hip_ext.so", [os.path.join("ext", "edge_objective.hip")]),
               ("libbsms_hip_stats.so", [os.path.join("stats", "moments.hip")]),
               ("libbsms_hip_sample.so", [os.path.join("sample", "raster.hip")]),
-              ("libbsms_hip_query.so", [os.path.join("query", "chain_query.hip")])]
+              ("libbsms_hip_query.so", [os.path.join("query", "chain_query.hip")]),
+              ("libbsms_hip_diffop.so", [os.path.join("diffop", "cellgrad.hip")])]
 COMPANION_SOURCES = [src for _, srcs in COMPANIONS for src in srcs]
 SOURCES = ["plan.hip", "rowsum.hip", "chain.hip", "chain_d32.hip", "chain_d64.hip", "chain_d96.hip", "chain_d128.hip", "chain_d160.hip", "chain_d192.hip", "chain_d224.hip",
            "chain_d256.hip", "efuse.hip", "efwd.hip", "wgrad.hip", "gmp.hip", "mlp.hip", "bsgmp.hip", "optim.hip", "hierarchy.hip", "sim.hip", "posgrad.hip", "batch.hip", "errsum.hip", "edgediff.hip"]
 # chain.hip: prepack + dispatch on the latent width; chain_d<D>.hip: the chain kernels of one width (templates in chain_kernels.h /
 # chain_edge.h, launchers in chain_launch.h), one translation unit each so that they compile in parallel
 HEADERS = ["common.h", "chain.h", "host_orch.h", "gmp_block.h", "chain_dev.h", "chain_kernels.h", "chain_edge.h", "chain_launch.h", "edge_res.h", "objective_row.h", "edge_gather.h", "piece_sum.h", os.path.join("..", "..", "include", "bsms_hip.h"), os.path.join("..", "..", "include", "bsms_hip_ext.h"),
-           os.path.join("..", "..", "include", "bsms_hip_stats.h"), os.path.join("..", "..", "include", "bsms_hip_sample.h"), os.path.join("..", "..", "include", "bsms_hip_query.h")]
+           os.path.join("..", "..", "include", "bsms_hip_stats.h"), os.path.join("..", "..", "include", "bsms_hip_sample.h"), os.path.join("..", "..", "include", "bsms_hip_query.h"),
+           os.path.join("..", "..", "include", "bsms_hip_diffop.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 if os.environ.get("BSMS_EXPERIMENTS") == "1":   # profiling / A-B builds only: BSMS_DEBUG_FLAGS, in-kernel time stamps, launch-shape knobs
     FLAGS.append("-DBSMS_EXPERIMENTS")

@@ -521,6 +521,15 @@ class TrajectoryBank:
         from .sample import MeshSampler
         return MeshSampler(tr.pos if tr.pos_static else tr.pos[0], tr.cells, self.cfg.mesh_type, device=self.device)
 
+    def gradient_ops(self, i):
+        """A `diffop.MeshGradient` on the mesh of trajectory `i`, the twin of `sampler`: its stored `cells` and its
+        frame-0 positions.  Built on every call (the incidence is built on the host: keep it)."""
+        tr = self._trajs[int(i)]
+        if tr.cells is None:
+            raise ValueError('TrajectoryBank.gradient_ops: needs the trajectory\'s "cells" (cfg.field_names)')
+        from .diffop import MeshGradient
+        return MeshGradient(tr.pos if tr.pos_static else tr.pos[0], tr.cells, self.cfg.mesh_type, device=self.device)
+
     def batch(self, picks, train=True, draw=None, return_noise=False, horizon=None, transforms=None, return_transforms=False,
               return_weights=False):
         """The device batch of `picks`, a list of (trajectory, frame).  `train`: inject the training noise; `draw` selects the

@@ -49,6 +49,36 @@ def edge_error_mean_std(sums, relative=True):
     return E.mean(0), E.std(0, unbiased=False)
 
 
+def _cell_columns(sums, who):
+    sums = sums.to(torch.float64)
+    if sums.dim() != 2 or (sums.shape[1] - 5) % 2 or sums.shape[1] < 7:
+        raise ValueError(f"{who}: sums [B, 1+2C+4] expected, got {tuple(sums.shape)}")
+    return sums, (sums.shape[1] - 5) // 2
+
+
+def cell_error_mean_std(sums, relative=True):
+    """(mean [C], std [C]) in fp64 over the samples of `sums` [B, 1+2C+4] = [A | GE | GT | DP DT WE WT] (`MeshGradient.sums`,
+    DESIGN.md 4.30):
+
+        E[b,c] = sqrt(GE / A)          divided by sqrt(GT / A) when `relative`
+
+    the RMS P1 gradient of the error field over the mesh (its H1 seminorm over the square root of the area), against that of the
+    target field.  The standard deviation is the population one, as `edge_error_mean_std` takes it."""
+    sums, C = _cell_columns(sums, "cell_error_mean_std")
+    A, GE, GT = sums[:, :1], sums[:, 1:1 + C], sums[:, 1 + C:1 + 2 * C]
+    E = torch.sqrt(GE / A)
+    if relative:
+        E = E / torch.sqrt(GT / A)
+    return E.mean(0), E.std(0, unbiased=False)
+
+
+def divergence_rms(sums):
+    """(pred [B], target [B]) in fp64 from `sums` [B, 1+2C+4] (`MeshGradient.sums` with a velocity pair): the RMS divergence of the
+    predicted and of the target velocity field over the mesh, sqrt(DP / A) and sqrt(DT / A)."""
+    sums, C = _cell_columns(sums, "divergence_rms")
+    return torch.sqrt(sums[:, 1 + 2 * C] / sums[:, 0]), torch.sqrt(sums[:, 2 + 2 * C] / sums[:, 0])
+
+
 def equivariance_error(model, batch, transforms, groups, rows_per_sample=None):
     """How far `model` is from commuting with a change of frame, per channel, as a relative RMS difference (fp64 [C]):
 

@@ -533,6 +533,22 @@ class Trainer:
             out = torch.stack(edge_error_mean_std(sums, relative)).float().cpu().numpy()
         return out[0], out[1]
 
+    def get_cell_error(self, data, ops, relative=True, velocity=None, ema=False):
+        """(mean, std) per channel as float32 NumPy arrays [C] of the CELL-GRADIENT error: per sample the RMS P1
+        gradient of the error field over `ops`' mesh (diffop.MeshGradient), E = sqrt(GE / A), divided by that of the target field,
+        sqrt(GT / A), when `relative`.  Mean and population standard deviation run over the batch's samples; a variable-mesh batch is
+        ONE sample of sum N rows, as in `get_error`, so `ops` then spans the union.  `velocity` is handed to `ops.sums` (it does not
+        change these figures).  One bsms_cell_gradient_sums launch pair; 2C numbers are copied back."""
+        from .eval import cell_error_mean_std
+        data = self.move_to_device(data)
+        with torch.no_grad():
+            pred = self.get_pred(data, ema)
+            tar, mask = self.get_label_mask(data)
+            rows, C = pred.shape[-2], pred.shape[-1]
+            sums = ops.sums(pred.reshape(-1, rows, C), tar.reshape(-1, rows, C), mask.reshape(-1, rows), velocity)
+            out = torch.stack(cell_error_mean_std(sums, relative)).float().cpu().numpy()
+        return out[0], out[1]
+
     def iter(self, data, node_weights=None):
         """One training iteration (trainer.py:134-156): statistics only during warm-up, otherwise
         fwd + loss + bwd (+ gradient all-reduce) + clip + AdamW + LR schedule.  With model_cfg.unroll_steps = K > 1 `data` is
