@@ -149,6 +149,38 @@ constexpr size_t kIdxAlign = 64;   // int32 elements (256 bytes) between the arr
 #define BSMS_HD
 #endif
 BSMS_HD inline size_t idx_pad(size_t n) { return (n + kIdxAlign - 1) / kIdxAlign * kIdxAlign; }
+// THE layout of a plan's two index blocks (the arrays: see bsms_plan below), the one statement every reader and writer takes its
+// offsets from -- the host builds and the plan's own pointers (plan.hip), the union's allocations and k_plan_concat (rowsum.hip).
+// Word offsets of the arrays, each array padded to kIdxAlign, in block order; `words`: the block's length.
+struct MainLayout { size_t rowptr, t_rowptr, src, dst, perm, t_dst, t_eid, t_pos, words; };
+struct PoolLayout { size_t ids, inv, k_rowptr, k_src, k_eid, p_rowptr, p_src, p_eid, k_w, p_w, words; };
+BSMS_HD inline MainLayout main_layout(size_t N, size_t E) {
+  const size_t nN = idx_pad(N + 1), nE = idx_pad(E);
+  MainLayout l;
+  l.rowptr = 0; l.t_rowptr = l.rowptr + nN; l.src = l.t_rowptr + nN; l.dst = l.src + nE; l.perm = l.dst + nE;
+  l.t_dst = l.perm + nE; l.t_eid = l.t_dst + nE; l.t_pos = l.t_eid + nE; l.words = l.t_pos + nE;
+  return l;
+}
+BSMS_HD inline PoolLayout pool_layout(size_t N, size_t Nk, size_t Ek, size_t Ep) {
+  const size_t nEk = idx_pad(Ek), nEp = idx_pad(Ep);
+  PoolLayout l;
+  l.ids = 0; l.inv = l.ids + idx_pad(Nk); l.k_rowptr = l.inv + idx_pad(N); l.k_src = l.k_rowptr + idx_pad(Nk + 1); l.k_eid = l.k_src + nEk;
+  l.p_rowptr = l.k_eid + nEk; l.p_src = l.p_rowptr + idx_pad(N + 1); l.p_eid = l.p_src + nEp; l.k_w = l.p_eid + nEp; l.p_w = l.k_w + nEk;
+  l.words = l.p_w + nEp;
+  return l;
+}
+// the arrays of a block at `base` (I: int32_t or const int32_t; k_w / p_w are float words, given as words here)
+template <class I> struct MainPtrs { I *rowptr, *t_rowptr, *src, *dst, *perm, *t_dst, *t_eid, *t_pos; };
+template <class I> struct PoolPtrs { I *ids, *inv, *k_rowptr, *k_src, *k_eid, *p_rowptr, *p_src, *p_eid, *k_w, *p_w; };
+template <class I> BSMS_HD inline MainPtrs<I> main_ptrs(I* base, size_t N, size_t E) {
+  const MainLayout l = main_layout(N, E);
+  return {base + l.rowptr, base + l.t_rowptr, base + l.src, base + l.dst, base + l.perm, base + l.t_dst, base + l.t_eid, base + l.t_pos};
+}
+template <class I> BSMS_HD inline PoolPtrs<I> pool_ptrs(I* base, size_t N, size_t Nk, size_t Ek, size_t Ep) {
+  const PoolLayout l = pool_layout(N, Nk, Ek, Ep);
+  return {base + l.ids, base + l.inv, base + l.k_rowptr, base + l.k_src, base + l.k_eid, base + l.p_rowptr, base + l.p_src, base + l.p_eid,
+          base + l.k_w, base + l.p_w};
+}
 constexpr int kCatParts = 16;
 struct CatPart {
   const int32_t *blk, *pool;               // the part's two device blocks (pool: null when no part has one)

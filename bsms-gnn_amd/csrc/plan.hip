@@ -266,6 +266,18 @@ int wait_written(const bsms_plan* p) {
   if (p->written) BSMS_HIP_CHECK(hipEventSynchronize(p->written));
   return BSMS_OK;
 }
+
+// The pointers of a plan into its two blocks, from its sizes (common.h: the layout): the one place that sets them
+void point_into_blocks(bsms_plan* p) {
+  const MainPtrs<int32_t> m = main_ptrs(p->block, p->N, p->E);
+  p->rowptr = m.rowptr; p->t_rowptr = m.t_rowptr; p->src = m.src; p->dst = m.dst; p->perm = m.perm;
+  p->t_dst = m.t_dst; p->t_eid = m.t_eid; p->t_pos = m.t_pos;
+  if (!p->pool_block) return;
+  const PoolPtrs<int32_t> k = pool_ptrs(p->pool_block, p->N, p->Nk, p->Ek, p->Ep);
+  p->ids = k.ids; p->inv = k.inv; p->k_rowptr = k.k_rowptr; p->k_src = k.k_src; p->k_eid = k.k_eid;
+  p->p_rowptr = k.p_rowptr; p->p_src = k.p_src; p->p_eid = k.p_eid;
+  p->k_w = reinterpret_cast<float*>(k.k_w); p->p_w = reinterpret_cast<float*>(k.p_w);
+}
 }  // namespace
 
 extern "C" int bsms_plan_create(const int64_t* coo, int64_t E, int64_t N, bsms_plan_t** out) {
@@ -283,44 +295,42 @@ extern "C" int bsms_plan_create(const int64_t* coo, int64_t E, int64_t N, bsms_p
                  (long long)gi[e], (long long)gj[e], (long long)N);
 
   // all eight index arrays in one host block (layout = the device block)
-  const size_t nN = idx_pad(size_t(N) + 1), nE = idx_pad(size_t(E));
-  std::vector<int32_t> blk(2 * nN + 6 * nE, 0);
-  int32_t *rowptr = blk.data(), *t_rowptr = rowptr + nN, *src = t_rowptr + nN, *dst = src + nE, *perm = dst + nE,
-          *t_dst = perm + nE, *t_eid = t_dst + nE, *t_pos = t_eid + nE;
+  std::vector<int32_t> blk(main_layout(N, E).words, 0);
+  const MainPtrs<int32_t> h = main_ptrs(blk.data(), N, E);
   for (int64_t e = 0; e < E; ++e) {
-    rowptr[gj[e] + 1]++;
-    t_rowptr[gi[e] + 1]++;
+    h.rowptr[gj[e] + 1]++;
+    h.t_rowptr[gi[e] + 1]++;
   }
   int64_t min_deg = E > 0 || N > 0 ? INT64_MAX : 0, max_src = -1, max_in = 0, max_out = 0;
   for (int64_t n = 0; n < N; ++n) {
-    min_deg = std::min<int64_t>(min_deg, t_rowptr[n + 1]);
-    max_out = std::max<int64_t>(max_out, t_rowptr[n + 1]);
-    max_in = std::max<int64_t>(max_in, rowptr[n + 1]);
+    min_deg = std::min<int64_t>(min_deg, h.t_rowptr[n + 1]);
+    max_out = std::max<int64_t>(max_out, h.t_rowptr[n + 1]);
+    max_in = std::max<int64_t>(max_in, h.rowptr[n + 1]);
   }
   if (N == 0) min_deg = 0;
   for (int64_t e = 0; e < E; ++e) max_src = std::max(max_src, gi[e]);
-  std::partial_sum(rowptr, rowptr + N + 1, rowptr);
-  std::partial_sum(t_rowptr, t_rowptr + N + 1, t_rowptr);
+  std::partial_sum(h.rowptr, h.rowptr + N + 1, h.rowptr);
+  std::partial_sum(h.t_rowptr, h.t_rowptr + N + 1, h.t_rowptr);
 
   // stable counting sorts: slots of equal key keep the caller's edge order
   std::vector<int32_t> slot_of_edge(E);
   {
-    std::vector<int32_t> cur(rowptr, rowptr + N);
+    std::vector<int32_t> cur(h.rowptr, h.rowptr + N);
     for (int64_t e = 0; e < E; ++e) {
       int32_t q = cur[gj[e]]++;
-      src[q] = (int32_t)gi[e];
-      dst[q] = (int32_t)gj[e];
-      perm[q] = (int32_t)e;
+      h.src[q] = (int32_t)gi[e];
+      h.dst[q] = (int32_t)gj[e];
+      h.perm[q] = (int32_t)e;
       slot_of_edge[e] = q;
     }
   }
   {
-    std::vector<int32_t> cur(t_rowptr, t_rowptr + N);
+    std::vector<int32_t> cur(h.t_rowptr, h.t_rowptr + N);
     for (int64_t e = 0; e < E; ++e) {
       int32_t t = cur[gi[e]]++;
-      t_dst[t] = (int32_t)gj[e];
-      t_eid[t] = (int32_t)e;
-      t_pos[t] = slot_of_edge[e];
+      h.t_dst[t] = (int32_t)gj[e];
+      h.t_eid[t] = (int32_t)e;
+      h.t_pos[t] = slot_of_edge[e];
     }
   }
 
@@ -339,14 +349,7 @@ extern "C" int bsms_plan_create(const int64_t* coo, int64_t E, int64_t N, bsms_p
   }
   p->host.swap(blk);   // kept until the first bsms_plan_set_pool, which builds the compact transition lists from it
   p->host_words = p->host.size();
-  p->rowptr = p->block;
-  p->t_rowptr = p->rowptr + nN;
-  p->src = p->t_rowptr + nN;
-  p->dst = p->src + nE;
-  p->perm = p->dst + nE;
-  p->t_dst = p->perm + nE;
-  p->t_eid = p->t_dst + nE;
-  p->t_pos = p->t_eid + nE;
+  point_into_blocks(p);
   *out = p;
   return BSMS_OK;
 }
@@ -356,18 +359,14 @@ extern "C" int bsms_plan_set_pool(bsms_plan_t* p, const int64_t* ids, int64_t Nk
   BSMS_REQUIRE(Nk >= 0 && Nk <= p->N && (ids != nullptr || Nk == 0), BSMS_E_SHAPE,
                "plan_set_pool: bad Nk=%lld for N=%lld", (long long)Nk, (long long)p->N);
   { int rc_ = wait_written(p); if (rc_) return rc_; }   // a union still being written: its blocks are read back / recycled below
-  const size_t nK = idx_pad(size_t(Nk)), nNinv = idx_pad(size_t(p->N));
-  std::vector<int32_t> head(nK + nNinv, -1);
-  int32_t *h_ids = head.data(), *h_inv = h_ids + nK;
+  std::vector<int32_t> inv(size_t(p->N), -1);   // fine -> coarse; the sizes Ek / Ep of the pool block follow from it
   for (int64_t k = 0; k < Nk; ++k) {
     BSMS_REQUIRE(ids[k] >= 0 && ids[k] < p->N, BSMS_E_INVALID_ARG, "plan_set_pool: id %lld out of range",
                  (long long)ids[k]);
-    BSMS_REQUIRE(h_inv[ids[k]] < 0, BSMS_E_INVALID_ARG, "plan_set_pool: duplicate id %lld", (long long)ids[k]);
-    h_ids[k] = (int32_t)ids[k];
-    h_inv[ids[k]] = (int32_t)k;
+    BSMS_REQUIRE(inv[ids[k]] < 0, BSMS_E_INVALID_ARG, "plan_set_pool: duplicate id %lld", (long long)ids[k]);
+    inv[ids[k]] = (int32_t)k;
   }
   // compact lists of the two pooled transitions (common.h), from the host copy of the CSR
-  const size_t nN = idx_pad(size_t(p->N) + 1), nE = idx_pad(size_t(p->E));
   // the host copy of the CSR: kept since bsms_plan_create for the FIRST pooling only (a cache of 1024 plans used to carry ~2 MB each for
   // good: ADVICE round 4); a plan that is pooled again reads its index block back from the device
   std::vector<int32_t> readback;
@@ -381,31 +380,30 @@ extern "C" int bsms_plan_set_pool(bsms_plan_t* p, const int64_t* ids, int64_t Nk
     if (dev != p->device) (void)hipSetDevice(dev);
     BSMS_REQUIRE(e == hipSuccess, BSMS_E_HIP, "plan_set_pool: reading the index block back: %s", hipGetErrorString(e));
   }
-  const int32_t* const hostp = p->host.empty() ? readback.data() : p->host.data();
-  const int32_t *rowptr = hostp, *t_rowptr = rowptr + nN, *src = t_rowptr + nN, *perm = src + 2 * nE,
-                *t_dst = perm + nE, *t_eid = t_dst + nE;
+  const MainPtrs<const int32_t> c = main_ptrs<const int32_t>(p->host.empty() ? readback.data() : p->host.data(), p->N, p->E);
   int64_t Ek = 0, Ep = 0;
-  for (int64_t k = 0; k < Nk; ++k) Ek += rowptr[h_ids[k] + 1] - rowptr[h_ids[k]];
-  for (int64_t t = 0; t < p->E; ++t) Ep += h_inv[t_dst[t]] >= 0;
-  const size_t nK1 = idx_pad(size_t(Nk) + 1), nEk = idx_pad(size_t(Ek)), nEp = idx_pad(size_t(Ep));
-  std::vector<int32_t> blk(nK + nNinv + nK1 + 2 * nEk + nN + 2 * nEp + nEk + nEp, 0);
-  std::copy(head.begin(), head.end(), blk.begin());
-  int32_t *k_rowptr = blk.data() + nK + nNinv, *k_src = k_rowptr + nK1, *k_eid = k_src + nEk, *p_rowptr = k_eid + nEk,
-          *p_src = p_rowptr + nN, *p_eid = p_src + nEp;
+  for (int64_t k = 0; k < Nk; ++k) Ek += c.rowptr[ids[k] + 1] - c.rowptr[ids[k]];
+  for (int64_t t = 0; t < p->E; ++t) Ep += inv[c.t_dst[t]] >= 0;
+  std::vector<int32_t> blk(pool_layout(p->N, Nk, Ek, Ep).words, 0);
+  const PoolPtrs<int32_t> h = pool_ptrs(blk.data(), p->N, Nk, Ek, Ep);
+  std::fill_n(h.ids, idx_pad(Nk), -1);   // the padding behind ids and inv is -1 (common.h)
+  std::fill_n(h.inv, idx_pad(p->N), -1);
+  std::copy(inv.begin(), inv.end(), h.inv);
   {
     int64_t q = 0;
     for (int64_t k = 0; k < Nk; ++k) {
-      k_rowptr[k] = (int32_t)q;
-      for (int32_t s = rowptr[h_ids[k]]; s < rowptr[h_ids[k] + 1]; ++s, ++q) { k_src[q] = src[s]; k_eid[q] = perm[s]; }
+      h.ids[k] = (int32_t)ids[k];
+      h.k_rowptr[k] = (int32_t)q;
+      for (int32_t s = c.rowptr[ids[k]]; s < c.rowptr[ids[k] + 1]; ++s, ++q) { h.k_src[q] = c.src[s]; h.k_eid[q] = c.perm[s]; }
     }
-    k_rowptr[Nk] = (int32_t)q;
+    h.k_rowptr[Nk] = (int32_t)q;
     int64_t u = 0;
     for (int64_t i = 0; i < p->N; ++i) {
-      p_rowptr[i] = (int32_t)u;
-      for (int32_t t = t_rowptr[i]; t < t_rowptr[i + 1]; ++t)
-        if (h_inv[t_dst[t]] >= 0) { p_src[u] = h_inv[t_dst[t]]; p_eid[u] = t_eid[t]; ++u; }
+      h.p_rowptr[i] = (int32_t)u;
+      for (int32_t t = c.t_rowptr[i]; t < c.t_rowptr[i + 1]; ++t)
+        if (inv[c.t_dst[t]] >= 0) { h.p_src[u] = inv[c.t_dst[t]]; h.p_eid[u] = c.t_eid[t]; ++u; }
     }
-    p_rowptr[p->N] = (int32_t)u;
+    h.p_rowptr[p->N] = (int32_t)u;
   }
   release_block(p->pool_block, p->pool_cap, p->device);
   p->pool_block = p->ids = p->inv = nullptr;
@@ -415,50 +413,15 @@ extern "C" int bsms_plan_set_pool(bsms_plan_t* p, const int64_t* ids, int64_t Nk
   p->Nk = p->Ek = p->Ep = 0;
   int rc;
   if ((rc = upload_block(&p->pool_block, &p->pool_cap, blk))) return rc;
-  p->ids = p->pool_block;
-  p->inv = p->pool_block + nK;
-  p->k_rowptr = p->inv + nNinv;
-  p->k_src = p->k_rowptr + nK1;
-  p->k_eid = p->k_src + nEk;
-  p->p_rowptr = p->k_eid + nEk;
-  p->p_src = p->p_rowptr + nN;
-  p->p_eid = p->p_src + nEp;
-  p->k_w = reinterpret_cast<float*>(p->p_eid + nEp);
-  p->p_w = p->k_w + nEk;
   p->Nk = Nk;
   p->Ek = Ek;
   p->Ep = Ep;
+  point_into_blocks(p);
   if (!p->host.empty()) {   // the compact lists are built: the host copy has served its purpose
     p->host_words = p->host.size();
     std::vector<int32_t>().swap(p->host);
   }
   return BSMS_OK;
-}
-
-// The pointers of a plan into its two blocks, from its sizes (the layouts bsms_plan_create / bsms_plan_set_pool write)
-static void point_into_blocks(bsms_plan* p) {
-  const size_t nN = idx_pad(size_t(p->N) + 1), nE = idx_pad(size_t(p->E));
-  p->rowptr = p->block;
-  p->t_rowptr = p->rowptr + nN;
-  p->src = p->t_rowptr + nN;
-  p->dst = p->src + nE;
-  p->perm = p->dst + nE;
-  p->t_dst = p->perm + nE;
-  p->t_eid = p->t_dst + nE;
-  p->t_pos = p->t_eid + nE;
-  if (!p->pool_block) return;
-  const size_t nK = idx_pad(size_t(p->Nk)), nNinv = idx_pad(size_t(p->N)), nK1 = idx_pad(size_t(p->Nk) + 1),
-               nEk = idx_pad(size_t(p->Ek)), nEp = idx_pad(size_t(p->Ep));
-  p->ids = p->pool_block;
-  p->inv = p->pool_block + nK;
-  p->k_rowptr = p->inv + nNinv;
-  p->k_src = p->k_rowptr + nK1;
-  p->k_eid = p->k_src + nEk;
-  p->p_rowptr = p->k_eid + nEk;
-  p->p_src = p->p_rowptr + nN;
-  p->p_eid = p->p_src + nEp;
-  p->k_w = reinterpret_cast<float*>(p->p_eid + nEp);
-  p->p_w = p->k_w + nEk;
 }
 
 // Block-diagonal union of plans ON THE DEVICE (round 6).  The stable dst-sorted CSR, its transpose and
@@ -492,15 +455,13 @@ extern "C" int bsms_plan_concat(const bsms_plan_t* const* parts, int nparts, con
   p->device = dev;
   p->N = N; p->E = E;
   p->min_out_degree = (N > 0 || E > 0) ? INT64_MAX : 0;
-  const size_t nN = idx_pad(size_t(N) + 1), nE = idx_pad(size_t(E));
-  const size_t words = 2 * nN + 6 * nE;
+  const size_t words = main_layout(N, E).words;
   int rc = alloc_block(&p->block, std::max<size_t>(words, 1) * sizeof(int32_t), &p->block_cap);
   if (rc) { bsms_plan_destroy(p); return rc; }
   p->host_words = words;
   if (pooled) {
     p->Nk = Nk; p->Ek = Ek; p->Ep = Ep;
-    const size_t nK = idx_pad(size_t(Nk)), nNinv = idx_pad(size_t(N)), nK1 = idx_pad(size_t(Nk) + 1), nEk = idx_pad(size_t(Ek)), nEp = idx_pad(size_t(Ep));
-    const size_t pw = nK + nNinv + nK1 + 2 * nEk + nN + 2 * nEp + nEk + nEp;
+    const size_t pw = pool_layout(N, Nk, Ek, Ep).words;
     if ((rc = alloc_block(&p->pool_block, std::max<size_t>(pw, 1) * sizeof(int32_t), &p->pool_cap))) { bsms_plan_destroy(p); return rc; }
   }
   point_into_blocks(p);

@@ -8,6 +8,8 @@
 // reproducible, and bit-identical to a sequential scatter_add_ (utils/basic.py:324-343).
 // Lanes run along the feature axis (16-byte loads, a 128-float row = one 512-byte burst of a
 // half-wave), so every HBM access is a fully used, coalesced row segment.
+#include <type_traits>
+
 #include "chain.h"
 
 // hipcc defaults to -ffp-contract=fast, which would fuse the rounded product x*ew with the running sum
@@ -357,44 +359,39 @@ __global__ __launch_bounds__(256) void k_rowsum_scalar(RowSumArgs a) {
 
 // below this many lanes the chip is under-filled (256 CUs x 2048 threads) and latency, not bandwidth, is the limit
 constexpr int64_t kDeepBelowThreads = 400 * 1024;
+// the DEEP (latency) regime of a launch: `workers` output rows of `lanes` lanes each
+inline bool deep_regime(int64_t workers, int64_t lanes) { return workers * lanes < kDeepBelowThreads; }
 
-template <bool WEIGHTED, bool MAPPED>
-int launch_rowsum_wm(const RowSumArgs& a, hipStream_t s) {
-  const int64_t workers = int64_t(a.B) * a.n_out;
-  if (workers == 0 || a.D == 0) return BSMS_OK;
-  if (a.D % 4 != 0) {
-    const int64_t total = workers * a.D;
-    hipLaunchKernelGGL((k_rowsum_scalar<WEIGHTED, MAPPED>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, a);
-  } else {
-    const int d4 = a.D / 4;
-#define BSMS_RS(L)                                                                                              \
-  do {                                                                                                          \
-    if (workers * L < kDeepBelowThreads)                                                                        \
-      hipLaunchKernelGGL((k_rowsum_v4<L, WEIGHTED, MAPPED, true>), dim3((unsigned)ceil_div(workers * L, 256)),  \
-                         dim3(256), 0, s, a);                                                                   \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_rowsum_v4<L, WEIGHTED, MAPPED, false>), dim3((unsigned)ceil_div(workers * L, 256)), \
-                         dim3(256), 0, s, a);                                                                   \
-  } while (0)
-    if (d4 <= 1) BSMS_RS(1);
-    else if (d4 <= 2) BSMS_RS(2);
-    else if (d4 <= 4) BSMS_RS(4);
-    else if (d4 <= 8) BSMS_RS(8);
-    else if (d4 <= 16) BSMS_RS(16);
-    else if (d4 <= 32) BSMS_RS(32);
-    else BSMS_RS(64);
-#undef BSMS_RS
-  }
+// Runtime value -> template argument, the one way in this file: f(std::integral_constant) for the value of Vs... that `v` equals
+// (none: f is not called -- every caller has checked or rounded `v` before), or for a bool.  A caller lists exactly the values its
+// kernel is built for, so nothing else is instantiated.
+template <int... Vs, class F>
+void pick(int v, F&& f) { (void)((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...); }
+template <class F>
+void pick(bool v, F&& f) { v ? f(std::true_type()) : f(std::false_type()); }
+
+// one launch of 256-thread workgroups over `threads` threads in x (`ny` in y)
+template <class... P, class... A>
+int launch(void (*kernel)(P...), int64_t threads, unsigned ny, hipStream_t s, const A&... a) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(threads, 256), ny), dim3(256), 0, s, a...);
   BSMS_LAUNCH_CHECK();
   return BSMS_OK;
 }
 
 int launch_rowsum(const RowSumArgs& a, hipStream_t s) {
-  const bool wt = a.w != nullptr, mp = a.xmap != nullptr;
-  if (wt && mp) return launch_rowsum_wm<true, true>(a, s);
-  if (wt) return launch_rowsum_wm<true, false>(a, s);
-  if (mp) return launch_rowsum_wm<false, true>(a, s);
-  return launch_rowsum_wm<false, false>(a, s);
+  const int64_t workers = int64_t(a.B) * a.n_out;
+  if (workers == 0 || a.D == 0) return BSMS_OK;
+  int lanes = 1;   // per row: the power of two >= D / 4, at most 64
+  while (lanes < a.D / 4 && lanes < 64) lanes *= 2;
+  int rc = BSMS_OK;
+  pick(a.w != nullptr, [&](auto wt) { pick(a.xmap != nullptr, [&](auto mp) {
+    constexpr bool W = decltype(wt)::value, M = decltype(mp)::value;
+    if (a.D % 4 != 0) rc = launch(k_rowsum_scalar<W, M>, workers * a.D, 1, s, a);
+    else pick<1, 2, 4, 8, 16, 32, 64>(lanes, [&](auto L) { pick(deep_regime(workers, lanes), [&](auto deep) {
+      rc = launch(k_rowsum_v4<decltype(L)::value, W, M, decltype(deep)::value>, workers * lanes, 1, s, a);
+    }); });
+  }); });
+  return rc;
 }
 
 // out[b, oidx[r], :] = in[b, iidx[r], :]   (either index optional)
@@ -414,6 +411,14 @@ __global__ __launch_bounds__(256) void k_copy_rows(const float* in, float* out, 
   float* dst = out + b * out_bstride + orow * D;
   if (v4) reinterpret_cast<float4*>(dst)[c] = reinterpret_cast<const float4*>(src)[c];
   else dst[c] = src[c];
+}
+// `n_rows` rows per batch item, in [B, n_in, D] -> out [B, n_out, D]
+template <typename IndexT>
+int launch_copy_rows(const float* in, float* out, const IndexT* iidx, const IndexT* oidx, int64_t n_in, int64_t n_out, int64_t n_rows,
+                     int64_t B, int64_t D, hipStream_t s) {
+  const int64_t total = B * n_rows * (D % 4 == 0 ? D / 4 : D);
+  if (total == 0) return BSMS_OK;
+  return launch(k_copy_rows<IndexT>, total, 1, s, in, out, iidx, oidx, n_in * D, n_out * D, (int32_t)n_rows, (int32_t)B, (int32_t)D);
 }
 
 __global__ __launch_bounds__(256) void k_cal_ew_nodes(const int32_t* rowptr, const int32_t* src,
@@ -440,49 +445,42 @@ __global__ __launch_bounds__(256) void k_cal_ew_edges(const int32_t* src, const 
   ec[perm[q]] = __fdiv_rn(__fdiv_rn(w[i], deg), aggr_w[dst[q]]);   // ops/basic.py:165
 }
 
+// The sum of a plan's edge rows x [B,E,D] (plan order) into its node rows out [B,N,D]: over the slots of each TARGET, which are
+// contiguous in plan order (PlanOrder), or of each SOURCE, through the transpose CSR (BySource)
+enum class Csr { PlanOrder, BySource };
+RowSumArgs plan_args(const bsms_plan* p, Csr csr, const float* x, float* out, int64_t B, int64_t D) {
+  RowSumArgs a{};
+  a.rowptr = csr == Csr::BySource ? p->t_rowptr : p->rowptr;
+  a.xidx = csr == Csr::BySource ? p->t_pos : nullptr;
+  a.x = x; a.out = out;
+  a.x_bstride = p->E * D; a.out_bstride = p->N * D;
+  a.n_out = (int32_t)p->N; a.B = (int32_t)B; a.D = (int32_t)D;
+  return a;
+}
+
 }  // namespace
 
 // Exposed to the other translation units of the library (gmp.hip): plan-order segment sums.
 namespace bsms {
 int rowsum_plan_order(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* out, hipStream_t s) {
-  RowSumArgs a{};
-  a.rowptr = p->rowptr;
-  a.x = x; a.out = out;
-  a.x_bstride = p->E * D; a.out_bstride = p->N * D;
-  a.n_out = (int32_t)p->N; a.B = (int32_t)B; a.D = (int32_t)D;
-  return launch_rowsum(a, s);
+  return launch_rowsum(plan_args(p, Csr::PlanOrder, x, out, B, D), s);
 }
 // the same with bf16 messages (bf16 precision of the GMP block): D = 128 / 256 only
 int rowsum_plan_order_bf16(const bsms_plan* p, const float* x_bf16, int64_t B, int64_t D, float* out, hipStream_t s) {
   BSMS_REQUIRE(D == 128 || D == 256, BSMS_E_UNSUPPORTED, "bf16 aggregation: D=%lld (128, 256)", (long long)D);
-  RowSumArgs a{};
-  a.rowptr = p->rowptr;
-  a.x = x_bf16; a.out = out;
-  a.x_bstride = p->E * D; a.out_bstride = p->N * D;
-  a.n_out = (int32_t)p->N; a.B = (int32_t)B; a.D = (int32_t)D;
+  const RowSumArgs a = plan_args(p, Csr::PlanOrder, x_bf16, out, B, D);
   const int64_t workers = B * p->N;
   if (workers == 0) return BSMS_OK;
   const int lpr = int(D / 8);   // eight features per lane
-  const dim3 grid((unsigned)ceil_div(workers * lpr, 256));
-  const bool deep = workers * (D / 4) < kDeepBelowThreads;   // the same levels as the fp32 kernel
-  if (D == 128) {
-    if (deep) hipLaunchKernelGGL((k_rowsum_bf16in<16, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_rowsum_bf16in<16, false>), grid, dim3(256), 0, s, a);
-  } else {
-    if (deep) hipLaunchKernelGGL((k_rowsum_bf16in<32, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_rowsum_bf16in<32, false>), grid, dim3(256), 0, s, a);
-  }
-  BSMS_LAUNCH_CHECK();
-  return BSMS_OK;
+  int rc = BSMS_OK;
+  pick<16, 32>(lpr, [&](auto L) { pick(deep_regime(workers, D / 4), [&](auto deep) {   // the same levels as the fp32 kernel
+    rc = launch(k_rowsum_bf16in<decltype(L)::value, decltype(deep)::value>, workers * lpr, 1, s, a);
+  }); });
+  return rc;
 }
 // out[b, i, :] = sum over edges whose SOURCE is i of x[b, slot(e), :]   (x in plan order)
 int rowsum_by_source(const bsms_plan* p, const float* x, int64_t B, int64_t D, float* out, hipStream_t s) {
-  RowSumArgs a{};
-  a.rowptr = p->t_rowptr; a.xidx = p->t_pos;
-  a.x = x; a.out = out;
-  a.x_bstride = p->E * D; a.out_bstride = p->N * D;
-  a.n_out = (int32_t)p->N; a.B = (int32_t)B; a.D = (int32_t)D;
-  return launch_rowsum(a, s);
+  return launch_rowsum(plan_args(p, Csr::BySource, x, out, B, D), s);
 }
 // by source and by target at once + the narrow weight-gradient partials (see k_rowsum_pair_fiber); returns the number
 // of partial blocks in *nwg, or 0 there if this shape is not built (the caller then runs the separate kernels)
@@ -495,32 +493,14 @@ int rowsum_source_target_fiber(const bsms_plan* p, const float* x, int64_t B, in
   const int64_t blocks = ceil_div(workers * lpr, 256);
   const int64_t tgt_blocks = std::min<int64_t>(blocks, std::min<int64_t>(part_blocks, 1024));   // = partial blocks to reduce
   if (workers == 0 || (D != 128 && D != 256) || ncols < 1 || ncols > 4 || (ld & 3) || tgt_blocks < 1) return BSMS_OK;
-  RowSumArgs a0{}, a1{};
-  a0.rowptr = p->t_rowptr; a0.xidx = p->t_pos;
-  a1.rowptr = p->rowptr;
-  a0.x = a1.x = x; a0.out = outS; a1.out = outD;
-  a0.x_bstride = a1.x_bstride = p->E * D; a0.out_bstride = a1.out_bstride = p->N * D;
-  a0.n_out = a1.n_out = (int32_t)p->N; a0.B = a1.B = (int32_t)B; a0.D = a1.D = (int32_t)D;
-  const dim3 grid((unsigned)(blocks + tgt_blocks));
-  const bool deep = workers * lpr < kDeepBelowThreads;
-  const int nsrc = (int)blocks;
-#define BSMS_PF(L, NS)                                                                                                                 \
-  do {                                                                                                                                 \
-    if (x_bf16) {                                                                                                                      \
-      if (deep) hipLaunchKernelGGL((k_rowsum_pair_fiber<L, NS, true, true>), grid, dim3(256), 0, s, a0, a1, fiber, ld, part, nsrc);    \
-      else hipLaunchKernelGGL((k_rowsum_pair_fiber<L, NS, false, true>), grid, dim3(256), 0, s, a0, a1, fiber, ld, part, nsrc);        \
-    } else if (deep) hipLaunchKernelGGL((k_rowsum_pair_fiber<L, NS, true>), grid, dim3(256), 0, s, a0, a1, fiber, ld, part, nsrc);     \
-    else hipLaunchKernelGGL((k_rowsum_pair_fiber<L, NS, false>), grid, dim3(256), 0, s, a0, a1, fiber, ld, part, nsrc);                \
-  } while (0)
-  if (D == 128) {
-    if (ncols == 1) BSMS_PF(32, 1); else if (ncols == 2) BSMS_PF(32, 2); else if (ncols == 3) BSMS_PF(32, 3); else BSMS_PF(32, 4);
-  } else {
-    if (ncols == 1) BSMS_PF(64, 1); else if (ncols == 2) BSMS_PF(64, 2); else if (ncols == 3) BSMS_PF(64, 3); else BSMS_PF(64, 4);
-  }
-#undef BSMS_PF
-  BSMS_LAUNCH_CHECK();
-  *nwg = (int)tgt_blocks;
-  return BSMS_OK;
+  const RowSumArgs a0 = plan_args(p, Csr::BySource, x, outS, B, D), a1 = plan_args(p, Csr::PlanOrder, x, outD, B, D);
+  int rc = BSMS_OK;
+  pick<32, 64>(lpr, [&](auto L) { pick<1, 2, 3, 4>(ncols, [&](auto NS) { pick(deep_regime(workers, lpr), [&](auto deep) { pick(x_bf16, [&](auto xbf) {
+    rc = launch(k_rowsum_pair_fiber<decltype(L)::value, decltype(NS)::value, decltype(deep)::value, decltype(xbf)::value>,
+                (blocks + tgt_blocks) * 256, 1, s, a0, a1, fiber, ld, part, (int)blocks);
+  }); }); }); });
+  if (rc == BSMS_OK) *nwg = (int)tgt_blocks;
+  return rc;
 }
 // by source and by target at once: outS[b,i,:] = sum_{e: src(e)=i} x[b,slot(e),:], outD[b,j,:] = sum_{e: dst(e)=j} x[b,slot(e),:]
 // `x_bf16`: x holds bf16 rows (D = 128 / 256 only); the sums and both outputs are fp32
@@ -530,33 +510,17 @@ int rowsum_source_and_target(const bsms_plan* p, const float* x, int64_t B, int6
     int rc = rowsum_by_source(p, x, B, D, outS, s);
     return rc ? rc : rowsum_plan_order(p, x, B, D, outD, s);
   }
-  RowSumArgs a0{}, a1{};
-  a0.rowptr = p->t_rowptr; a0.xidx = p->t_pos;
-  a1.rowptr = p->rowptr;
-  a0.x = a1.x = x; a0.out = outS; a1.out = outD;
-  a0.x_bstride = a1.x_bstride = p->E * D; a0.out_bstride = a1.out_bstride = p->N * D;
-  a0.n_out = a1.n_out = (int32_t)p->N; a0.B = a1.B = (int32_t)B; a0.D = a1.D = (int32_t)D;
+  const RowSumArgs a0 = plan_args(p, Csr::BySource, x, outS, B, D), a1 = plan_args(p, Csr::PlanOrder, x, outD, B, D);
   const int64_t workers = B * p->N;
   if (workers == 0) return BSMS_OK;
-  if (x_bf16) {   // the lanes per row, and the DEEP levels, of the fused pair kernel the live path runs
-    const int lpr = int(D / 4);
-    const dim3 gridb((unsigned)ceil_div(workers * lpr, 256), 2);
-    const bool deep = workers * lpr < kDeepBelowThreads;
-    if (D == 128) {
-      if (deep) hipLaunchKernelGGL((k_rowsum_pair_bf16<32, true>), gridb, dim3(256), 0, s, a0, a1);
-      else hipLaunchKernelGGL((k_rowsum_pair_bf16<32, false>), gridb, dim3(256), 0, s, a0, a1);
-    } else {
-      if (deep) hipLaunchKernelGGL((k_rowsum_pair_bf16<64, true>), gridb, dim3(256), 0, s, a0, a1);
-      else hipLaunchKernelGGL((k_rowsum_pair_bf16<64, false>), gridb, dim3(256), 0, s, a0, a1);
-    }
-    BSMS_LAUNCH_CHECK();
-    return BSMS_OK;
-  }
-  const dim3 grid((unsigned)ceil_div(workers * 32, 256), 2);
-  if (workers * 32 < kDeepBelowThreads) hipLaunchKernelGGL((k_rowsum_pair<32, true>), grid, dim3(256), 0, s, a0, a1);
-  else hipLaunchKernelGGL((k_rowsum_pair<32, false>), grid, dim3(256), 0, s, a0, a1);
-  BSMS_LAUNCH_CHECK();
-  return BSMS_OK;
+  const int lpr = int(D / 4);   // bf16: the lanes per row, and the DEEP levels, of the fused pair kernel the live path runs
+  int rc = BSMS_OK;
+  pick(deep_regime(workers, lpr), [&](auto deep) {
+    constexpr bool DEEP = decltype(deep)::value;
+    if (x_bf16) pick<32, 64>(lpr, [&](auto L) { rc = launch(k_rowsum_pair_bf16<decltype(L)::value, DEEP>, workers * lpr, 2, s, a0, a1); });
+    else rc = launch(k_rowsum_pair<32, DEEP>, workers * lpr, 2, s, a0, a1);
+  });
+  return rc;
 }
 }  // namespace bsms
 
@@ -564,12 +528,8 @@ extern "C" int bsms_segment_sum_fwd(const bsms_plan_t* p, const float* src, int6
                                     float* out, bsms_stream_t stream) {
   BSMS_REQUIRE(p && out && (src || p->E == 0), BSMS_E_INVALID_ARG, "segment_sum_fwd: null argument");
   BSMS_REQUIRE(B >= 0 && D >= 1, BSMS_E_SHAPE, "segment_sum_fwd: bad B=%lld D=%lld", (long long)B, (long long)D);
-  RowSumArgs a{};
-  a.rowptr = p->rowptr;
-  a.xidx = plan_order ? nullptr : p->perm;
-  a.x = src; a.out = out;
-  a.x_bstride = p->E * D; a.out_bstride = p->N * D;
-  a.n_out = (int32_t)p->N; a.B = (int32_t)B; a.D = (int32_t)D;
+  RowSumArgs a = plan_args(p, Csr::PlanOrder, src, out, B, D);
+  if (!plan_order) a.xidx = p->perm;   // src in the caller's edge order
   return launch_rowsum(a, as_stream(stream));
 }
 
@@ -584,14 +544,7 @@ extern "C" int bsms_segment_sum_bwd(const bsms_plan_t* p, const float* grad_out,
                                     float* grad_src, bsms_stream_t stream) {
   BSMS_REQUIRE(p && grad_out && (grad_src || p->E == 0), BSMS_E_INVALID_ARG, "segment_sum_bwd: null argument");
   BSMS_REQUIRE(B >= 0 && D >= 1, BSMS_E_SHAPE, "segment_sum_bwd: bad B/D");
-  const int per_row = (D % 4 == 0) ? int(D / 4) : int(D);
-  const int64_t total = B * p->E * per_row;
-  if (total == 0) return BSMS_OK;
-  hipLaunchKernelGGL((k_copy_rows<int32_t>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(stream),
-                     grad_out, grad_src, (const int32_t*)p->dst, (const int32_t*)p->perm, p->N * D, p->E * D,
-                     (int32_t)p->E, (int32_t)B, (int32_t)D);
-  BSMS_LAUNCH_CHECK();
-  return BSMS_OK;
+  return launch_copy_rows<int32_t>(grad_out, grad_src, p->dst, p->perm, p->N, p->E, p->E, B, D, as_stream(stream));
 }
 
 extern "C" int bsms_cal_ew(const bsms_plan_t* p, const float* w, float* ec, float* aggr_w, bsms_stream_t stream) {
@@ -624,65 +577,54 @@ __global__ __launch_bounds__(256) void k_bind_ew(const float* ew, const int32_t*
 // the part; every array of the part is copied to its place in the union with the offsets of common.h: CatPart added.  Entry N_b of
 // a part's rowptr arrays coincides with entry 0 of the next part's (same value): a benign double write.
 namespace {
-struct PlanView {
-  const int32_t *rowptr, *t_rowptr, *src, *dst, *perm, *t_dst, *t_eid, *t_pos;
-  const int32_t *ids, *inv, *k_rowptr, *k_src, *k_eid, *p_rowptr, *p_src, *p_eid, *k_w, *p_w;
+// the arrays of both blocks of a plan (common.h: the layout); the pool half is only read when there is a pool block
+template <class I>
+struct PlanView : MainPtrs<I>, PoolPtrs<I> {
+  __device__ PlanView(I* blk, I* pool, int32_t N, int32_t E, int32_t Nk, int32_t Ek, int32_t Ep)
+      : MainPtrs<I>(main_ptrs(blk, N, E)), PoolPtrs<I>(pool_ptrs(pool, N, Nk, Ek, Ep)) {}
 };
-__device__ __forceinline__ PlanView view_of(const int32_t* blk, const int32_t* pool, int64_t N, int64_t E, int64_t Nk, int64_t Ek, int64_t Ep) {
-  PlanView v;
-  const size_t nN = idx_pad(size_t(N) + 1), nE = idx_pad(size_t(E));
-  v.rowptr = blk; v.t_rowptr = blk + nN; v.src = v.t_rowptr + nN; v.dst = v.src + nE; v.perm = v.dst + nE;
-  v.t_dst = v.perm + nE; v.t_eid = v.t_dst + nE; v.t_pos = v.t_eid + nE;
-  const size_t nK = idx_pad(size_t(Nk)), nNinv = idx_pad(size_t(N)), nK1 = idx_pad(size_t(Nk) + 1), nEk = idx_pad(size_t(Ek)), nEp = idx_pad(size_t(Ep));
-  v.ids = pool; v.inv = pool + nK; v.k_rowptr = v.inv + nNinv; v.k_src = v.k_rowptr + nK1; v.k_eid = v.k_src + nEk;
-  v.p_rowptr = v.k_eid + nEk; v.p_src = v.p_rowptr + nN; v.p_eid = v.p_src + nEp; v.k_w = v.p_eid + nEp; v.p_w = v.k_w + nEk;
-  return v;
-}
 __global__ __launch_bounds__(256) void k_plan_concat(bsms::CatArgs a) {
   const bsms::CatPart c = a.part[blockIdx.y];
-  const PlanView in = view_of(c.blk, c.pool, c.N, c.E, c.Nk, c.Ek, c.Ep);
-  const PlanView o = view_of(a.out_blk, a.out_pool, a.N, a.E, a.Nk, a.Ek, a.Ep);
-  int32_t* const* ow = reinterpret_cast<int32_t* const*>(&o);   // (the union's arrays are written: same layout, mutable block)
-  auto W = [&](const int32_t* field) { return const_cast<int32_t*>(field); };
-  (void)ow;
+  const PlanView<const int32_t> in(c.blk, c.pool, c.N, c.E, c.Nk, c.Ek, c.Ep);
+  const PlanView<int32_t> o(a.out_blk, a.out_pool, a.N, a.E, a.Nk, a.Ek, a.Ep);   // the union's arrays are written: same layout, mutable block
   const int longest = max(max(c.N + 1, c.E), max(max(c.Nk + 1, c.Ek), c.Ep));
   const bool pooled = a.out_pool != nullptr;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < longest; i += gridDim.x * blockDim.x) {
     if (i <= c.N) {
-      W(o.rowptr)[c.n_off + i] = in.rowptr[i] + c.e_off;
-      W(o.t_rowptr)[c.n_off + i] = in.t_rowptr[i] + c.e_off;
-      if (pooled) W(o.p_rowptr)[c.n_off + i] = in.p_rowptr[i] + c.ep_off;
+      o.rowptr[c.n_off + i] = in.rowptr[i] + c.e_off;
+      o.t_rowptr[c.n_off + i] = in.t_rowptr[i] + c.e_off;
+      if (pooled) o.p_rowptr[c.n_off + i] = in.p_rowptr[i] + c.ep_off;
     }
     if (i < c.N && pooled) {
       const int32_t v = in.inv[i];
-      W(o.inv)[c.n_off + i] = v < 0 ? -1 : v + c.k_off;
+      o.inv[c.n_off + i] = v < 0 ? -1 : v + c.k_off;
     }
     if (i < c.E) {
       const int32_t sq = in.src[i] + c.n_off, dq = in.dst[i] + c.n_off, pq = in.perm[i] + c.e_off;
-      W(o.src)[c.e_off + i] = sq;
-      W(o.dst)[c.e_off + i] = dq;
-      W(o.perm)[c.e_off + i] = pq;
-      W(o.t_dst)[c.e_off + i] = in.t_dst[i] + c.n_off;
-      W(o.t_eid)[c.e_off + i] = in.t_eid[i] + c.e_off;
-      W(o.t_pos)[c.e_off + i] = in.t_pos[i] + c.e_off;
+      o.src[c.e_off + i] = sq;
+      o.dst[c.e_off + i] = dq;
+      o.perm[c.e_off + i] = pq;
+      o.t_dst[c.e_off + i] = in.t_dst[i] + c.n_off;
+      o.t_eid[c.e_off + i] = in.t_eid[i] + c.e_off;
+      o.t_pos[c.e_off + i] = in.t_pos[i] + c.e_off;
       if (a.coo_out) { a.coo_out[pq] = sq; a.coo_out[int64_t(a.E) + pq] = dq; }   // plan slot -> the caller's edge id
     }
     if (pooled) {
-      if (i <= c.Nk) W(o.k_rowptr)[c.k_off + i] = in.k_rowptr[i] + c.ek_off;
+      if (i <= c.Nk) o.k_rowptr[c.k_off + i] = in.k_rowptr[i] + c.ek_off;
       if (i < c.Nk) {
         const int32_t v = in.ids[i] + c.n_off;
-        W(o.ids)[c.k_off + i] = v;
+        o.ids[c.k_off + i] = v;
         if (a.ids_out) a.ids_out[c.k_off + i] = v;
       }
       if (i < c.Ek) {
-        W(o.k_src)[c.ek_off + i] = in.k_src[i] + c.n_off;
-        W(o.k_eid)[c.ek_off + i] = in.k_eid[i] + c.e_off;
-        if (a.has_w) W(o.k_w)[c.ek_off + i] = in.k_w[i];
+        o.k_src[c.ek_off + i] = in.k_src[i] + c.n_off;
+        o.k_eid[c.ek_off + i] = in.k_eid[i] + c.e_off;
+        if (a.has_w) o.k_w[c.ek_off + i] = in.k_w[i];
       }
       if (i < c.Ep) {
-        W(o.p_src)[c.ep_off + i] = in.p_src[i] + c.k_off;   // COARSE row of the target
-        W(o.p_eid)[c.ep_off + i] = in.p_eid[i] + c.e_off;
-        if (a.has_w) W(o.p_w)[c.ep_off + i] = in.p_w[i];
+        o.p_src[c.ep_off + i] = in.p_src[i] + c.k_off;   // COARSE row of the target
+        o.p_eid[c.ep_off + i] = in.p_eid[i] + c.e_off;
+        if (a.has_w) o.p_w[c.ep_off + i] = in.p_w[i];
       }
     }
   }
@@ -772,24 +714,12 @@ extern "C" int bsms_scatter_rows(const float* h, int64_t B, int64_t Nk, int64_t 
   BSMS_REQUIRE(B >= 0 && Nk >= 0 && N >= 0 && D >= 1, BSMS_E_SHAPE, "scatter_rows: bad shape");
   hipStream_t s = as_stream(stream);
   if (B * N * D > 0) BSMS_HIP_CHECK(hipMemsetAsync(out, 0, size_t(B) * N * D * sizeof(float), s));
-  const int per_row = (D % 4 == 0) ? int(D / 4) : int(D);
-  const int64_t total = B * Nk * per_row;
-  if (total == 0) return BSMS_OK;
-  hipLaunchKernelGGL((k_copy_rows<int64_t>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, h, out,
-                     (const int64_t*)nullptr, idx, Nk * D, N * D, (int32_t)Nk, (int32_t)B, (int32_t)D);
-  BSMS_LAUNCH_CHECK();
-  return BSMS_OK;
+  return launch_copy_rows<int64_t>(h, out, nullptr, idx, Nk, N, Nk, B, D, s);
 }
 
 extern "C" int bsms_gather_rows(const float* x, int64_t B, int64_t N, int64_t D, const int64_t* idx, int64_t Nk,
                                 float* out, bsms_stream_t stream) {
   BSMS_REQUIRE((out && x && idx) || Nk == 0, BSMS_E_INVALID_ARG, "gather_rows: null argument");
   BSMS_REQUIRE(B >= 0 && Nk >= 0 && N >= 0 && D >= 1, BSMS_E_SHAPE, "gather_rows: bad shape");
-  const int per_row = (D % 4 == 0) ? int(D / 4) : int(D);
-  const int64_t total = B * Nk * per_row;
-  if (total == 0) return BSMS_OK;
-  hipLaunchKernelGGL((k_copy_rows<int64_t>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(stream), x,
-                     out, idx, (const int64_t*)nullptr, N * D, Nk * D, (int32_t)Nk, (int32_t)B, (int32_t)D);
-  BSMS_LAUNCH_CHECK();
-  return BSMS_OK;
+  return launch_copy_rows<int64_t>(x, out, idx, nullptr, N, Nk, Nk, B, D, as_stream(stream));
 }

@@ -240,9 +240,9 @@ def test_adamw_bitwise_repeatable(eng):
 
 
 # ==================================================================================================== B: row sums, both launch regimes
-# csrc/rowsum.hip: `constexpr int64_t kDeepBelowThreads = 400 * 1024`.  launch_rowsum_wm gives a row L lanes (the power of two >= D/4,
-# at most 64) and launches the DEEP instantiation (batches of 32 slots, then 8, then the tail) iff workers * L < kDeepBelowThreads,
-# with workers = B * n_out; rowsum_plan_order_bf16 takes the same decision from workers * D/4.
+# csrc/rowsum.hip: `constexpr int64_t kDeepBelowThreads = 400 * 1024`.  launch_rowsum gives a row L lanes (the power of two >= D/4,
+# at most 64) and launches the DEEP instantiation (batches of 32 slots, then 8, then the tail) iff deep_regime(workers, L), that is
+# workers * L < kDeepBelowThreads, with workers = B * n_out; rowsum_plan_order_bf16 takes the same decision from workers * D/4.
 DEEP_BELOW = 400 * 1024
 HUB_DEG = 6 * 32 + 16 + 8 + 5              # one row with 32-slot batches (16-slot ones in the bf16 kernel), then 8-slot batches, then a tail
 LAT_N = 1531
